@@ -1391,6 +1391,32 @@ def emit(obj):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, line)
 
 
+DUMP_SIGNATURES = 32            # witness / instance rows written by --dump-outputs
+DUMP_WITNESS_ELEMENTS = 16384   # witness elements per row: 32 x 16,384 x 64 B = 33.5 MB, + 4.2 MB of instances (Falcon-1024)
+
+
+def dump_outputs(path, world, rank, lo, d_wit, d_inst, d_st, slot_sig, held):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, as float64 .npy files under `path`, for
+    output-for-output comparison of two builds.  The whole step's statuses, and a fixed, seeded sample of the witness buffer
+    as the timed launches left it: DUMP_SIGNATURES slots, each with its whole instance vector and DUMP_WITNESS_ELEMENTS
+    witness elements.  A field element (4 x u64 Montgomery limbs) is written as its 8 little-endian 32-bit halves, so
+    float64 holds it exactly; `sample_signature_index` (global) and `witness_element_index` say which rows and columns were taken."""
+    rng = np.random.default_rng(SEED)
+    slots = np.sort(rng.choice(held, min(held, DUMP_SIGNATURES), replace=False))
+    cols = np.sort(rng.choice(d_wit.shape[1], min(d_wit.shape[1], DUMP_WITNESS_ELEMENTS), replace=False))
+    s = torch.from_numpy(slots).to(d_wit.device)
+    wit = d_wit[s[:, None], torch.from_numpy(cols).to(d_wit.device)[None, :]].cpu().numpy()
+    inst = d_inst.index_select(0, s).cpu().numpy()
+    halves = lambda a: a.view(np.uint32).reshape(a.shape[:-1] + (8,)).astype(np.float64)
+    out = {"status": d_st.cpu().numpy().astype(np.float64),
+           "witness": halves(wit), "instance": halves(inst),
+           "sample_signature_index": (lo + slot_sig[slots]).astype(np.float64),
+           "witness_element_index": cols.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, "%s%s.npy" % (name, ".rank%d" % rank if world > 1 else "")), a)
+
+
 def gather_leg(args, plan, eng, dev, cdev, world, rank, logn, batch, chunk, L, d_in, d_wit, d_st, stream):
     """Second curve (north_star / BASELINE configs[3]): generate + all-gather of the per-signature witness vectors for a
     FULL step, every chunk.  MI355X-first form: each rank generates its chunk in FRW_ENC_COMPACT (0.51 MB per signature
@@ -1612,7 +1638,14 @@ def main():
     ap.add_argument("--dump-digests", default="",
                     help="after the run, write this rank's per-signature (global index, status, witness digest) of one "
                          "extra, untimed pass to PATH.rank<r>.npy (multi-rank consistency tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed -- statuses, and a fixed, seeded sample of the "
+                         "witnesses and instances -- as float64 DIR/<name>.npy (< 64 MB; verify workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "verify":
+        ap.error("--dump-outputs is implemented for --workload verify only")
     if args.plan:
         return print_plans(args, ap.get_default("gpus") != args.gpus)
 
@@ -1729,6 +1762,8 @@ def main():
     slot_sig = np.arange(held, dtype=np.int64) + last_a
     if held > last_cnt:
         slot_sig[last_cnt:] = np.arange(last_cnt, held) + (nchunks - 2) * chunk
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, world, rank, lo, d_wit, d_inst, d_st, slot_sig, held)
     d_dig = torch.zeros(held, dtype=torch.int64, device=dev)
     eng.digest_dev(d_wit, L.num_witness * 4, held, d_dig, stream.cuda_stream)
     torch.cuda.synchronize()

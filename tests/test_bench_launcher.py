@@ -98,3 +98,41 @@ def test_ranks_do_not_outlive_an_interrupted_launcher(tmp_path):
         except (ProcessLookupError, FileNotFoundError):
             alive = False
         assert not alive, "rank %d outlived its launcher" % pid
+
+
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs on CPU tensors of the Falcon-1024 shapes: float64 files that give back every sampled 64-bit limb
+    exactly, the same sample twice, under 64 MB with the default batch's status vector."""
+    code = r"""
+import os, sys, numpy as np, torch
+sys.argv = ["bench.py"]
+sys.path.insert(0, %r)
+import bench
+held, nw, ni, batch, lo = 33, 156724, 2049, 65536, 1000
+g = torch.Generator().manual_seed(5)
+wit = torch.randint(-2**62, 2**62, (held, nw, 4), generator=g, dtype=torch.int64)
+inst = torch.randint(-2**62, 2**62, (held, ni, 4), generator=g, dtype=torch.int64)
+st = torch.randint(0, 3, (batch,), generator=g, dtype=torch.int32)
+slot_sig = np.arange(held) + 7
+for d in ("a", "b"):
+    bench.dump_outputs(os.path.join(%r, d), 1, 0, lo, wit, inst, st, slot_sig, held)
+def limbs(a):
+    u = a.astype(np.uint64)
+    return (u[..., 0::2] | (u[..., 1::2] << np.uint64(32))).view(np.int64)
+out = {n[:-4]: np.load(os.path.join(%r, "a", n)) for n in os.listdir(os.path.join(%r, "a"))}
+assert sorted(out) == ["instance", "sample_signature_index", "status", "witness", "witness_element_index"], sorted(out)
+assert all(a.dtype == np.float64 for a in out.values())
+assert sum(a.nbytes for a in out.values()) < 64 << 20
+rows = out["sample_signature_index"].astype(np.int64) - lo - 7
+cols = out["witness_element_index"].astype(np.int64)
+assert len(rows) == 32 and len(set(rows)) == 32 and len(cols) == bench.DUMP_WITNESS_ELEMENTS
+assert np.array_equal(limbs(out["witness"]), wit.numpy()[rows][:, cols])
+assert np.array_equal(limbs(out["instance"]), inst.numpy()[rows])
+assert np.array_equal(out["status"], st.numpy())
+for n, a in out.items():
+    assert np.array_equal(a, np.load(os.path.join(%r, "b", n + ".npy"))), n
+print("ok")
+""" % ((ROOT,) + (str(tmp_path),) * 4)
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=600,
+                         env=_env_without_launcher())
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr[-3000:]

@@ -130,6 +130,12 @@ PROTOTYPES = {
     "frw_groth16_vk_load": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "frw_groth16_vk_free": (None, [C.c_void_p]),
     "frw_groth16_verify": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "frw_groth16_vk_load_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_groth16_verify_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "frw_groth16_prepare_inputs_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p]),
+    "frw_groth16_verify_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
     "frw_diag_pairing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_compact_layout": (C.c_int, [C.c_int, C.POINTER(CompactLayoutStruct)]),
     "frw_witness_ntt_verify_compact_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,

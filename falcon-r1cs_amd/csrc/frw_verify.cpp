@@ -2,6 +2,8 @@
 // verify_proof_with_prepared_inputs) -- what examples/pok_sig.rs:34-47 ends with.  HOST code, like the reference's: one
 // proof is a 2N-term sum of small multiples of the key's gamma_abc points, three Miller loops and one final exponentiation,
 // ~15 ms on one core; a batch runs one proof per host thread.  The device is not involved and need not be present.
+// frw_verify_dev.hip is the same verifier with prepare_inputs (and the key's gamma_abc_g1 checks) on the device: everything after
+// prepare_inputs is verify_prepared below, shared by both.
 #include <stdint.h>
 #include <algorithm>
 #include <atomic>
@@ -13,25 +15,15 @@
 
 #include "../../include/frw.h"
 #include "frw_pairing.h"
+#include "frw_verify.h"
 #include "host/frw_host.hpp"
 
 namespace {
 using namespace frw;
 using namespace frw::pairing;
 using frw::host::Fr;
+using namespace frw::verify;
 
-// ark-ff affine point (x | y, 6 x u64 each, x 2^384; all zero = the point at infinity) -> both forms used here
-G1Affine29 g1_lazy_from_ark(const uint64_t *w)
-{
-    G1Affine29 p;
-    uint64_t any = 0;
-    for (int k = 0; k < 12; k++) any |= w[k];
-    p.inf = any == 0;
-    p.x = fq_canonical(fq_from_ark((const uint32_t *)w));
-    p.y = fq_canonical(fq_from_ark((const uint32_t *)(w + 6)));
-    return p;
-}
-G1 g1_strict(const G1Affine29 &p) { G1 r; r.x.v = fq_canonical(p.x); r.y.v = fq_canonical(p.y); r.inf = p.inf; return r; }
 G2 g2_from_ark(const uint64_t *w)
 {
     G2 p;
@@ -44,41 +36,11 @@ G2 g2_from_ark(const uint64_t *w)
 }
 G2 g2_neg(const G2 &p) { G2 r = p; r.y = fp2_neg(p.y); return r; }
 
-// r P = O?  (r = the group order: the scalar field's modulus)
-template <class F> bool in_subgroup(const AffineT<F> &p)
-{
-    if (p.inf) return true;
-    XyzzT<F> acc = pt_identity<F>();
-    for (int bit = 254; bit >= 0; bit--) {
-        acc = pt_double(acc);
-        if ((Fr::P[bit >> 6] >> (bit & 63)) & 1ull) acc = pt_add_affine(acc, p);
-    }
-    return acc.inf || F::is_zero(acc.zz);
-}
 AffineT<Fq2Field> g2_lazy(const G2 &p)
 {
     AffineT<Fq2Field> r;
     r.x.c0 = p.x.c0.v; r.x.c1 = p.x.c1.v; r.y.c0 = p.y.c0.v; r.y.c1 = p.y.c1.v; r.inf = p.inf;
     return r;
-}
-
-// ark's deserialiser rejects a field element whose representation is not below the modulus; raw limbs are taken here, so the
-// same is asked of them BEFORE any arithmetic reduces them silently (x and x + q would otherwise be one point with two encodings)
-constexpr uint64_t FQ_MODULUS[6] = {0xb9feffffffffaaabULL, 0x1eabfffeb153ffffULL, 0x6730d2a0f6b0f624ULL,
-                                    0x64774b84f38512bfULL, 0x4b1ba7b6434bacd7ULL, 0x1a0111ea397fe69aULL};
-bool fq_limbs_below_modulus(const uint64_t *w)
-{
-    for (int k = 5; k >= 0; k--) {
-        if (w[k] < FQ_MODULUS[k]) return true;
-        if (w[k] > FQ_MODULUS[k]) return false;
-    }
-    return false;
-}
-bool coordinates_canonical(const uint64_t *w, int coordinates)
-{
-    for (int k = 0; k < coordinates; k++)
-        if (!fq_limbs_below_modulus(w + 6 * k)) return false;
-    return true;
 }
 
 int bit_length(const uint64_t c[4])
@@ -87,29 +49,18 @@ int bit_length(const uint64_t c[4])
         if (c[k]) return 64 * k + 64 - __builtin_clzll(c[k]);
     return 0;
 }
-bool below_modulus(const uint64_t c[4])
-{
-    for (int k = 3; k >= 0; k--) {
-        if (c[k] < Fr::P[k]) return true;
-        if (c[k] > Fr::P[k]) return false;
-    }
-    return false;
-}
+bool below_modulus(const uint64_t c[4]) { return fr_limbs_below_modulus(c); }
 }  // namespace
-
-struct frw_groth16_vk {
-    size_t num_instance;
-    std::vector<G1Affine29> gamma_abc;
-    G2 gamma_neg, delta_neg;
-    Fp12 alpha_beta;                        // final_exponentiation(miller_loop(alpha_g1, beta_g2))
-    FrobeniusConstants fc;
-};
 
 extern "C" int frw_groth16_vk_load(const uint64_t *vk, size_t num_instance, frw_groth16_vk **out)
 {
     return frw_groth16_vk_load_opts(vk, num_instance, 0, out);
 }
 extern "C" int frw_groth16_vk_load_opts(const uint64_t *vk, size_t num_instance, int flags, frw_groth16_vk **out)
+{
+    return frw::verify::vk_load(vk, num_instance, (flags & FRW_VK_POINTS_ARE_CHECKED) == 0, out);
+}
+int frw::verify::vk_load(const uint64_t *vk, size_t num_instance, bool check_gamma_abc, frw_groth16_vk **out)
 {
     if (!vk || !out || num_instance == 0) return FRW_E_INVALID_ARG;
     *out = nullptr;
@@ -128,15 +79,14 @@ extern "C" int frw_groth16_vk_load_opts(const uint64_t *vk, size_t num_instance,
         // reads (a ladder per point: a few host threads for the 32,769 points of a sixteen-statement aggregate's key)
         if (ok) {
             const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-            const bool vouched = (flags & FRW_VK_POINTS_ARE_CHECKED) != 0;
+            const bool vouched = !check_gamma_abc;
             const size_t threads = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(num_instance / 256, hw), 64));
             std::atomic<bool> good{true};
             auto work = [&](size_t tid) {
                 for (size_t i = tid; i < num_instance && good; i += threads) {
                     const uint64_t *w = vk + 84 + 12 * i;
-                    if (!coordinates_canonical(w, 2)) { good = false; break; }
+                    if (!coordinates_canonical(w, 2) || (!vouched && !g1_point_valid(w))) { good = false; break; }
                     k->gamma_abc[i] = g1_lazy_from_ark(w);
-                    if (!vouched && (!g1_on_curve(g1_strict(k->gamma_abc[i])) || !in_subgroup(k->gamma_abc[i]))) good = false;
                 }
             };
             std::vector<std::thread> pool;
@@ -208,6 +158,29 @@ G1Xyzz prepare_inputs(const frw_groth16_vk &vk, const std::vector<uint64_t> &can
     return total;
 }
 
+// the proof's points: canonical limbs, on their curves, in the subgroups (unless the caller vouches for that); 0 or -1
+int check_proof(const uint64_t *proof, int flags, G1 &as, G2 &b, G1 &cs)
+{
+    if (!coordinates_canonical(proof, 8)) return -1;                          // A (x, y), B (x.c0, x.c1, y.c0, y.c1), C (x, y)
+    const G1Affine29 a = g1_lazy_from_ark(proof), c = g1_lazy_from_ark(proof + 36);
+    b = g2_from_ark(proof + 12);
+    as = g1_strict(a);
+    cs = g1_strict(c);
+    if (!g1_on_curve(as) || !g2_on_curve(b) || !g1_on_curve(cs)) return -1;
+    if (!(flags & FRW_VERIFY_POINTS_ARE_CHECKED) && (!in_subgroup(a) || !in_subgroup(g2_lazy(b)) || !in_subgroup(c))) return -1;
+    return 0;
+}
+// e(A, B) e(acc, -gamma) e(C, -delta) == e(alpha, beta)
+int pairing_check(const frw_groth16_vk &vk, const G1 &as, const G2 &b, const G1 &acc, const G1 &cs)
+{
+    const G1 ps[3] = {as, acc, cs};
+    const G2 qs[3] = {b, vk.gamma_neg, vk.delta_neg};
+    bool degenerate = false;
+    const Fp12 f = miller_loop(ps, qs, 3, &degenerate);
+    if (degenerate) return -1;              // only a point outside the subgroup gets here (FRW_VERIFY_POINTS_ARE_CHECKED and not true)
+    return fp12_eq(final_exponentiation(f, vk.fc), vk.alpha_beta) ? 1 : 0;
+}
+
 int verify_one(const frw_groth16_vk &vk, const uint64_t *inputs, int encoding, const uint64_t *proof, int flags)
 {
     const size_t n = vk.num_instance;
@@ -219,22 +192,20 @@ int verify_one(const frw_groth16_vk &vk, const uint64_t *inputs, int encoding, c
         else std::memcpy(&canon[4 * i], inputs + 4 * i, 32);
     }
     if (canon[0] != 1 || canon[1] || canon[2] || canon[3]) return -1;         // the instance vector starts with the constant one
-    if (!coordinates_canonical(proof, 8)) return -1;                          // A (x, y), B (x.c0, x.c1, y.c0, y.c1), C (x, y)
-    const G1Affine29 a = g1_lazy_from_ark(proof), c = g1_lazy_from_ark(proof + 36);
-    const G2 b = g2_from_ark(proof + 12);
-    const G1 as = g1_strict(a), cs = g1_strict(c);
-    if (!g1_on_curve(as) || !g2_on_curve(b) || !g1_on_curve(cs)) return -1;
-    if (!(flags & FRW_VERIFY_POINTS_ARE_CHECKED) && (!in_subgroup(a) || !in_subgroup(g2_lazy(b)) || !in_subgroup(c))) return -1;
-    const G1Affine29 acc = g1_to_affine(prepare_inputs(vk, canon));
-    // e(A, B) e(acc, -gamma) e(C, -delta) == e(alpha, beta)
-    const G1 ps[3] = {as, g1_strict(acc), cs};
-    const G2 qs[3] = {b, vk.gamma_neg, vk.delta_neg};
-    bool degenerate = false;
-    const Fp12 f = miller_loop(ps, qs, 3, &degenerate);
-    if (degenerate) return -1;              // only a point outside the subgroup gets here (FRW_VERIFY_POINTS_ARE_CHECKED and not true)
-    return fp12_eq(final_exponentiation(f, vk.fc), vk.alpha_beta) ? 1 : 0;
+    G1 as, cs;
+    G2 b;
+    if (check_proof(proof, flags, as, b, cs)) return -1;
+    return pairing_check(vk, as, b, g1_strict(g1_to_affine(prepare_inputs(vk, canon))), cs);
 }
 }  // namespace
+
+int frw::verify::verify_prepared(const frw_groth16_vk &vk, const uint64_t *prepared, const uint64_t *proof, int flags)
+{
+    G1 as, cs;
+    G2 b;
+    if (check_proof(proof, flags, as, b, cs)) return -1;
+    return pairing_check(vk, as, b, g1_strict(g1_lazy_from_ark(prepared)), cs);
+}
 
 extern "C" int frw_groth16_verify(const frw_groth16_vk *vk, size_t batch, const uint64_t *instance, int encoding,
                                   const uint64_t *proofs, int flags, int32_t *accepted)
@@ -242,29 +213,10 @@ extern "C" int frw_groth16_verify(const frw_groth16_vk *vk, size_t batch, const 
     if (!vk || (batch && (!instance || !proofs || !accepted))) return FRW_E_INVALID_ARG;
     if (encoding != FRW_ENC_MONTGOMERY && encoding != FRW_ENC_CANONICAL) return FRW_E_INVALID_ARG;
     try {
-        const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-        const size_t threads = std::min<size_t>(std::min<size_t>(batch, hw), 32);
-        std::atomic<size_t> next{0};
-        std::atomic<bool> failed{false};
-        auto work = [&]() {
-            try {
-                for (size_t i; (i = next.fetch_add(1)) < batch;)
-                    accepted[i] = verify_one(*vk, instance + i * vk->num_instance * 4, encoding, proofs + i * 48, flags);
-            } catch (...) {
-                failed = true;
-            }
-        };
-        if (threads <= 1) work();
-        else {
-            std::vector<std::thread> pool;
-            try {
-                for (size_t t = 0; t < threads; t++) pool.emplace_back(work);
-            } catch (...) {                                              // no more threads to be had: the ones there are finish the batch
-                if (pool.empty()) work();
-            }
-            for (auto &t : pool) t.join();
-        }
-        return failed ? FRW_E_OUT_OF_MEMORY : FRW_OK;
+        const bool ok = frw::verify::for_each_proof(batch, [&](size_t i) {
+            accepted[i] = verify_one(*vk, instance + i * vk->num_instance * 4, encoding, proofs + i * 48, flags);
+        });
+        return ok ? FRW_OK : FRW_E_OUT_OF_MEMORY;
     } catch (...) {
         return FRW_E_OUT_OF_MEMORY;
     }

@@ -96,11 +96,13 @@ GROTH16_COMBINE_WORKSPACE = 4096
 
 
 class Groth16Verifier:
-    """ark-groth16's prepared verifying key + verify_proof (examples/pok_sig.rs:34-47).  Host code: no device involved.
+    """ark-groth16's prepared verifying key + verify_proof (examples/pok_sig.rs:34-47).  Host code: no device involved -- unless
+    `device` is given: the key is then loaded with frw_groth16_vk_load_dev (every gamma_abc_g1 point checked on that device, no
+    vouching: points_are_checked must stay False) and prepare_inputs_dev / verify_dev run prepare_inputs there.
 
     vk: the dict WitnessEngine.groth16_setup returns, or one flat uint64 array in frw_groth16_setup's vk_out layout."""
 
-    def __init__(self, vk, points_are_checked=False):
+    def __init__(self, vk, points_are_checked=False, device=None):
         self._lib = load_library()
         if isinstance(vk, dict):
             vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
@@ -108,9 +110,15 @@ class Groth16Verifier:
         if vk.size < 96 or (vk.size - 84) % 12:
             raise FrwError("verifying key: expected 84 + 12 x num_instance uint64 values")
         self.num_instance = (vk.size - 84) // 12
+        self.device = device
         self._h = C.c_void_p()
-        check(self._lib.frw_groth16_vk_load_opts(vk.ctypes.data_as(C.c_void_p), self.num_instance, VK_POINTS_ARE_CHECKED if points_are_checked else 0,
-                                                 C.byref(self._h)), "frw_groth16_vk_load")
+        flags = VK_POINTS_ARE_CHECKED if points_are_checked else 0
+        if device is None:
+            check(self._lib.frw_groth16_vk_load_opts(vk.ctypes.data_as(C.c_void_p), self.num_instance, flags, C.byref(self._h)),
+                  "frw_groth16_vk_load")
+        else:
+            check(self._lib.frw_groth16_vk_load_dev(int(device), vk.ctypes.data_as(C.c_void_p), self.num_instance, flags, C.byref(self._h)),
+                  "frw_groth16_vk_load_dev")
 
     def verify(self, instance, proofs, encoding=ENC_MONTGOMERY, flags=0):
         """instance: uint64[batch, num_instance, 4] as the witness entry points write it (the constant one first);
@@ -120,6 +128,42 @@ class Groth16Verifier:
         out = np.zeros(proofs.shape[0], dtype=np.int32)
         check(self._lib.frw_groth16_verify(self._h, proofs.shape[0], instance.ctypes.data_as(C.c_void_p), int(encoding),
                                            proofs.ctypes.data_as(C.c_void_p), int(flags), out.ctypes.data_as(C.c_void_p)), "frw_groth16_verify")
+        return out
+
+    def workspace_bytes(self, batch_in_flight):
+        """Device workspace for `batch_in_flight` proofs (frw_groth16_verify_workspace_bytes; 0 for a host-only key)."""
+        return int(self._lib.frw_groth16_verify_workspace_bytes(self._h, int(batch_in_flight)))
+
+    def _workspace(self, batch, workspace):
+        import torch
+        if workspace is None:
+            workspace = torch.empty(max(self.workspace_bytes(batch), 16), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        return workspace, workspace.numel() * workspace.element_size()
+
+    def prepare_inputs_dev(self, d_instance, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
+        """d_instance: device tensor [batch, num_instance, 4] of 64-bit limbs -> (prepared int64[batch, 12] in ark-ff's bytes,
+        status int32[batch]: 0 or -1 malformed), device tensors, ordered on `stream`."""
+        import torch
+        batch = d_instance.shape[0]
+        dev = d_instance.device
+        prepared = torch.empty((batch, 12), dtype=torch.int64, device=dev)
+        status = torch.empty(batch, dtype=torch.int32, device=dev)
+        ws, ws_bytes = self._workspace(batch, workspace)
+        check(self._lib.frw_groth16_prepare_inputs_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding), C.c_void_p(prepared.data_ptr()),
+                                                       C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_prepare_inputs_dev")
+        return prepared, status
+
+    def verify_dev(self, d_instance, d_proofs, encoding=ENC_MONTGOMERY, flags=0, stream=0, workspace=None):
+        """verify() with the instance vectors [batch, num_instance, 4] and the proofs [batch, 48] in device memory (as the witness and
+        prove entry points write them).  Returns numpy int32[batch], the values verify() gives for the same bytes; synchronises `stream`.
+        workspace: a device tensor (16-byte aligned) or None for one of the whole batch."""
+        batch = d_proofs.shape[0]
+        out = np.zeros(batch, dtype=np.int32)
+        ws, ws_bytes = self._workspace(batch, workspace)
+        check(self._lib.frw_groth16_verify_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding), C.c_void_p(d_proofs.data_ptr()),
+                                               int(flags), out.ctypes.data_as(C.c_void_p), C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_verify_dev")
         return out
 
     def close(self):

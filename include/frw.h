@@ -549,7 +549,7 @@ int frw_groth16_prove_combine_dev(const frw_groth16_pk *pk, size_t world, const 
  * ark-groth16 0.3.0 verifier.rs: prepare_verifying_key (e(alpha_g1, beta_g2), -gamma_g2, -delta_g2), prepare_inputs
  * (gamma_abc_g1[0] + sum x_i gamma_abc_g1[i]) and verify_proof: e(A, B) e(inputs, -gamma_g2) e(C, -delta_g2) == e(alpha_g1, beta_g2)
  * as one product of three Miller loops and one final exponentiation.  HOST code like the reference's (about 15 ms per proof on
- * one core; a batch runs one proof per host thread); no device is needed.
+ * one core; a batch runs one proof per host thread); no device is needed (frw_groth16_verify_dev below: prepare_inputs on one).
  *     vk          the layout frw_groth16_setup writes: alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | gamma_abc_g1[num_instance]
  *                 (FRW_E_INVALID_ARG if a coordinate's limbs are not below the field modulus, a point is not on its curve or
  *                 not in the subgroup of order r -- every point, gamma_abc_g1 included: what ark's deserialiser checks)
@@ -573,6 +573,35 @@ int frw_groth16_vk_load_opts(const uint64_t *vk, size_t num_instance, int flags,
 void frw_groth16_vk_free(frw_groth16_vk *vk);
 int frw_groth16_verify(const frw_groth16_vk *vk, size_t batch, const uint64_t *instance, int encoding, const uint64_t *proofs,
                        int flags, int32_t *accepted);
+/* The same verifier with prepare_inputs ON THE DEVICE (round 6), for instance vectors and proofs that are in device memory already.
+ * frw_groth16_vk_load_dev: the host key as frw_groth16_vk_load makes it, plus a copy of gamma_abc_g1 on `device` as a narrow MSM handle
+ * (a table handle up to 2^18 points, a bare one beyond).  EVERY gamma_abc_g1 point is checked on the device: canonical limbs (< q), on
+ * the curve, in the subgroup of order r (all zero = infinity is accepted, as on the host) -- the checks frw_groth16_vk_load makes, by the
+ * same code; the four fixed points are checked on the host.  flags must be 0: FRW_VK_POINTS_ARE_CHECKED -> FRW_E_INVALID_ARG (vouching
+ * is what this call makes unnecessary).  No device -> FRW_E_NO_DEVICE (no host fallback).  The handle serves frw_groth16_verify
+ * unchanged too; frw_groth16_vk_free frees both parts. */
+int frw_groth16_vk_load_dev(int device, const uint64_t *vk, size_t num_instance, int flags, frw_groth16_vk **out);
+/* bytes of device workspace for `batch_in_flight` proofs (16-byte aligned; a smaller one runs a batch in chunks); 0 for a key without
+ * a device part */
+size_t frw_groth16_verify_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight);
+/* prepare_inputs on the device: stream-ordered, allocates nothing.
+ *     d_instance  uint64_t[batch][num_instance][4], FRW_ENC_MONTGOMERY or FRW_ENC_CANONICAL, as the witness entry points write it
+ *     d_prepared  uint64_t[batch][12]: gamma_abc_g1[0] + sum_{i>=1} x_i gamma_abc_g1[i], affine, ark-ff's bytes (all zero = infinity;
+ *                 all zero too where d_status is -1)
+ *     d_status    int32_t[batch]: 0, or -1 malformed -- a value whose raw limbs are >= r (either encoding) or instance[0] != 1: exactly
+ *                 the cases where frw_groth16_verify returns -1 because of the instance vector
+ *     d_workspace at least frw_groth16_verify_workspace_bytes(vk, 1) bytes, 16-byte aligned
+ * FRW_E_INVALID_ARG for a null pointer, a small or misaligned workspace, or a key without a device part. */
+int frw_groth16_prepare_inputs_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, uint64_t *d_prepared,
+                                   int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+/* frw_groth16_verify with the instance vectors and the proofs in device memory (d_proofs: uint64_t[batch][48], as frw_groth16_prove_dev
+ * writes them).  prepare_inputs runs on the device (above); one affine point, one status and the 384 proof bytes per proof are then
+ * copied to the host, which does the rest -- the proof points' canonical / on-curve / subgroup checks, three Miller loops and the final
+ * exponentiation, one proof per host thread, the code frw_groth16_verify runs.  accepted: HOST int32_t[batch], the values
+ * frw_groth16_verify gives for the same bytes and flags.  Synchronises `stream`; not capture-safe.  Workspace as above: as many
+ * proofs per pass as it holds.  A key without a device part -> FRW_E_INVALID_ARG. */
+int frw_groth16_verify_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint64_t *d_proofs,
+                           int flags, int32_t *accepted, void *d_workspace, size_t workspace_bytes, void *stream);
 /* diagnostics for the parity tests: the verifier's pairing of one pair (g1: 12, g2: 24 uint64_t), written as the twelve
  * coefficients of 1, w, ..., w^11 in Fq[w] / (w^12 - 2 w^6 + 2), 6 uint64_t each in ark-ff's form.  The value is the CUBE of the
  * reduced ate pairing (frw_pairing.h says why that is as good). */

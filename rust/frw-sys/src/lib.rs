@@ -273,6 +273,15 @@ extern "C" {
     pub fn frw_groth16_vk_free(vk: *mut frw_groth16_vk);
     pub fn frw_groth16_verify(vk: *const frw_groth16_vk, batch: usize, instance: *const u64, encoding: c_int, proofs: *const u64,
                               flags: c_int, accepted: *mut i32) -> c_int;
+    pub fn frw_groth16_vk_load_dev(device: c_int, vk: *const u64, num_instance: usize, flags: c_int,
+                                   out: *mut *mut frw_groth16_vk) -> c_int;
+    pub fn frw_groth16_verify_workspace_bytes(vk: *const frw_groth16_vk, batch_in_flight: usize) -> usize;
+    pub fn frw_groth16_prepare_inputs_dev(vk: *const frw_groth16_vk, batch: usize, d_instance: *const u64, encoding: c_int,
+                                          d_prepared: *mut u64, d_status: *mut i32, d_workspace: *mut c_void,
+                                          workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_verify_dev(vk: *const frw_groth16_vk, batch: usize, d_instance: *const u64, encoding: c_int,
+                                  d_proofs: *const u64, flags: c_int, accepted: *mut i32, d_workspace: *mut c_void,
+                                  workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_diag_pairing(g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,
                                  d_msg_off: *const u64, d_hm: *mut u16, stream: *mut c_void) -> c_int;

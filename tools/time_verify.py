@@ -1,0 +1,124 @@
+"""Time Groth16 verification on the host (frw_groth16_verify) against the device path (frw_groth16_vk_load_dev,
+frw_groth16_prepare_inputs_dev, frw_groth16_verify_dev).  One JSON object per case:
+  (a) 64 Falcon-1024 per-signature proofs (frw_groth16_setup + frw_groth16_prove_dev)
+  (b) 64 proofs against one 32,769-input key (a sixteen-statement aggregate's size)
+  (c) one proof with 1,571,841 inputs (the 1,024-statement aggregate's)
+(b) and (c) are statements made in the exponent (tests/test_gpu_verify_dev.py: gamma_abc_g1[i] = g_i G1 from the oracle's fixed-base
+multiples, A = a G1, B = b G2, C solved for), 14-bit inputs.  Key loads: host with every point checked, host vouched
+(FRW_VK_POINTS_ARE_CHECKED), device (every point checked there).  usage: python tools/time_verify.py [a|b|c ...] [reps=3]"""
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import falcon_r1cs_amd as frw
+import frw_testlib as T
+import test_gpu_verify_dev as V
+
+R = V.R
+
+
+def timed(fn):
+    t = time.perf_counter()
+    out = fn()
+    return out, time.perf_counter() - t
+
+
+def falcon_case(batch=64, logn=10):
+    dev = torch.device("cuda:0")
+    eng = frw.WitnessEngine(0)
+    L = frw.layout(logn)
+    rng = random.Random(5)
+    pk, vk = eng.groth16_setup(0, logn, *(rng.randrange(2, R) for _ in range(5)))
+    r1cs = eng.r1cs_load(0, logn)
+    sig, pk_, hm = frw.synth_triples(logn, batch, seed=1)
+    d = [torch.from_numpy(a.view(np.int16)).to(dev) for a in (sig, pk_, hm)]
+    wit = torch.empty((batch, L.num_witness, 4), dtype=torch.int64, device=dev)
+    inst = torch.empty((batch, L.num_instance, 4), dtype=torch.int64, device=dev)
+    st = torch.empty(batch, dtype=torch.int32, device=dev)
+    eng.witness_ntt_verify_dev(logn, batch, d[0], d[1], d[2], wit, inst, st, frw.ENC_MONTGOMERY, 0)
+    rs = np.array([T.ints_to_limbs([rng.randrange(R), rng.randrange(R)]) for _ in range(batch)])
+    ws_bytes = eng.groth16_workspace_bytes(pk, r1cs, batch)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    proofs = torch.empty((batch, 48), dtype=torch.int64, device=dev)
+    eng.groth16_prove_dev(pk, r1cs, batch, wit, inst, rs, proofs, ws, ws_bytes, None, 0)
+    torch.cuda.synchronize()
+    del wit, ws
+    eng.r1cs_free(r1cs)
+    eng.groth16_pk_free(pk)
+    flat = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
+    return "a: %d Falcon-%d proofs" % (batch, 1 << logn), flat, inst, proofs
+
+
+def exponent_case(oracle, n, batch):
+    k = V.Key(oracle, n, seed=n)
+    rng = random.Random(n)
+    rs = np.random.default_rng(n)
+    insts, proofs = [], []
+    for _ in range(batch):
+        small = rs.integers(0, 1 << 14, n)
+        small[0] = 1
+        proofs.append(V.proof_limbs(k.proof(k.dot(small, {}), rng)))
+        insts.append(V.encode(small, {}, True))
+    name = "%s: %d proof%s against a %d-input key" % ("b" if batch > 1 else "c", batch, "s" if batch > 1 else "", n)
+    return name, k.limbs(), V._dev(np.stack(insts)), V._dev(np.stack(proofs))
+
+
+def run(name, vk, d_inst, d_proofs, reps):
+    batch = d_proofs.shape[0]
+    inst_h, proofs_h = d_inst.cpu().numpy().view(np.uint64), d_proofs.cpu().numpy().view(np.uint64)
+    host, load_full = timed(lambda: frw.Groth16Verifier(vk))
+    vouched, load_vouched = timed(lambda: frw.Groth16Verifier(vk, points_are_checked=True))
+    vouched.close()
+    devk, load_dev = timed(lambda: frw.Groth16Verifier(vk, device=0))
+    ws = torch.empty(devk.workspace_bytes(batch), dtype=torch.uint8, device=d_inst.device)
+    devk.prepare_inputs_dev(d_inst, workspace=ws)                         # (warm-up)
+    torch.cuda.synchronize()
+    prep = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        devk.prepare_inputs_dev(d_inst, workspace=ws)
+        torch.cuda.synchronize()
+        prep.append(time.perf_counter() - t)
+    host_s, dev_s = [], []
+    for _ in range(reps):
+        h, s = timed(lambda: host.verify(inst_h, proofs_h))
+        host_s.append(s)
+        d, s = timed(lambda: devk.verify_dev(d_inst, d_proofs, workspace=ws))
+        dev_s.append(s)
+        assert h.tolist() == d.tolist(), (h, d)
+    out = {"case": name, "num_instance": host.num_instance, "batch": batch, "accepted": int((d == 1).sum()),
+           "vk_load_s": {"host_checked": round(load_full, 4), "host_vouched": round(load_vouched, 4), "device_checked": round(load_dev, 4)},
+           "prepare_inputs_dev_ms": {"min": round(1e3 * min(prep), 3), "median": round(1e3 * sorted(prep)[len(prep) // 2], 3)},
+           "verify_s": {"host_min": round(min(host_s), 4), "device_min": round(min(dev_s), 4),
+                        "host_median": round(sorted(host_s)[len(host_s) // 2], 4), "device_median": round(sorted(dev_s)[len(dev_s) // 2], 4)},
+           "workspace_bytes": int(ws.numel())}
+    host.close()
+    devk.close()
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.isdigit()] or ["a", "b", "c"]
+    reps = int(next((a for a in sys.argv[1:] if a.isdigit()), 3))
+    oracle = T.load_oracle()
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "host_threads": os.cpu_count(), "reps": reps}), flush=True)
+    for c in args:
+        if c == "a":
+            run(*falcon_case(), reps)
+        elif c == "b":
+            run(*exponent_case(oracle, 32769, 64), reps)
+        elif c == "c":
+            run(*exponent_case(oracle, V.BIG, 1), reps)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -137,6 +137,10 @@ PROTOTYPES = {
     "frw_groth16_verify_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
     "frw_diag_pairing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_groth16_verify_full_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int]),
+    "frw_groth16_verify_full_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frw_diag_pairing_dev": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_compact_layout": (C.c_int, [C.c_int, C.POINTER(CompactLayoutStruct)]),
     "frw_witness_ntt_verify_compact_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p]),

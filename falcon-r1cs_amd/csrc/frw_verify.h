@@ -19,7 +19,13 @@ struct frw_groth16_vk {
     frw::pairing::FrobeniusConstants fc;
     int device = -1;                        // frw_groth16_vk_load_dev: the device `msm` lives on (-1: a host key)
     frw_msm *msm = nullptr;                 // ... and gamma_abc_g1 there, as a narrow MSM handle (frw_verify_dev.hip says which kind)
-    ~frw_groth16_vk() { if (msm) frw_msm_free(msm); }
+    uint32_t *d_pairing = nullptr;          // ... and the device pairing's fixed part there (frw_pairing_dev.hip: line tables, constants)
+    unsigned pairing_inf = 0;               // ... bit j: the fixed G2 point j (-gamma, -delta, beta) is the point at infinity
+    ~frw_groth16_vk()
+    {
+        if (msm) frw_msm_free(msm);
+        if (d_pairing) (void)hipFree(d_pairing);
+    }
 };
 
 namespace frw {

@@ -10,7 +10,8 @@
 //   the sum                 frw_msm_g1_dev over the key's narrow handle: x_0 = 1, so it sums all num_instance points, gamma_0 included
 //   prepared_clear_kernel   the point of a malformed vector is written as zeros (what it would have been is of no use to anybody)
 // Everything after prepare_inputs -- the proof points' checks, three Miller loops, the final exponentiation -- is the host's
-// frw::verify::verify_prepared, the code frw_groth16_verify runs too.
+// frw::verify::verify_prepared in frw_groth16_verify_dev, the code frw_groth16_verify runs too; frw_groth16_verify_full_dev runs it on
+// the device instead (frw_pairing_dev.hip), after the same prepare_inputs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstring>
@@ -19,6 +20,7 @@
 
 #include "../../include/frw.h"
 #include "frw_device.h"
+#include "frw_pairing_dev.h"
 #include "frw_verify.h"
 
 namespace frw {
@@ -150,6 +152,12 @@ extern "C" int frw_groth16_vk_load_dev(int device, const uint64_t *vk, size_t nu
     }
     k->device = device;
     k->msm = m;
+    // the device pairing's fixed part: -gamma, -delta and beta's line tables, the Frobenius constants, e(alpha, beta)^3
+    rc = frw::pairing_dev::upload_key(k, vk, vk + 12);
+    if (rc != FRW_OK) {
+        frw_groth16_vk_free(k);
+        return rc;
+    }
     *out = k;
     return FRW_OK;
 }
@@ -212,6 +220,68 @@ extern "C" int frw_groth16_verify_dev(const frw_groth16_vk *vk, size_t batch, co
         }
     } catch (...) {
         return FRW_E_OUT_OF_MEMORY;
+    }
+    return FRW_OK;
+}
+
+// ---- the whole verification on the device --------------------------------------------------------------------------------------------
+namespace frw {
+namespace {
+size_t full_workspace_bytes(const frw_groth16_vk *vk, size_t k, int flags, size_t *prepare_part = nullptr)
+{
+    const size_t p = workspace_bytes(vk, k);
+    if (prepare_part) *prepare_part = p;
+    return p + k * pairing_dev::proof_workspace_bytes(flags) + pairing_dev::pass_workspace_bytes(flags);
+}
+size_t full_proofs_in_flight(const frw_groth16_vk *vk, size_t batch, int flags, size_t bytes)
+{
+    if (batch == 0 || full_workspace_bytes(vk, 1, flags) > bytes) return 0;
+    size_t lo = 1, hi = batch;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (full_workspace_bytes(vk, mid, flags) <= bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+}  // namespace
+}  // namespace frw
+
+extern "C" size_t frw_groth16_verify_full_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags)
+{
+    if (!vk || !vk->msm || !vk->d_pairing || batch_in_flight == 0 || (flags & ~(FRW_VERIFY_POINTS_ARE_CHECKED | FRW_VERIFY_BATCHED))) return 0;
+    return frw::full_workspace_bytes(vk, batch_in_flight, flags);
+}
+
+extern "C" int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding,
+                                           const uint64_t *d_proofs, int flags, const uint64_t *seed, int32_t *d_accepted,
+                                           int32_t *d_batch_passed, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (!vk || !vk->msm || !vk->d_pairing) return FRW_E_INVALID_ARG;
+    if (encoding != FRW_ENC_MONTGOMERY && encoding != FRW_ENC_CANONICAL) return FRW_E_INVALID_ARG;
+    if (flags & ~(FRW_VERIFY_POINTS_ARE_CHECKED | FRW_VERIFY_BATCHED)) return FRW_E_INVALID_ARG;
+    if ((flags & FRW_VERIFY_BATCHED) && !seed) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    if (!d_instance || !d_proofs || !d_accepted || !d_workspace || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
+    const size_t chunk = frw::full_proofs_in_flight(vk, batch, flags, workspace_bytes);
+    if (chunk == 0) return FRW_E_INVALID_ARG;
+    hipError_t e = hipSetDevice(vk->device);
+    if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n = vk->num_instance;
+    size_t prepare_part = 0, msm_part = 0;
+    frw::full_workspace_bytes(vk, chunk, flags, &prepare_part);
+    frw::workspace_bytes(vk, chunk, &msm_part);
+    uint64_t *d_prepared = (uint64_t *)((char *)d_workspace + msm_part);
+    int32_t *d_status = (int32_t *)(d_prepared + 12 * chunk);
+    void *d_pairing_ws = (char *)d_workspace + prepare_part;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
+        int rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, d_prepared, d_status, d_workspace, msm_part, st);
+        if (rc == FRW_OK)
+            rc = frw::pairing_dev::verify_proofs(vk, cnt, lo, d_proofs + lo * 48, d_prepared, d_status, flags, seed, d_accepted + lo,
+                                                 d_batch_passed, d_pairing_ws, st);
+        if (rc != FRW_OK) return rc;
     }
     return FRW_OK;
 }

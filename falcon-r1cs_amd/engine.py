@@ -89,6 +89,7 @@ def synth_triples(logn, batch, seed=0x46414C434F4E, first_index=0):
 
 
 VERIFY_POINTS_ARE_CHECKED = 1
+VERIFY_BATCHED = 2
 VK_POINTS_ARE_CHECKED = 1
 KEY_AUTO, KEY_TABLES, KEY_BARE = 0, 1, 2           # frw.h FRW_KEY_*: window tables, or the points only (keys that would not fit)
 GROTH16_PARTIAL_WORDS = 72
@@ -166,6 +167,36 @@ class Groth16Verifier:
               "frw_groth16_verify_dev")
         return out
 
+    def full_workspace_bytes(self, batch_in_flight, flags=0):
+        """Device workspace of verify_full_dev for `batch_in_flight` proofs (0 for a host-only key)."""
+        return int(self._lib.frw_groth16_verify_full_workspace_bytes(self._h, int(batch_in_flight), int(flags)))
+
+    def verify_full_dev(self, d_instance, d_proofs, encoding=ENC_MONTGOMERY, flags=0, batched=False, seed=None, stream=0, workspace=None,
+                        batch_passed=None):
+        """The whole verification on the device (frw_groth16_verify_full_dev): prepare_inputs, the proof points' checks, the pairings.
+        Returns a device int32 tensor [batch] with the values verify() gives for the same bytes, ordered on `stream`, without
+        synchronising.  batched: the batched check first (FRW_VERIFY_BATCHED); seed: 4 uint64 (None: 32 fresh random bytes, drawn now,
+        after the proofs); batch_passed: an optional device int32 tensor of one element that receives whether the batched check passed.
+        workspace: a device tensor (16-byte aligned) or None for one of the whole batch."""
+        import os
+        import torch
+        batch = d_proofs.shape[0]
+        flags = int(flags) | (VERIFY_BATCHED if batched else 0)
+        out = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
+        seed_arr = None
+        if flags & VERIFY_BATCHED:
+            seed_arr = np.frombuffer(os.urandom(32), dtype=np.uint64).copy() if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(4)
+        if workspace is None:
+            workspace = torch.empty(max(self.full_workspace_bytes(batch, flags), 16), dtype=torch.uint8, device=d_proofs.device)
+        ws_bytes = workspace.numel() * workspace.element_size()
+        check(self._lib.frw_groth16_verify_full_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding),
+                                                    C.c_void_p(d_proofs.data_ptr()), flags,
+                                                    None if seed_arr is None else seed_arr.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
+                                                    None if batch_passed is None else C.c_void_p(batch_passed.data_ptr()),
+                                                    C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_verify_full_dev")
+        return out
+
     def close(self):
         if self._h:
             self._lib.frw_groth16_vk_free(self._h)
@@ -186,6 +217,19 @@ def diag_pairing(g1, g2):
     check(load_library().frw_diag_pairing(g1.ctypes.data_as(C.c_void_p), g2.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "frw_diag_pairing")
     return out
 
+
+
+def diag_pairing_dev(g1, g2, device=0):
+    """diag_pairing for many pairs at once on `device` (frw_diag_pairing_dev): g1 uint64[count, 12], g2 uint64[count, 24] ->
+    uint64[count, 12, 6].  No device is an error (FrwError, FRW_E_NO_DEVICE), never a host fallback."""
+    g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(-1, 12)
+    g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1, 24)
+    if g1.shape[0] != g2.shape[0]:
+        raise FrwError("diag_pairing_dev: as many G1 as G2 points")
+    out = np.zeros((g1.shape[0], 12, 6), dtype=np.uint64)
+    check(load_library().frw_diag_pairing_dev(int(device), g1.shape[0], g1.ctypes.data_as(C.c_void_p), g2.ctypes.data_as(C.c_void_p),
+                                              out.ctypes.data_as(C.c_void_p)), "frw_diag_pairing_dev")
+    return out
 
 def _u16(a, n):
     a = np.ascontiguousarray(a, dtype=np.uint16)

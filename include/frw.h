@@ -563,6 +563,7 @@ int frw_groth16_prove_combine_dev(const frw_groth16_pk *pk, size_t world, const 
  *                 for x), a point off its curve or outside the subgroup -- or, with FRW_VERIFY_POINTS_ARE_CHECKED, a point the
  *                 caller vouched for wrongly that drives the Miller loop into a vertical line */
 #define FRW_VERIFY_POINTS_ARE_CHECKED 1
+#define FRW_VERIFY_BATCHED 2          /* frw_groth16_verify_full_dev only: see there */
 typedef struct frw_groth16_vk frw_groth16_vk;
 int frw_groth16_vk_load(const uint64_t *vk, size_t num_instance, frw_groth16_vk **out);
 /* flags: FRW_VK_POINTS_ARE_CHECKED -- the caller vouches for gamma_abc_g1 being on the curve and in the subgroup (a key it made itself a
@@ -606,6 +607,36 @@ int frw_groth16_verify_dev(const frw_groth16_vk *vk, size_t batch, const uint64_
  * coefficients of 1, w, ..., w^11 in Fq[w] / (w^12 - 2 w^6 + 2), 6 uint64_t each in ark-ff's form.  The value is the CUBE of the
  * reduced ate pairing (frw_pairing.h says why that is as good). */
 int frw_diag_pairing(const uint64_t *g1, const uint64_t *g2, uint64_t *out);
+/* The WHOLE verification on the device (frw_pairing_dev.hip): prepare_inputs as frw_groth16_prepare_inputs_dev, then the proof points'
+ * checks, the three Miller loops, the final exponentiation and the comparison with e(alpha, beta)^3 -- no host round trip, verdicts in
+ * device memory.  The key must come from frw_groth16_vk_load_dev (it uploads -gamma, -delta and beta's Miller-loop line tables,
+ * e(alpha, beta)^3 and the Frobenius constants, computed on the host at load); any other key -> FRW_E_INVALID_ARG.
+ *     d_accepted     DEVICE int32_t[batch]: what frw_groth16_verify returns for the same bytes and flags -- 1, 0 or -1 (an instance value
+ *                    >= r or instance[0] != 1, a coordinate >= q, a point off its curve or outside the subgroup, a vertical line in the
+ *                    Miller loop of a point vouched for wrongly)
+ *     flags          FRW_VERIFY_POINTS_ARE_CHECKED and / or FRW_VERIFY_BATCHED; any other bit -> FRW_E_INVALID_ARG
+ *     seed           HOST uint64_t[4], read with FRW_VERIFY_BATCHED (required then: NULL -> FRW_E_INVALID_ARG)
+ *     d_batch_passed DEVICE int32_t (may be NULL): with FRW_VERIFY_BATCHED, 1 if the batched check passed in every pass, else 0
+ *     d_workspace    at least frw_groth16_verify_full_workspace_bytes(vk, 1, flags) bytes, 16-byte aligned; a smaller one than the batch
+ *                    needs runs it in chunks (about 26 KB per proof in flight besides prepare_inputs' share, 0.6 KB more batched)
+ * FRW_VERIFY_BATCHED: the well-formed proofs of a pass (not -1) are checked together first.  rho_i = the first 128 bits of
+ * SHAKE256(seed || le64(i) || proof i's 384 bytes), i the proof's index in the whole batch (one if they are all zero), and
+ *     prod_i e(rho_i A_i, B_i) e(sum rho_i P_i, -gamma) e(sum rho_i C_i, -delta) e(-(sum rho_i) alpha, beta) == 1
+ * (P_i the prepared inputs): N + 3 Miller loops, a product tree, ONE final exponentiation.  If it holds, every well-formed proof of the
+ * pass gets 1; if not, the per-proof check decides each (its kernels are always launched and return at once when the batched check
+ * passed).  Soundness: a pass holding a proof that the per-proof check rejects passes the batched check with probability at most about
+ * 2^-128 over the choice of the rho_i -- PROVIDED the seed is chosen after the proofs and statements are fixed (unpredictable to whoever
+ * made them; a fresh random seed per call).  A seed known in advance lets a prover craft proofs whose errors cancel.
+ * Stream-ordered on `stream`, allocates nothing, does not synchronise: capture-safe.  batch = 0 is a no-op.  FRW_E_INVALID_ARG for a null
+ * pointer, a bad encoding, a small or misaligned workspace. */
+size_t frw_groth16_verify_full_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags);
+int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint64_t *d_proofs,
+                                int flags, const uint64_t *seed, int32_t *d_accepted, int32_t *d_batch_passed, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+/* frw_diag_pairing for `count` pairs on `device` (host buffers: g1 count x 12, g2 count x 24, out count x 72 uint64_t, the same basis):
+ * the device pairing's kernels, for the parity tests.  Allocates and synchronises.  A point off its curve -> FRW_E_INVALID_ARG; no
+ * device -> FRW_E_NO_DEVICE (no host fallback). */
+int frw_diag_pairing_dev(int device, size_t count, const uint64_t *g1, const uint64_t *g2, uint64_t *out);
 
 /* ---- input preparation (what the reference does with falcon-rust before any gadget runs) ---------------------
  * falcon_ntt.rs:27-28,44: sig_poly = Polynomial::from(&sig), pk_poly = Polynomial::from(&pk),

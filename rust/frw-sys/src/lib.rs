@@ -120,6 +120,7 @@ pub struct frw_groth16_vk {
     _private: [u8; 0],
 }
 pub const FRW_VERIFY_POINTS_ARE_CHECKED: c_int = 1;
+pub const FRW_VERIFY_BATCHED: c_int = 2;
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct frw_groth16_pk_desc_t {
@@ -283,6 +284,12 @@ extern "C" {
                                   d_proofs: *const u64, flags: c_int, accepted: *mut i32, d_workspace: *mut c_void,
                                   workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_diag_pairing(g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
+    pub fn frw_groth16_verify_full_workspace_bytes(vk: *const frw_groth16_vk, batch_in_flight: usize, flags: c_int) -> usize;
+    pub fn frw_groth16_verify_full_dev(vk: *const frw_groth16_vk, batch: usize, d_instance: *const u64, encoding: c_int,
+                                       d_proofs: *const u64, flags: c_int, seed: *const u64, d_accepted: *mut i32,
+                                       d_batch_passed: *mut i32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                       stream: *mut c_void) -> c_int;
+    pub fn frw_diag_pairing_dev(device: c_int, count: usize, g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,
                                  d_msg_off: *const u64, d_hm: *mut u16, stream: *mut c_void) -> c_int;
     pub fn frw_decode_public_keys_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_pk_bytes: *const u8,

@@ -3,9 +3,13 @@ frw_groth16_prepare_inputs_dev, frw_groth16_verify_dev).  One JSON object per ca
   (a) 64 Falcon-1024 per-signature proofs (frw_groth16_setup + frw_groth16_prove_dev)
   (b) 64 proofs against one 32,769-input key (a sixteen-statement aggregate's size)
   (c) one proof with 1,571,841 inputs (the 1,024-statement aggregate's)
+  (f) the whole verification on the device (frw_groth16_verify_full_dev) of Falcon-1024 per-signature proofs at 1, 64, 1,024, 4,096 and
+      16,384 proofs (64 proofs made, tiled), per proof and batched (FRW_VERIFY_BATCHED: one final exponentiation per pass), proofs/s
+      next to the host (frw_groth16_verify) and verify_dev columns -- those two up to
+      1,024 proofs: beyond that the host's pairings alone take many seconds a repetition
 (b) and (c) are statements made in the exponent (tests/test_gpu_verify_dev.py: gamma_abc_g1[i] = g_i G1 from the oracle's fixed-base
 multiples, A = a G1, B = b G2, C solved for), 14-bit inputs.  Key loads: host with every point checked, host vouched
-(FRW_VK_POINTS_ARE_CHECKED), device (every point checked there).  usage: python tools/time_verify.py [a|b|c ...] [reps=3]"""
+(FRW_VK_POINTS_ARE_CHECKED), device (every point checked there).  usage: python tools/time_verify.py [a|b|c|f ...] [reps=3]"""
 import json
 import os
 import random
@@ -105,6 +109,55 @@ def run(name, vk, d_inst, d_proofs, reps):
     print(json.dumps(out), flush=True)
 
 
+def full_leg(reps, sizes=(1, 64, 1024, 4096, 16384), host_up_to=1024):
+    name, vk, inst, proofs = falcon_case()
+    devk = frw.Groth16Verifier(vk, device=0)
+    host = frw.Groth16Verifier(vk)
+    for n in sizes:
+        idx = torch.arange(n, device=inst.device) % inst.shape[0]
+        d_inst, d_proofs = inst[idx].contiguous(), proofs[idx].contiguous()
+        ws = torch.empty(devk.full_workspace_bytes(n), dtype=torch.uint8, device=inst.device)
+        got = devk.verify_full_dev(d_inst, d_proofs, workspace=ws)          # (warm-up)
+        torch.cuda.synchronize()
+        assert int((got == 1).sum()) == n
+        full = []
+        for _ in range(reps):
+            t = time.perf_counter()
+            devk.verify_full_dev(d_inst, d_proofs, workspace=ws)
+            torch.cuda.synchronize()
+            full.append(time.perf_counter() - t)
+        wsb = torch.empty(devk.full_workspace_bytes(n, frw.VERIFY_BATCHED), dtype=torch.uint8, device=inst.device)
+        passed = torch.zeros(1, dtype=torch.int32, device=inst.device)
+        got_b = devk.verify_full_dev(d_inst, d_proofs, batched=True, workspace=wsb, batch_passed=passed)   # (warm-up)
+        torch.cuda.synchronize()
+        assert got_b.cpu().tolist() == got.cpu().tolist() and passed.item() == 1
+        batched = []
+        for _ in range(reps):
+            t = time.perf_counter()
+            devk.verify_full_dev(d_inst, d_proofs, batched=True, workspace=wsb, batch_passed=passed)
+            torch.cuda.synchronize()
+            batched.append(time.perf_counter() - t)
+        out = {"case": "f: %d Falcon-1024 proofs, verify_full_dev" % n, "batch": n, "num_instance": devk.num_instance,
+               "full_dev_ms": {"min": round(1e3 * min(full), 3), "median": round(1e3 * sorted(full)[len(full) // 2], 3)},
+               "full_dev_proofs_per_s": round(n / min(full), 1),
+               "batched_ms": {"min": round(1e3 * min(batched), 3), "median": round(1e3 * sorted(batched)[len(batched) // 2], 3)},
+               "batched_proofs_per_s": round(n / min(batched), 1), "workspace_bytes": int(ws.numel())}
+        del ws, wsb
+        if n <= host_up_to:
+            inst_h, proofs_h = d_inst.cpu().numpy().view(np.uint64), d_proofs.cpu().numpy().view(np.uint64)
+            wsd = torch.empty(devk.workspace_bytes(n), dtype=torch.uint8, device=inst.device)
+            h, hs = timed(lambda: host.verify(inst_h, proofs_h))
+            d, ds = timed(lambda: devk.verify_dev(d_inst, d_proofs, workspace=wsd))
+            assert h.tolist() == d.tolist() == got.cpu().tolist()
+            out["host_proofs_per_s"] = round(n / hs, 1)
+            out["verify_dev_proofs_per_s"] = round(n / ds, 1)
+            del wsd
+        print(json.dumps(out), flush=True)
+        torch.cuda.empty_cache()
+    devk.close()
+    host.close()
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.isdigit()] or ["a", "b", "c"]
     reps = int(next((a for a in sys.argv[1:] if a.isdigit()), 3))
@@ -117,6 +170,8 @@ def main():
             run(*exponent_case(oracle, 32769, 64), reps)
         elif c == "c":
             run(*exponent_case(oracle, V.BIG, 1), reps)
+        elif c == "f":
+            full_leg(reps)
         torch.cuda.empty_cache()
 
 

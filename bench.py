@@ -16,11 +16,15 @@ peer would consume them from).  Multi-GPU: signatures shard by index, every rank
 no data-path collective inside `value`; the north-star's all-gather of the witness vectors is measured as a second,
 separately reported curve (compact encoding over RCCL, expanded on every receiver).
 
-Prints ONE JSON line (rank 0).  What is checked is what was timed: after the timed region the witnesses the LAST timed
-launch left in HBM are digested, checked against the independently emitted constraint system on the device
-(falcon_ntt.rs:159 `assert!(cs.is_satisfied())`), and a strided sample of them is compared with the oracle.
-`roofline` is measured live with HIP events on the launch stream; `cpu_baseline` times the oracle (oracle/frw_oracle.c, a
-restatement -- the Rust reference cannot run here) on this host's cores over a bounded sample of the same inputs.
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: it sets up, warms up, times the
+steps, checks the statuses the timed launches wrote, writes --dump-outputs if asked, and prints `value`, `ms_per_step`
+and the `roofline` of the timed launches from their own HIP events.  Everything else runs with --full only:
+what is checked is what was timed -- after the timed region the witnesses the LAST timed launch left in HBM are
+digested, checked against the independently emitted constraint system on the device (falcon_ntt.rs:159
+`assert!(cs.is_satisfied())`), and a strided sample of them is compared with the oracle; the roofline gains a
+calibration write stream of the same device; `secondary` measures the other kernels, sizes and the prover;
+`cpu_baseline` times the oracle (oracle/frw_oracle.c, a C restatement of the Rust reference) on the
+host's cores over a bounded sample of the same inputs; and N > 1 runs add their gather, proof and sharded-aggregate legs.
 """
 import argparse
 import hashlib
@@ -1586,13 +1590,18 @@ def main():
                          "series; at N = 8 two steps are configs[3]'s 1 M signatures over the node)")
     ap.add_argument("--plan", action="store_true",
                     help="touch no GPU: print, for N = 1, 2, 4, 8 (or --gpus N alone if given), every rank's global index "
-                         "range, launches, gather chunking and HBM bytes of the run these arguments describe, assert that "
+                         "range, launches, gather chunking (--full) and HBM bytes of the run these arguments describe, assert that "
                          "each fits 0.9 x 288 GB, and exit")
     ap.add_argument("--chunk", type=int, default=0,
                     help="signatures per kernel launch = size of the reused HBM witness buffer.  Default: 32,768 Falcon-1024 "
                          "witnesses = 164 GB of the 288 GB (a step = two launches): sized for the HBM, and measured -- the "
                          "write stream itself sustains 6.5 TB/s over a buffer of this size, 6.0 TB/s over 82 GB "
                          "(profiles/r02_chunk_sizes.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not only the headline: the R1CS check, digests, launch-shape check and "
+                         "oracle comparison of what the timed launches left, the calibration write stream of `roofline`, "
+                         "`secondary`, `cpu_baseline`, and for N > 1 the gather, proof and sharded-aggregate legs.  The --no-* "
+                         "options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-r1cs-check", action="store_true",
                     help="skip the untimed on-device check that every witness of the last timed launch satisfies the "
@@ -1619,7 +1628,7 @@ def main():
     ap.add_argument("--allgather-deadline", type=int, default=240,
                     help="seconds the N > 1 gather legs may take before the run reports `value` without them")
     ap.add_argument("--inject-leg-failure", type=int, default=-1, metavar="RANK",
-                    help="testing only: the N > 1 gather leg raises on this rank before its first collective (the run must "
+                    help="testing only, with --full: the N > 1 gather leg raises on this rank before its first collective (the run must "
                          "print its primary line, say why on stderr and exit 3 through the launcher)")
     ap.add_argument("--force-pg", action="store_true",
                     help="initialise the process group and run the N > 1 legs even with one rank (rehearses the RCCL "
@@ -1764,13 +1773,15 @@ def main():
         slot_sig[last_cnt:] = np.arange(last_cnt, held) + (nchunks - 2) * chunk
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, world, rank, lo, d_wit, d_inst, d_st, slot_sig, held)
-    d_dig = torch.zeros(held, dtype=torch.int64, device=dev)
-    eng.digest_dev(d_wit, L.num_witness * 4, held, d_dig, stream.cuda_stream)
-    torch.cuda.synchronize()
-    held_dig = d_dig.cpu().numpy().view(np.uint64)
-    checked = {"signatures": held, "from_the_last_timed_launch": last_cnt,
-               "from_the_full_size_launch_before_it": held - last_cnt, "distinct_digests": int(len(np.unique(held_dig)))}
-    if not dual:
+    checked = held_dig = None
+    if args.full:
+        d_dig = torch.zeros(held, dtype=torch.int64, device=dev)
+        eng.digest_dev(d_wit, L.num_witness * 4, held, d_dig, stream.cuda_stream)
+        torch.cuda.synchronize()
+        held_dig = d_dig.cpu().numpy().view(np.uint64)
+        checked = {"signatures": held, "from_the_last_timed_launch": last_cnt,
+                   "from_the_full_size_launch_before_it": held - last_cnt, "distinct_digests": int(len(np.unique(held_dig)))}
+    if args.full and not dual:
         for name, cnt in (("full_size_launch", chunk), ("remainder_launch", last_cnt if last_cnt != chunk else 0)):
             if cnt:
                 sh = eng.launch_shape(logn, cnt)
@@ -1782,7 +1793,7 @@ def main():
                                  "rounds": round(cnt / max(1, sh["grid"]), 2), "split_signatures": sh["split_signatures"]}
     r1cs = None
     qap_result = msm_result = groth16_result = prove_info = None
-    if not args.no_r1cs_check:
+    if args.full and not args.no_r1cs_check:
         # the reference's assert!(cs.is_satisfied()) (falcon_ntt.rs:159) for every witness in the buffer, on the device,
         # in place, against matrices emitted from the gadget definitions by the host mirror (not the kernels' closed form)
         h = eng.r1cs_load(1 if dual else 0, logn)
@@ -1820,19 +1831,21 @@ def main():
     # ---- calibration (untimed): what a compute-free write stream of the same shape SUSTAINS on this device now -----
     # Same regime as the timed region: one step's worth of launches back to back, second of two rounds (a single
     # launch squeezed between witness kernels reads 5-10 % high: the device boosts after every change of load).
-    # Runs after the checks above: it overwrites the witness buffer.
-    wbytes = d_wit.numel() * 8
-    cal_ms = 0.0
-    cal_reps = max(2, nchunks)
-    for _ in range(2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(cal_reps):
-            eng.diag_write_stream_dev(d_wit, wbytes, L.num_witness * 32, stream.cuda_stream)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        cal_ms = e0.elapsed_time(e1) / cal_reps
-    write_stream_gbs = wbytes / (cal_ms * 1e-3) / 1e9
+    # Runs after the checks above: it overwrites the witness buffer.  --full only: these are launches of their own.
+    write_stream_gbs = None
+    if args.full:
+        wbytes = d_wit.numel() * 8
+        cal_ms = 0.0
+        cal_reps = max(2, nchunks)
+        for _ in range(2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(cal_reps):
+                eng.diag_write_stream_dev(d_wit, wbytes, L.num_witness * 32, stream.cuda_stream)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            cal_ms = e0.elapsed_time(e1) / cal_reps
+        write_stream_gbs = wbytes / (cal_ms * 1e-3) / 1e9
 
     ranks_seen = dist.get_world_size() if use_pg else 1
     devs = sharding.gather_per_signature(torch.tensor([dev_index], dtype=torch.int64, device=cdev), world, rank, world)
@@ -1842,7 +1855,7 @@ def main():
     # should a collective of theirs ever hang (they cannot be rehearsed on more than one RCCL rank here), rank 0 still
     # emits `value` and every rank leaves through os._exit instead of waiting for peers.
     gather_info, legs_hung = None, False
-    if use_pg and not args.no_allgather and not dual:
+    if args.full and use_pg and not args.no_allgather and not dual:
         import threading
         box = {}
 
@@ -1895,7 +1908,7 @@ def main():
     # of the 2^27 domain, this rank's slices of the key and one proof's workspace (sharding.sharded_aggregate_plan).  One collective on its
     # data path (an all-gather of 576 bytes per rank), so it runs under a deadline like the gather legs.
     sharded_info = None
-    if use_pg and not dual and args.aggregate_sharded and logn == 10 and not legs_hung:
+    if args.full and use_pg and not dual and args.aggregate_sharded and logn == 10 and not legs_hung:
         import threading
         mix = sharding.aggregate_mix(args.aggregate_sharded)
         splan = sharding.sharded_aggregate_plan(world, rank, mix)
@@ -1954,11 +1967,13 @@ def main():
                          "kernel": "witness_%sntt_verify_kernel<%d,1>" % ("dual_" if dual else "", logn),
                          "kernel_source_sha256_16": kernel_source_sha(),
                          "algorithmic_bytes_per_launch": chunk * bytes_per_sig,
-                         "avg_launch_ms": round(launch_ms, 4), "launches_timed": len(full),
-                         "device_write_stream_GBs": round(write_stream_gbs, 1),
-                         "frac_of_device_write_stream": round(achieved / write_stream_gbs, 4)},
-            "launch_shape_checked": checked,
+                         "avg_launch_ms": round(launch_ms, 4), "launches_timed": len(full)},
         }
+        if write_stream_gbs is not None:
+            result["roofline"].update({"device_write_stream_GBs": round(write_stream_gbs, 1),
+                                       "frac_of_device_write_stream": round(achieved / write_stream_gbs, 4)})
+        if checked is not None:
+            result["launch_shape_checked"] = checked
         if r1cs is not None:
             result["r1cs_check"] = r1cs
         if gather_info is not None or prove_info is not None or sharded_info is not None:
@@ -1970,7 +1985,7 @@ def main():
                 result["scaling_curves"]["prove_proofs_per_s"] = prove_info.get("proofs_per_s_all_gpus")
             if sharded_info is not None:
                 result["scaling_curves"]["aggregate_proof_sharded"] = sharded_info
-        if world == 1 and not args.no_secondary and not dual:
+        if args.full and world == 1 and not args.no_secondary and not dual:
             # untimed w.r.t. `value`: the other two rooflines BASELINE / north_star name, measured in this process
             result["secondary"] = {
                 "ntt_modq_falcon512_batch4096": time_ntt_modq(eng, dev, 9, 4096, 200, 20, three_streams=not args.no_aggregate),
@@ -2003,7 +2018,7 @@ def main():
                 assert sharding.sharded_aggregate_plan(1, 0, mix)["fits"]
                 result["secondary"]["aggregate_proof_%d_mixed" % len(mix)] = time_aggregate_proof(eng, dev, mix, 3, None)
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline and not dual:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dual:
             slots = np.arange(0, held, max(1, held // 4096))[:4096]        # strided over the whole buffer
             digest_of = {int(slot_sig[j]): int(held_dig[j]) for j in slots}
             result["cpu_baseline"] = cpu_baseline(logn, sig, pk, hm, slot_sig[slots], lambda i: digest_of[int(i)])
@@ -2055,8 +2070,8 @@ def make_plan(args, world, rank):
     CL = frw.compact_layout(args.logn)
     batch = args.batch or 65536
     chunk = min(args.chunk or (32768 if args.logn == 10 else 65536), batch)
-    legs = (world > 1 or args.force_pg) and not args.no_allgather and not dual
-    prove = (world > 1 or args.force_pg) and not args.no_prove and not args.no_r1cs_check and not dual
+    legs = args.full and (world > 1 or args.force_pg) and not args.no_allgather and not dual
+    prove = args.full and (world > 1 or args.force_pg) and not args.no_prove and not args.no_r1cs_check and not dual
     agg = args.aggregate_leg if prove and args.logn == 10 else 0
     return sharding.step_plan(world, rank, batch, chunk, args.allgather_chunk, L.n, L.num_witness, L.num_instance,
                               int(CL.bytes_per_signature), with_gather_legs=legs, with_prove_leg=prove, aggregate_statements=agg)
@@ -2078,7 +2093,7 @@ def print_plans(args, only_this_world):
             "hbm_plan_bytes_per_rank": p0["hbm_plan_bytes"], "hbm_plan_GB_per_rank": round(p0["hbm_plan_bytes"] / 1e9, 2),
             "hbm_limit_bytes": p0["hbm_limit_bytes"], "fits": p0["fits"],
             "buffers_GB": {k: round(v / 1e9, 3) for k, v in p0["buffers"].items()}}
-        if args.aggregate_sharded and args.logn == 10 and args.circuit != "dual":
+        if args.full and args.aggregate_sharded and args.logn == 10 and args.circuit != "dual":
             # the last leg, after the witness buffer has gone back to the device: ONE proof for K mixed statements, the key in `world` slices
             sp = [sharding.sharded_aggregate_plan(world, r, sharding.aggregate_mix(args.aggregate_sharded)) for r in range(world)]
             sharding.check_sharded_aggregate_plans(sp)

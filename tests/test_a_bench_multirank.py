@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--aggregate-sharded", "0", "--aggregate-leg", "0"]
+COMMON = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--aggregate-sharded", "0", "--aggregate-leg", "0"]
 
 
 def _run(cmd, timeout=600):
@@ -131,7 +131,7 @@ def test_one_proof_with_its_key_in_slices_over_two_and_four_ranks():
     frw_groth16_prove_combine_dev on every rank.  The leg itself asserts that all ranks hold the same 384 bytes and that the product's
     pairing verifier accepts them (and rejects them for another statement); here: two and four ranks reproduce the ONE-rank proof
     (the whole key, frw_groth16_prove_dev) byte for byte."""
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--no-allgather", "--no-prove", "--aggregate-leg", "0",
+    common = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--no-allgather", "--no-prove", "--aggregate-leg", "0",
               "--batch", "256", "--chunk", "128", "--backend", "gloo", "--aggregate-sharded", "4"]
     shas = {}
     for world in (1, 2, 4):

@@ -7,7 +7,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 1 --warmup 0 --batch 32768 --chunk 32768 --no-cpu-baseline --no-r1cs-check --no-secondary"
+ARGS="--full --steps 1 --warmup 0 --batch 32768 --chunk 32768 --no-cpu-baseline --no-r1cs-check --no-secondary"
 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_STALL_sum TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum --output-format csv -d $OUT/${TAG}_pmc_st1 -- python3 $REPO/bench.py $ARGS > /dev/null 2> $OUT/${TAG}_pmc_st1.log
 rocprofv3 --pmc TCC_WRITE_sum TCC_TOO_MANY_EA_WRREQS_STALL_sum TCC_TAG_STALL_sum TCC_IB_STALL_sum --output-format csv -d $OUT/${TAG}_pmc_st2 -- python3 $REPO/bench.py $ARGS > /dev/null 2> $OUT/${TAG}_pmc_st2.log
 cd $REPO

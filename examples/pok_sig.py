@@ -8,6 +8,8 @@
     pok_sig.rs:32      create_random_proof                            -> frw_witness_ntt_verify_dev + frw_groth16_prove_dev
     pok_sig.rs:34-47   public inputs pk_ntt || hm_ntt; verify_proof   -> frw_groth16_verify (host pairing) on the instance buffer and the
                                                                         proof as the device wrote them; and again for a wrong statement
+    (a Proof on the wire)                                             -> frw_groth16_proofs_to_wire_dev: the 192 bytes of Proof::serialize,
+                                                                        verified from them by frw_groth16_verify_wire_dev
 
     python examples/pok_sig.py tests/golden/falcon_signed.json [--case 0] [--seed 1] [--json]
 """
@@ -74,18 +76,30 @@ def main():
     verifier.close()
     if accepted != 1 or accepted_other != 0:
         raise SystemExit("verify_proof: %d for the statement proved, %d for another one" % (accepted, accepted_other))
+    # the proof as it travels: Proof::serialize's 192 bytes, made on the device; a verifier that holds the key's bytes
+    # (VerifyingKey::serialize) checks it from them without leaving the device
+    wire, wire_status = frw.proofs_to_wire_dev(proof)
+    from_bytes = frw.Groth16Verifier.from_wire(frw.vk_to_wire(vk), device=0)
+    accepted_wire = int(from_bytes.verify_wire_dev(inst, wire)[0])
+    from_bytes.close()
+    proof_bytes = wire[0].cpu().numpy().tobytes()
+    if int(wire_status[0]) != 0 or accepted_wire != 1:
+        raise SystemExit("verification from the proof's 192 wire bytes: %d" % accepted_wire)
     # public inputs: pk_ntt || hm_ntt                                                        pok_sig.rs:38-45
     r_inv = pow(1 << 256, -1, R)
     public = [int.from_bytes(row.tobytes(), "little") * r_inv % R for row in inst[0, 1:].cpu().numpy().view(np.uint64)]
     hexl = lambda a: ["%016x" % int(v) for v in a]
     if args.json:
         print(json.dumps({"logn": logn, "verified": accepted == 1, "public_inputs": [str(x) for x in public], "proof": {"a": hexl(p[:12]), "b": hexl(p[12:36]), "c": hexl(p[36:])},
+                          "proof_wire": proof_bytes.hex(),
                           "vk": {k: (hexl(v) if v.ndim == 1 else [hexl(r) for r in v]) for k, v in vk.items()}}))
     else:
         print("Falcon-%d signature on %r: Groth16 proof made on the device" % (L.n, bytes.fromhex(case["msg"])))
         print("  %d constraints, %d witnesses, %d public inputs (pk_ntt || hm_ntt)" % (L.num_constraints, L.num_witness, len(public)))
         print("  A.x = 0x%s..." % "".join(reversed(hexl(p[:6])))[:48])
         print("  verify_proof: accepted; for another public key: rejected")
+        print("  proof, %d bytes as ark-serialize writes it: %s" % (len(proof_bytes), proof_bytes.hex()))
+        print("  verified again from those bytes on the device: accepted")
     eng.r1cs_free(r1cs)
     eng.groth16_pk_free(key)
     eng.close()

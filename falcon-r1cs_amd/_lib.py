@@ -137,6 +137,19 @@ PROTOTYPES = {
     "frw_groth16_verify_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
     "frw_diag_pairing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_groth16_proof_wire_bytes": (C.c_size_t, [C.c_int]),
+    "frw_groth16_vk_wire_bytes": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "frw_groth16_proofs_to_wire": (C.c_int, [C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "frw_groth16_proofs_from_wire": (C.c_int, [C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "frw_groth16_proofs_to_wire_dev": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_groth16_proofs_from_wire_dev": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_groth16_verify_wire_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "frw_groth16_verify_wire_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frw_groth16_vk_to_wire": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "frw_groth16_vk_load_wire": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_groth16_vk_load_wire_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_diag_wire_greater": (C.c_int, [C.c_void_p, C.c_void_p]),
     "frw_groth16_verify_full_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int]),
     "frw_groth16_verify_full_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -22,6 +22,7 @@
 #include "frw_device.h"
 #include "frw_pairing_dev.h"
 #include "frw_verify.h"
+#include "frw_wire.h"
 
 namespace frw {
 namespace {
@@ -244,6 +245,25 @@ size_t full_proofs_in_flight(const frw_groth16_vk *vk, size_t batch, int flags, 
     }
     return lo;
 }
+// frw_groth16_verify_wire_dev: the decoded proofs (384 bytes each) and the decoder's statuses in front of the chain's own workspace
+size_t wire_part_bytes(size_t k) { return 384 * k + ((4 * k + 15) & ~(size_t)15); }
+size_t wire_proofs_in_flight(const frw_groth16_vk *vk, size_t batch, int flags, size_t bytes)
+{
+    if (batch == 0 || wire_part_bytes(1) + full_workspace_bytes(vk, 1, flags) > bytes) return 0;
+    size_t lo = 1, hi = batch;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (wire_part_bytes(mid) + full_workspace_bytes(vk, mid, flags) <= bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// a proof the decoder refused is malformed for everything that follows (after prepare, which sets d_status from the instance vector)
+__global__ __launch_bounds__(256) void wire_status_kernel(uint64_t n, const int32_t *__restrict__ decoded, int32_t *__restrict__ status)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < n && decoded[g]) status[g] = -1;
+}
 }  // namespace
 }  // namespace frw
 
@@ -281,6 +301,54 @@ extern "C" int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batc
         if (rc == FRW_OK)
             rc = frw::pairing_dev::verify_proofs(vk, cnt, lo, d_proofs + lo * 48, d_prepared, d_status, flags, seed, d_accepted + lo,
                                                  d_batch_passed, d_pairing_ws, st);
+        if (rc != FRW_OK) return rc;
+    }
+    return FRW_OK;
+}
+
+// ---- the same from proofs in ark-serialize's wire format (frw_wire.h) ----------------------------------------------------------------
+extern "C" size_t frw_groth16_verify_wire_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags, int mode)
+{
+    if (mode != FRW_WIRE_COMPRESSED && mode != FRW_WIRE_UNCOMPRESSED) return 0;
+    const size_t full = frw_groth16_verify_full_workspace_bytes(vk, batch_in_flight, flags);
+    return full ? frw::wire_part_bytes(batch_in_flight) + full : 0;
+}
+
+extern "C" int frw_groth16_verify_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint8_t *d_wire,
+                                           int mode, int flags, const uint64_t *seed, int32_t *d_accepted, int32_t *d_batch_passed,
+                                           void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (!vk || !vk->msm || !vk->d_pairing) return FRW_E_INVALID_ARG;
+    if (encoding != FRW_ENC_MONTGOMERY && encoding != FRW_ENC_CANONICAL) return FRW_E_INVALID_ARG;
+    if (mode != FRW_WIRE_COMPRESSED && mode != FRW_WIRE_UNCOMPRESSED) return FRW_E_INVALID_ARG;
+    if (flags & ~(FRW_VERIFY_POINTS_ARE_CHECKED | FRW_VERIFY_BATCHED)) return FRW_E_INVALID_ARG;
+    if ((flags & FRW_VERIFY_BATCHED) && !seed) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    if (!d_instance || !d_wire || !d_accepted || !d_workspace || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
+    const size_t chunk = frw::wire_proofs_in_flight(vk, batch, flags, workspace_bytes);
+    if (chunk == 0) return FRW_E_INVALID_ARG;
+    hipError_t e = hipSetDevice(vk->device);
+    if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n = vk->num_instance, wire_bytes = frw::wire::proof_bytes(mode);
+    uint64_t *d_decoded = (uint64_t *)d_workspace;
+    int32_t *d_decode_status = (int32_t *)(d_decoded + 48 * chunk);
+    char *ws = (char *)d_workspace + frw::wire_part_bytes(chunk);
+    size_t prepare_part = 0, msm_part = 0;
+    frw::full_workspace_bytes(vk, chunk, flags, &prepare_part);
+    frw::workspace_bytes(vk, chunk, &msm_part);
+    uint64_t *d_prepared = (uint64_t *)(ws + msm_part);
+    int32_t *d_status = (int32_t *)(d_prepared + 12 * chunk);
+    void *d_pairing_ws = ws + prepare_part;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
+        int rc = frw::wire::decode_proofs_launch(cnt, d_wire + lo * wire_bytes, mode, d_decoded, d_decode_status, st);
+        if (rc == FRW_OK) rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, d_prepared, d_status, ws, msm_part, st);
+        if (rc != FRW_OK) return rc;
+        hipLaunchKernelGGL(frw::wire_status_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (uint64_t)cnt,
+                           (const int32_t *)d_decode_status, d_status);
+        rc = frw::pairing_dev::verify_proofs(vk, cnt, lo, d_decoded, d_prepared, d_status, flags, seed, d_accepted + lo, d_batch_passed,
+                                             d_pairing_ws, st);
         if (rc != FRW_OK) return rc;
     }
     return FRW_OK;

@@ -197,6 +197,59 @@ class Groth16Verifier:
               "frw_groth16_verify_full_dev")
         return out
 
+    @classmethod
+    def from_wire(cls, data, device=None, compressed=True):
+        """The key from ark-serialize's bytes (VerifyingKey::serialize / serialize_uncompressed; frw.h has the format): decoded and
+        loaded with every point checked -- on the host (frw_groth16_vk_load_wire), or with `device` given gamma_abc_g1 decoded and
+        checked there (frw_groth16_vk_load_wire_dev), the handle then serving the device verifiers too."""
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        self._h = C.c_void_p()
+        self.device = device
+        data = bytes(data)
+        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+        head = 336 if compressed else 672
+        self.num_instance = int.from_bytes(data[head:head + 8], "little") if len(data) >= head + 8 else 0
+        buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+        if device is None:
+            check(self._lib.frw_groth16_vk_load_wire(buf, len(data), mode, C.byref(self._h)), "frw_groth16_vk_load_wire")
+        else:
+            check(self._lib.frw_groth16_vk_load_wire_dev(int(device), buf, len(data), mode, C.byref(self._h)), "frw_groth16_vk_load_wire_dev")
+        return self
+
+    def wire_workspace_bytes(self, batch_in_flight, flags=0, compressed=True):
+        """Device workspace of verify_wire_dev for `batch_in_flight` proofs (0 for a host-only key)."""
+        return int(self._lib.frw_groth16_verify_wire_workspace_bytes(self._h, int(batch_in_flight), int(flags),
+                                                                     WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED))
+
+    def verify_wire_dev(self, d_instance, d_wire, compressed=True, encoding=ENC_MONTGOMERY, flags=0, batched=False, seed=None, stream=0,
+                        workspace=None, batch_passed=None):
+        """verify_full_dev with the proofs as ark-serialize's bytes (frw_groth16_verify_wire_dev): d_wire is a device uint8 tensor
+        [batch, 192] (compressed) or [batch, 384]; decoded on the device, -1 where the bytes are malformed, otherwise
+        verify_full_dev's verdict for the decoded proof.  Everything else as verify_full_dev."""
+        import os
+        import torch
+        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+        per = 192 if compressed else 384
+        if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
+            raise FrwError(-1, "verify_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
+        batch = d_wire.numel() // per
+        flags = int(flags) | (VERIFY_BATCHED if batched else 0)
+        out = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
+        seed_arr = None
+        if flags & VERIFY_BATCHED:
+            seed_arr = np.frombuffer(os.urandom(32), dtype=np.uint64).copy() if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(4)
+        if workspace is None:
+            workspace = torch.empty(max(self.wire_workspace_bytes(batch, flags, compressed), 16), dtype=torch.uint8, device=d_wire.device)
+        ws_bytes = workspace.numel() * workspace.element_size()
+        check(self._lib.frw_groth16_verify_wire_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding),
+                                                    C.c_void_p(d_wire.data_ptr()), mode, flags,
+                                                    None if seed_arr is None else seed_arr.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
+                                                    None if batch_passed is None else C.c_void_p(batch_passed.data_ptr()),
+                                                    C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_verify_wire_dev")
+        return out
+
     def close(self):
         if self._h:
             self._lib.frw_groth16_vk_free(self._h)
@@ -207,6 +260,81 @@ class Groth16Verifier:
             self.close()
         except Exception:
             pass
+
+
+WIRE_COMPRESSED, WIRE_UNCOMPRESSED = 0, 1      # frw.h FRW_WIRE_*
+
+
+def proof_wire_bytes(compressed=True):
+    return 192 if compressed else 384
+
+
+def proofs_to_wire(proofs, compressed=True):
+    """Proofs in limbs (uint64[batch, 48], as the prover writes them) -> (uint8[batch, 192 or 384] in ark-serialize's format, what
+    Proof::deserialize / deserialize_uncompressed reads; int32[batch] status: -1 and zero bytes where a coordinate's limbs are >= q).
+    Host code (frw_groth16_proofs_to_wire)."""
+    proofs = np.ascontiguousarray(proofs).view(np.uint64).reshape(-1, 48)
+    out = np.zeros((proofs.shape[0], proof_wire_bytes(compressed)), dtype=np.uint8)
+    status = np.zeros(proofs.shape[0], dtype=np.int32)
+    check(load_library().frw_groth16_proofs_to_wire(proofs.shape[0], proofs.ctypes.data_as(C.c_void_p), 0 if compressed else 1,
+                                                    out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_proofs_to_wire")
+    return out, status
+
+
+def proofs_from_wire(wire, compressed=True):
+    """ark-serialize's bytes (anything of batch x 192 or 384 bytes) -> (uint64[batch, 48] limbs, int32[batch] status: -1 and zero limbs
+    where the bytes are malformed).  Host code (frw_groth16_proofs_from_wire)."""
+    per = proof_wire_bytes(compressed)
+    wire = np.ascontiguousarray(np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray)) else wire, dtype=np.uint8).reshape(-1, per)
+    out = np.zeros((wire.shape[0], 48), dtype=np.uint64)
+    status = np.zeros(wire.shape[0], dtype=np.int32)
+    check(load_library().frw_groth16_proofs_from_wire(wire.shape[0], wire.ctypes.data_as(C.c_void_p), 0 if compressed else 1,
+                                                      out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_proofs_from_wire")
+    return out, status
+
+
+def proofs_to_wire_dev(d_proofs, compressed=True, stream=0):
+    """proofs_to_wire on the device of `d_proofs` (a device tensor [batch, 48] of 64-bit limbs): (uint8[batch, 192 or 384], int32[batch])
+    device tensors, ordered on `stream`, the host function's bytes."""
+    import torch
+    batch = d_proofs.shape[0]
+    out = torch.empty((batch, proof_wire_bytes(compressed)), dtype=torch.uint8, device=d_proofs.device)
+    status = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
+    check(load_library().frw_groth16_proofs_to_wire_dev(d_proofs.device.index or 0, batch, C.c_void_p(d_proofs.data_ptr()), 0 if compressed else 1,
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)),
+          "frw_groth16_proofs_to_wire_dev")
+    return out, status
+
+
+def proofs_from_wire_dev(d_wire, compressed=True, stream=0):
+    """proofs_from_wire on the device of `d_wire` (a contiguous device uint8 tensor of batch x 192 or 384 bytes): (int64[batch, 48] limbs,
+    int32[batch] status) device tensors, ordered on `stream`, the host function's values."""
+    import torch
+    per = proof_wire_bytes(compressed)
+    if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
+        raise FrwError(-1, "proofs_from_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
+    batch = d_wire.numel() // per
+    out = torch.empty((batch, 48), dtype=torch.int64, device=d_wire.device)
+    status = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
+    check(load_library().frw_groth16_proofs_from_wire_dev(d_wire.device.index or 0, batch, C.c_void_p(d_wire.data_ptr()), 0 if compressed else 1,
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)),
+          "frw_groth16_proofs_from_wire_dev")
+    return out, status
+
+
+def vk_to_wire(vk, compressed=True):
+    """A verifying key in limbs (the dict WitnessEngine.groth16_setup returns, or the flat uint64 array of frw_groth16_setup's vk_out)
+    -> bytes in ark-serialize's format (what VerifyingKey::deserialize reads): 344 + 48 n or 680 + 96 n bytes."""
+    if isinstance(vk, dict):
+        vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
+    vk = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
+    if vk.size < 96 or (vk.size - 84) % 12:
+        raise FrwError(-1, "vk_to_wire", "verifying key: expected 84 + 12 x num_instance uint64 values")
+    n = (vk.size - 84) // 12
+    lib = load_library()
+    out = np.zeros(lib.frw_groth16_vk_wire_bytes(n, 0 if compressed else 1), dtype=np.uint8)
+    check(lib.frw_groth16_vk_to_wire(vk.ctypes.data_as(C.c_void_p), n, 0 if compressed else 1, out.ctypes.data_as(C.c_void_p)), "frw_groth16_vk_to_wire")
+    return out.tobytes()
 
 
 def diag_pairing(g1, g2):

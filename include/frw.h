@@ -633,6 +633,70 @@ size_t frw_groth16_verify_full_workspace_bytes(const frw_groth16_vk *vk, size_t 
 int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint64_t *d_proofs,
                                 int flags, const uint64_t *seed, int32_t *d_accepted, int32_t *d_batch_passed, void *d_workspace,
                                 size_t workspace_bytes, void *stream);
+
+/* ---- proofs and verifying keys in arkworks' wire format (frw_wire.hip) ----------------------------------------------------------------
+ * What ark-groth16's Proof and VerifyingKey are on disk, in a message or across a process boundary: ark-serialize's CanonicalSerialize
+ * (ark-serialize / ark-ec 0.3, short-Weierstrass affine points over BLS12-381), restated here from the crates' sources (parity unpinned:
+ * DESIGN.md).  Everything above takes and gives uint64_t limbs in ark-ff's Montgomery form; these calls convert, on the host or on the
+ * device, by the same code.
+ *   Fq            48 bytes, little-endian, the CANONICAL integer (not x 2^384); a value >= q is malformed
+ *   Fq2           c0 then c1, 96 bytes
+ *   flags         the top two bits of the last byte of the last field element written: bit 7 = "y is the greater one", bit 6 = infinity
+ *                 (bit 5 of an Fq top byte is always 0; the flags are masked off before the >= q test)
+ *   greater       y > -y as ark orders fields: Fq by canonical integer, Fq2 by c1 first, then c0
+ *   compressed    x with flags -- G1 48 bytes, G2 96.  Infinity: x = 0, bit 6 set, bit 7 clear.  y = sqrt(x^3 + b), b = 4 (G1) or
+ *                 4 (1 + u) (G2); no root -> malformed; the greater of y, -y if and only if bit 7 is set
+ *   uncompressed  x, then y carrying only the infinity flag -- G1 96 bytes, G2 192.  Infinity: x = y = 0, bit 6 set.  The curve
+ *                 equation is checked
+ *   proof         A | B | C: 192 bytes compressed, 384 uncompressed
+ *   key           alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | le64(n) | gamma_abc_g1[n]: 344 + 48 n bytes compressed, 680 + 96 n uncompressed
+ * ONE encoding per point, as x + q is refused for x everywhere above: both flag bits set, infinity with a non-zero coordinate, and bit 7
+ * set in an uncompressed point are malformed.  (ark 0.3 is laxer on the last two as far as this restatement goes: it ignores the
+ * coordinates of a point flagged infinite and bit 7 of an uncompressed y.)  Subgroup membership is NOT the codec's business: the
+ * verifier's own checks make it unless the caller sets FRW_VERIFY_POINTS_ARE_CHECKED, and the key loaders always make it. */
+#define FRW_WIRE_COMPRESSED   0
+#define FRW_WIRE_UNCOMPRESSED 1
+/* bytes of one proof / of a key with num_instance gamma_abc_g1 points; 0 for a bad mode */
+size_t frw_groth16_proof_wire_bytes(int mode);
+size_t frw_groth16_vk_wire_bytes(size_t num_instance, int mode);
+/* HOST codec (no device needed).  proofs: uint64_t[batch][48] as frw_groth16_prove_dev writes them; out / in: batch x
+ * frw_groth16_proof_wire_bytes(mode) bytes, any alignment; status: int32_t[batch], 0 or -1 -- encoding: a coordinate's limbs are >= q
+ * (nothing else is checked: a point off its curve is encoded as it stands, and compressed it comes back as another point or as
+ * malformed); decoding: any malformed case above in any of the three points.  A refused proof's output is all zero bytes / limbs.  The
+ * call itself returns FRW_OK; FRW_E_INVALID_ARG for a null pointer or a bad mode. */
+int frw_groth16_proofs_to_wire(size_t batch, const uint64_t *proofs, int mode, uint8_t *out, int32_t *status);
+int frw_groth16_proofs_from_wire(size_t batch, const uint8_t *in, int mode, uint64_t *proofs, int32_t *status);
+/* The same with DEVICE pointers on `device`: stream-ordered on `stream`, allocates nothing, does not synchronise -- capture-safe; bytes,
+ * limbs and statuses are bit-equal to the host functions'.  Decoding a compressed proof is four square roots in Fq (one each for A and
+ * C, two for B) and an inversion.  No device -> FRW_E_NO_DEVICE (no host fallback). */
+int frw_groth16_proofs_to_wire_dev(int device, size_t batch, const uint64_t *d_proofs, int mode, uint8_t *d_out, int32_t *d_status, void *stream);
+int frw_groth16_proofs_from_wire_dev(int device, size_t batch, const uint8_t *d_in, int mode, uint64_t *d_proofs, int32_t *d_status, void *stream);
+/* frw_groth16_verify_full_dev with the proofs as wire bytes (d_wire: batch x frw_groth16_proof_wire_bytes(mode) bytes in device memory,
+ * any alignment): every pass decodes its proofs into the workspace and runs the chain above on them unchanged.  d_accepted[i] = -1 where
+ * the decoder refused proof i; otherwise what frw_groth16_verify_full_dev gives for the decoded limbs and the same flags.  Same flags,
+ * chunking, refusals and capture-safety as frw_groth16_verify_full_dev; a bad mode -> FRW_E_INVALID_ARG.  FRW_VERIFY_BATCHED: rho_i
+ * hashes the DECODED 384 limb bytes of proof i, exactly as frw_groth16_verify_full_dev does -- not the wire bytes -- and a refused proof
+ * is left out of the batched check like any other malformed one.
+ * Workspace: frw_groth16_verify_wire_workspace_bytes(vk, batch_in_flight, flags, mode) bytes, 16-byte aligned: for k proofs in flight,
+ * 384 k bytes of decoded limbs and 4 k of statuses rounded up to 16 on top of frw_groth16_verify_full_workspace_bytes(vk, k, flags)
+ * (388 bytes a proof plus padding); 0 for a bad mode or where that function gives 0. */
+size_t frw_groth16_verify_wire_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags, int mode);
+int frw_groth16_verify_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint8_t *d_wire,
+                                int mode, int flags, const uint64_t *seed, int32_t *d_accepted, int32_t *d_batch_passed, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+/* Keys.  frw_groth16_vk_to_wire (host): vk in the layout frw_groth16_setup writes -> frw_groth16_vk_wire_bytes(num_instance, mode) bytes;
+ * FRW_E_INVALID_ARG (and zero bytes) if a coordinate's limbs are >= q, for num_instance = 0, a null pointer or a bad mode.
+ * frw_groth16_vk_load_wire: decodes on the host and goes through frw_groth16_vk_load (every point checked).
+ * frw_groth16_vk_load_wire_dev: the four fixed points decoded on the host, gamma_abc_g1 on `device` (a lane per point), then
+ * everything frw_groth16_vk_load_dev does -- every point checked, no vouching flag; the handle serves every verifier above.
+ * FRW_E_INVALID_ARG for both loaders: a length that is not frw_groth16_vk_wire_bytes(n, mode) for the embedded n (truncated, over-long),
+ * n = 0, any malformed point, and whatever the limb loaders refuse.  No device -> FRW_E_NO_DEVICE (_dev only; no host fallback). */
+int frw_groth16_vk_to_wire(const uint64_t *vk, size_t num_instance, int mode, uint8_t *out);
+int frw_groth16_vk_load_wire(const uint8_t *bytes, size_t len, int mode, frw_groth16_vk **out);
+int frw_groth16_vk_load_wire_dev(int device, const uint8_t *bytes, size_t len, int mode, frw_groth16_vk **out);
+/* diagnostics for the codec's tests: the "greater" test on canonical integers (uint64_t[6] each; c1 NULL: the Fq order of c0, else
+ * the Fq2 order, c1 first) -> 1 if y > -y, else 0; FRW_E_INVALID_ARG for a null c0 */
+int frw_diag_wire_greater(const uint64_t *c0, const uint64_t *c1);
 /* frw_diag_pairing for `count` pairs on `device` (host buffers: g1 count x 12, g2 count x 24, out count x 72 uint64_t, the same basis):
  * the device pairing's kernels, for the parity tests.  Allocates and synchronises.  A point off its curve -> FRW_E_INVALID_ARG; no
  * device -> FRW_E_NO_DEVICE (no host fallback). */

@@ -121,6 +121,8 @@ pub struct frw_groth16_vk {
 }
 pub const FRW_VERIFY_POINTS_ARE_CHECKED: c_int = 1;
 pub const FRW_VERIFY_BATCHED: c_int = 2;
+pub const FRW_WIRE_COMPRESSED: c_int = 0;
+pub const FRW_WIRE_UNCOMPRESSED: c_int = 1;
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct frw_groth16_pk_desc_t {
@@ -289,6 +291,23 @@ extern "C" {
                                        d_proofs: *const u64, flags: c_int, seed: *const u64, d_accepted: *mut i32,
                                        d_batch_passed: *mut i32, d_workspace: *mut c_void, workspace_bytes: usize,
                                        stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_proof_wire_bytes(mode: c_int) -> usize;
+    pub fn frw_groth16_vk_wire_bytes(num_instance: usize, mode: c_int) -> usize;
+    pub fn frw_groth16_proofs_to_wire(batch: usize, proofs: *const u64, mode: c_int, out: *mut u8, status: *mut i32) -> c_int;
+    pub fn frw_groth16_proofs_from_wire(batch: usize, input: *const u8, mode: c_int, proofs: *mut u64, status: *mut i32) -> c_int;
+    pub fn frw_groth16_proofs_to_wire_dev(device: c_int, batch: usize, d_proofs: *const u64, mode: c_int, d_out: *mut u8,
+                                          d_status: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_proofs_from_wire_dev(device: c_int, batch: usize, d_in: *const u8, mode: c_int, d_proofs: *mut u64,
+                                            d_status: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_verify_wire_workspace_bytes(vk: *const frw_groth16_vk, batch_in_flight: usize, flags: c_int, mode: c_int) -> usize;
+    pub fn frw_groth16_verify_wire_dev(vk: *const frw_groth16_vk, batch: usize, d_instance: *const u64, encoding: c_int,
+                                       d_wire: *const u8, mode: c_int, flags: c_int, seed: *const u64, d_accepted: *mut i32,
+                                       d_batch_passed: *mut i32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                       stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_vk_to_wire(vk: *const u64, num_instance: usize, mode: c_int, out: *mut u8) -> c_int;
+    pub fn frw_groth16_vk_load_wire(bytes: *const u8, len: usize, mode: c_int, out: *mut *mut frw_groth16_vk) -> c_int;
+    pub fn frw_groth16_vk_load_wire_dev(device: c_int, bytes: *const u8, len: usize, mode: c_int, out: *mut *mut frw_groth16_vk) -> c_int;
+    pub fn frw_diag_wire_greater(c0: *const u64, c1: *const u64) -> c_int;
     pub fn frw_diag_pairing_dev(device: c_int, count: usize, g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,
                                  d_msg_off: *const u64, d_hm: *mut u16, stream: *mut c_void) -> c_int;

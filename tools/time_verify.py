@@ -9,7 +9,11 @@ frw_groth16_prepare_inputs_dev, frw_groth16_verify_dev).  One JSON object per ca
       1,024 proofs: beyond that the host's pairings alone take many seconds a repetition
 (b) and (c) are statements made in the exponent (tests/test_gpu_verify_dev.py: gamma_abc_g1[i] = g_i G1 from the oracle's fixed-base
 multiples, A = a G1, B = b G2, C solved for), 14-bit inputs.  Key loads: host with every point checked, host vouched
-(FRW_VK_POINTS_ARE_CHECKED), device (every point checked there).  usage: python tools/time_verify.py [a|b|c|f ...] [reps=3]"""
+(FRW_VK_POINTS_ARE_CHECKED), device (every point checked there).
+  --wire  4,096 Falcon-1024 proofs through frw_groth16_verify_wire_dev (compressed and uncompressed wire bytes) against
+      frw_groth16_verify_full_dev on limbs in the same process, HIP-event medians; the encode and the decode alone; the
+      1,571,841-input key loaded by frw_groth16_vk_load_wire_dev against frw_groth16_vk_load_dev
+usage: python tools/time_verify.py [a|b|c|f ...] [--wire] [reps=3]"""
 import json
 import os
 import random
@@ -158,7 +162,103 @@ def full_leg(reps, sizes=(1, 64, 1024, 4096, 16384), host_up_to=1024):
     host.close()
 
 
+def event_ms(fn, reps):
+    """HIP-event times of fn() on the current stream, in ms: (median, min), after two warm-ups.  fn is the C entry point alone: its
+    outputs are allocated before the timing, not inside it."""
+    fn()
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return round(sorted(times)[len(times) // 2], 3), round(min(times), 3)
+
+
+def wire_leg(oracle, reps, n=4096):
+    """--wire: verification from ark-serialize's bytes (frw_groth16_verify_wire_dev) against the limbs path (frw_groth16_verify_full_dev)
+    in the same process, the decode alone, and a key loaded from bytes against the same key loaded from limbs.  The timed calls are the
+    C entry points with every output allocated beforehand; the codec alone (well under a millisecond) gets five times the repetitions."""
+    import ctypes as C
+    reps = max(reps, 11)
+    short_reps = 5 * reps
+    name, vk, inst, proofs = falcon_case()
+    devk = frw.Groth16Verifier(vk, device=0)
+    lib, dev = frw.load_library(), inst.device
+    idx = torch.arange(n, device=dev) % inst.shape[0]
+    d_inst, d_proofs = inst[idx].contiguous(), proofs[idx].contiguous()
+    s0 = torch.cuda.current_stream().cuda_stream
+    ws = torch.empty(devk.wire_workspace_bytes(n, 0, False), dtype=torch.uint8, device=dev)
+    verdicts = torch.empty(n, dtype=torch.int32, device=dev)
+    back = torch.empty((n, 48), dtype=torch.int64, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+
+    def call(rc):
+        if rc:
+            raise RuntimeError("frw call failed: %d" % rc)
+
+    def verify_limbs():
+        call(lib.frw_groth16_verify_full_dev(devk._h, n, ptr(d_inst), frw.ENC_MONTGOMERY, ptr(d_proofs), 0, None, ptr(verdicts), None, ptr(ws),
+                                             ws.numel(), C.c_void_p(s0)))
+
+    limbs = event_ms(verify_limbs, reps)
+    assert int((verdicts == 1).sum()) == n
+    out = {"case": "wire: %d Falcon-1024 proofs" % n, "batch": n, "reps": reps, "codec_reps": short_reps,
+           "timed": "C entry points, outputs allocated beforehand, HIP events on one stream",
+           "verify_full_dev_limbs_ms": {"median": limbs[0], "min": limbs[1]}}
+    for compressed in (True, False):
+        tag, mode = ("compressed", 0) if compressed else ("uncompressed", 1)
+        d_wire = torch.empty((n, frw.proof_wire_bytes(compressed)), dtype=torch.uint8, device=dev)
+        enc = event_ms(lambda: call(lib.frw_groth16_proofs_to_wire_dev(0, n, ptr(d_proofs), mode, ptr(d_wire), ptr(st), C.c_void_p(s0))), short_reps)
+        assert not st.any().item()
+        dec = event_ms(lambda: call(lib.frw_groth16_proofs_from_wire_dev(0, n, ptr(d_wire), mode, ptr(back), ptr(st), C.c_void_p(s0))), short_reps)
+        assert bool((back == d_proofs).all()) and not st.any().item()
+        verdicts.zero_()
+        ver = event_ms(lambda: call(lib.frw_groth16_verify_wire_dev(devk._h, n, ptr(d_inst), frw.ENC_MONTGOMERY, ptr(d_wire), mode, 0, None,
+                                                                    ptr(verdicts), None, ptr(ws), ws.numel(), C.c_void_p(s0))), reps)
+        assert int((verdicts == 1).sum()) == n
+        out[tag] = {"encode_ms": {"median": enc[0], "min": enc[1]}, "decode_ms": {"median": dec[0], "min": dec[1]},
+                    "verify_wire_dev_ms": {"median": ver[0], "min": ver[1]}, "over_limbs": round(ver[0] / limbs[0], 3),
+                    "proofs_per_s": round(n / (1e-3 * ver[0]), 1)}
+    # (the limbs path once more, after the wire runs: drift shows here)
+    again = event_ms(verify_limbs, reps)
+    out["verify_full_dev_limbs_again_ms"] = {"median": again[0], "min": again[1]}
+    devk.close()
+    print(json.dumps(out), flush=True)
+    del ws, d_inst, d_proofs
+    torch.cuda.empty_cache()
+    # the largest key this tool uses: loaded from limbs and from bytes, every point checked on the device both ways
+    k = V.key(oracle, V.BIG)
+    flat = k.limbs()
+    out = {"case": "wire: a key of %d inputs" % V.BIG, "num_instance": V.BIG}
+    h, s = timed(lambda: frw.Groth16Verifier(flat, device=0))
+    h.close()
+    loads = []
+    for _ in range(3):
+        h, s = timed(lambda: frw.Groth16Verifier(flat, device=0))
+        h.close()
+        loads.append(s)
+    out["vk_load_dev_s"] = {"median": round(sorted(loads)[1], 4), "min": round(min(loads), 4)}
+    for compressed in (True, False):
+        data, s = timed(lambda: frw.vk_to_wire(flat, compressed))
+        loads = []
+        for _ in range(3):
+            h, t = timed(lambda: frw.Groth16Verifier.from_wire(data, device=0, compressed=compressed))
+            h.close()
+            loads.append(t)
+        out["compressed" if compressed else "uncompressed"] = {"bytes": len(data), "vk_to_wire_host_s": round(s, 4),
+                                                               "vk_load_wire_dev_s": {"median": round(sorted(loads)[1], 4), "min": round(min(loads), 4)}}
+    print(json.dumps(out), flush=True)
+
+
 def main():
+    if "--wire" in sys.argv:
+        sys.argv = [a for a in sys.argv if a != "--wire"] + ["wire"]
     args = [a for a in sys.argv[1:] if not a.isdigit()] or ["a", "b", "c"]
     reps = int(next((a for a in sys.argv[1:] if a.isdigit()), 3))
     oracle = T.load_oracle()
@@ -172,6 +272,8 @@ def main():
             run(*exponent_case(oracle, V.BIG, 1), reps)
         elif c == "f":
             full_leg(reps)
+        elif c == "wire":
+            wire_leg(oracle, reps)
         torch.cuda.empty_cache()
 
 

@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <mutex>
+#include "frw_layout.h"       // frw::Carve: a slot is carved into 256-byte aligned pieces (run once with base = nullptr to size it)
 
 namespace frw {
 
@@ -100,20 +101,6 @@ struct DrainOnExit {
         if (settled) return;
         if (a.compute) (void)hipStreamSynchronize(a.compute);
         if (a.copy) (void)hipStreamSynchronize(a.copy);
-    }
-};
-
-// carves 256-byte aligned pieces out of one slot (run once with base = nullptr to size the slot)
-struct Carve {
-    char *base;
-    size_t off = 0;
-    explicit Carve(void *b) : base((char *)b) {}
-    template <class T = void>
-    T *take(size_t bytes)
-    {
-        T *p = (T *)(base + off);
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
     }
 };
 

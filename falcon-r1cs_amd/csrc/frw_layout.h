@@ -1,0 +1,308 @@
+// frw_layout.h -- where the arrays of every caller-allocated device workspace live: the MSMs', the Groth16 prover's, the verification
+// chains'.  One function per layout: it walks the workspace once and returns the pointers; the size a caller is told is the same walk
+// from a null base.  Host code only, nothing of the HIP runtime is called: tests/test_layout_host.py compiles this header with g++ and
+// checks every offset against tests/golden/workspace_layouts.json.  The sizes and offsets are ABI: callers
+// allocate by them, and the alignment of a buffer moves kernel timings.  The constants the layouts depend on are here for that reason;
+// what they mean to the kernels is told where the kernels are (frw_msm.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace frw {
+
+// walks a workspace: take() hands out the next piece and steps over it, rounded up to `align` bytes (base = nullptr: only sizes)
+struct Carve {
+    char *base;
+    size_t off = 0;
+    explicit Carve(void *b) : base((char *)b) {}
+    template <class T = void>
+    T *take(size_t bytes, size_t align = 256)
+    {
+        T *p = (T *)(base + off);
+        off += (bytes + align - 1) & ~(align - 1);
+        return p;
+    }
+    uint32_t *words(size_t count) { return take<uint32_t>(count * 4, 4); }
+    void *at() const { return base + off; }
+    void align_to(size_t a) { off = (off + a - 1) & ~(a - 1); }       // (of the offset: every entry point checks its base)
+    static size_t up(size_t bytes, size_t a) { return (bytes + a - 1) & ~(a - 1); }
+};
+
+constexpr int MSM_C = 16;                       // window bits
+constexpr int MSM_W = 16;                       // windows: 16 x 16 = 256 >= 255 bits
+constexpr int MSM_BUCKETS = 1 << (MSM_C - 1);   // signed digits: |d| in 1 .. 2^15
+constexpr int MSM_FOLD1_THREADS = 4096;         // partial sums per signature at most (first stage: 8, 32 or 64 buckets per thread)
+constexpr int G1_BK_WORDS = 60, G2_BK_WORDS = 116;      // words of a bucket (Grp<F>::BK_WORDS): X, Y, ZZ, ZZZ limbs + the infinity flag
+constexpr int MSM_SLICES = 32, MSM_SLICES_LONE = 224;
+constexpr int WIDE_C = 20, WIDE_W = 13, WIDE_H = 1 << (WIDE_C - MSM_C), WIDE_ROWS = WIDE_W * WIDE_H;
+constexpr uint32_t WIDE_MAX_ITEMS = 65536;       // >= 32,768 + (32,768 / 1.5) 33 / 32 (finer = 1)
+constexpr int WIDE_SLICES = 128;                 // slices of a window in the bins' sort (whole tiles each)
+constexpr int WIDE_BINS = 512, WIDE_BIN_BUCKETS = MSM_BUCKETS * WIDE_H / WIDE_BINS, WIDE_ALL_BINS = WIDE_W * WIDE_BINS, WIDE_TILE = 4096;
+constexpr int WIDE_PARTS = 32;
+constexpr int MSM_MAX_ITEMS = 131072;          // >= 32,768 + 32,768 / (1.5 / 4): the finest split (a lone signature), a multiple of 64
+constexpr int MSM_MAX_ITEMS_LARGE = 32768 + (32768 * 24 * 2 / 3) / 32 * 33 + 64;     // 573,504
+static_assert(MSM_MAX_ITEMS_LARGE % 64 == 0 && MSM_MAX_ITEMS >= 32768 + (32768 * 4 * 2 / 3) / 32 * 33 + 64, "whole wavefronts; the finest split fits");
+// a bare handle's rows are windows of one sum: sixteen of them fill the chip with items of the buckets' own size (finer = 1)
+__host__ __device__ constexpr uint32_t msm_max_items(uint32_t n, bool bare = false)
+{
+    return !bare && n > (1u << 18) ? (uint32_t)MSM_MAX_ITEMS_LARGE : (uint32_t)MSM_MAX_ITEMS;
+}
+constexpr int NMSM_C = 8, NMSM_W = 32, NMSM_BUCKETS = 128;
+__host__ __device__ constexpr uint32_t nmsm_slices(uint32_t n) { return n > (1u << 18) ? 128u : 16u; }
+constexpr int NMSM_TARGET_ITEMS_MIN = 2048, NMSM_TARGET_ITEMS_MAX = 65536;
+__host__ __device__ constexpr uint32_t nmsm_target_items(uint32_t n)
+{
+    const uint32_t t = (n / 128 + 2047) / 2048 * 2048;
+    return t < (uint32_t)NMSM_TARGET_ITEMS_MIN ? (uint32_t)NMSM_TARGET_ITEMS_MIN : t > (uint32_t)NMSM_TARGET_ITEMS_MAX ? (uint32_t)NMSM_TARGET_ITEMS_MAX : t;
+}
+__host__ __device__ constexpr uint32_t nmsm_max_items(uint32_t n) { return nmsm_target_items(n) + 256; }
+constexpr int NMSM_ONES_MAX = 4096, NMSM_ONES_MAX_LARGE = 65536;
+__host__ __device__ constexpr uint32_t nmsm_ones_max(uint32_t n) { return n > (1u << 18) ? (uint32_t)NMSM_ONES_MAX_LARGE : (uint32_t)NMSM_ONES_MAX; }
+
+// ---- the dense pipeline: per grid row (a signature; a bare handle: a window), every array but the last two a multiple of four words per
+// row, so that whatever the number of points everything before them is 16-byte aligned (the items are read two words at a time).
+// `bw`: the group's words per bucket.  The sort's per-slice histograms borrow `buckets` (a lone row: `partial_items`) before either is written.
+static_assert((size_t)MSM_SLICES * 4 <= (size_t)G1_BK_WORDS * 4, "the slice histograms borrow the buckets' memory");
+static_assert((size_t)MSM_SLICES_LONE * MSM_BUCKETS <= (size_t)MSM_MAX_ITEMS * G1_BK_WORDS, "... or, for a lone signature, the work items'");
+struct MsmBufs {
+    uint32_t *counts, *offsets, *order, *item_first, *item_count, *ones_count, *items, *buckets, *partial, *partial_items, *entries, *ones_list, *end;
+    int16_t *digits;            // a bare handle: int16[16][n], the windows' digits of the scalar vector being summed
+    uint32_t *window_sums;      // ... and its sixteen window sums, waiting for Horner's rule
+    uint32_t max_items;
+    size_t ent_stride, ones_stride, bytes;
+};
+// counts .. partial: what the wide layout shares with the dense one (b.max_items is set)
+inline void msm_layout_head(Carve &c, MsmBufs &b, size_t rows, size_t bw)
+{
+    b.counts = c.words(rows * MSM_BUCKETS); b.offsets = c.words(rows * MSM_BUCKETS);
+    b.order = c.words(rows * MSM_BUCKETS); b.item_first = c.words(rows * MSM_BUCKETS);
+    b.item_count = c.words(rows * 4); b.ones_count = c.words(rows * 4);         // [rows], four words each
+    b.items = c.words(rows * (size_t)b.max_items * 2);                 // [rows][max_items][2]
+    b.buckets = c.words(rows * (size_t)MSM_BUCKETS * bw);
+    b.partial = c.words(rows * (size_t)MSM_FOLD1_THREADS * bw);
+}
+inline MsmBufs msm_layout(void *ws, size_t rows, uint32_t n, bool bare, size_t bw)
+{
+    MsmBufs b{};
+    Carve c(ws);
+    b.max_items = msm_max_items(n, bare);
+    b.ent_stride = bare ? (size_t)n : (size_t)MSM_W * n;
+    b.ones_stride = bare ? 0 : (size_t)n;                               // a bare handle's ones are digits like any other
+    msm_layout_head(c, b, rows, bw);
+    b.partial_items = c.words(rows * (size_t)b.max_items * bw);
+    b.entries = c.words(rows * b.ent_stride);
+    b.ones_list = c.words(rows * b.ones_stride);
+    if (bare) b.digits = (int16_t *)c.words(((size_t)MSM_W * n * 2 + 3) / 4);
+    b.end = (uint32_t *)c.at();
+    if (bare) { c.align_to(16); b.window_sums = c.words((size_t)MSM_W * bw); }
+    b.bytes = Carve::up(c.off, 16);
+    return b;
+}
+// thirteen 20-bit windows (WIDE_*): 208 rows.  The parts' histograms borrow `rows.buckets`, the digits `entries` (dead once the bins are
+// sorted; the entries are written after that).
+struct MsmWideBufs {
+    MsmBufs rows;                       // the 208 rows' arrays (entries apart: below)
+    uint32_t *partial_plain, *slice_hist, *bin_count, *row_count, *s1, *s0, *window_sums, *entries, *end;
+    unsigned long long *row_start, *bin_start;
+    uint2 *coarse;
+    int32_t *digits;
+    size_t bytes;
+};
+inline MsmWideBufs msm_layout_wide(void *ws, uint32_t n, size_t bw)
+{
+    constexpr size_t R = WIDE_ROWS;
+    MsmWideBufs w{};
+    MsmBufs &b = w.rows;
+    Carve c(ws);
+    b.max_items = WIDE_MAX_ITEMS;
+    msm_layout_head(c, b, R, bw);
+    w.partial_plain = c.words(R * (size_t)MSM_FOLD1_THREADS * bw);
+    b.partial_items = c.words(R * (size_t)b.max_items * bw);
+    w.s1 = c.words(R * bw); w.s0 = c.words(R * bw);
+    w.window_sums = c.words((size_t)WIDE_W * bw);
+    w.row_start = c.take<unsigned long long>(R * 8, 8);                 // (every term so far a multiple of four words)
+    w.bin_start = c.take<unsigned long long>((size_t)WIDE_ALL_BINS * 8, 8);
+    w.row_count = c.words(R); w.bin_count = c.words(WIDE_ALL_BINS);
+    w.slice_hist = c.words((size_t)WIDE_W * WIDE_SLICES * WIDE_BINS);
+    w.coarse = (uint2 *)c.words((size_t)WIDE_W * n * 2);
+    w.entries = c.words((size_t)WIDE_W * n);
+    w.digits = (int32_t *)w.entries;
+    w.end = (uint32_t *)c.at();
+    b.entries = w.entries; b.ones_list = w.end; b.end = w.end;
+    w.bytes = Carve::up(c.off, 16);
+    return w;
+}
+// what frw_msm_info reports for a dense handle (a bare one: sixteen rows, the windows, and their sixteen sums)
+inline size_t msm_workspace_per_signature(uint32_t n, bool bare, bool wide, size_t bw)
+{
+    return wide ? msm_layout_wide(nullptr, n, bw).bytes : msm_layout(nullptr, bare ? MSM_W : 1, n, bare, bw).bytes;
+}
+
+// ---- the narrow pipeline: the sort's arrays (which know nothing of the points) and a table's own
+struct NmsmBufs {
+    uint32_t *slice_hist, *counts, *offsets, *item_first, *items, *item_count, *ones_count, *ones_list, *entries;      // the sort's
+    uint32_t *partial_items, *partial_ones, *folded_ones, *bucket_sums;                                              // a table's own
+    uint32_t target, max_items, ones_stride;
+    uint32_t n = 0;             // (bare) how many scalars the sort is over: a table's rows, or the rows its index names
+    // a bare handle's sort (rows = the thirty-two windows of one scalar vector): where every window's entries start, and its tables'
+    // window sums [table][32]
+    unsigned long long *entry_base = nullptr;
+    uint32_t *window_sums = nullptr;
+    uint32_t *end = nullptr;
+    size_t used = 0, bytes = 0;      // from the base to `end`; what frw_msm_info reports for one signature
+};
+// a window table's: slice histograms, counts, offsets, first item of every bucket (all x 128), the item list + counter, the ones' list +
+// counter, the entries (32 n x 4 B), the items' and the ones' partial sums
+inline NmsmBufs nmsm_layout(void *ws, size_t cnt, uint32_t n, size_t bw)
+{
+    NmsmBufs b;
+    Carve c(ws);
+    b.target = nmsm_target_items(n); b.max_items = nmsm_max_items(n); b.ones_stride = nmsm_ones_max(n) / 64;
+    b.slice_hist = c.words(cnt * (size_t)nmsm_slices(n) * NMSM_BUCKETS);
+    b.counts = c.words(cnt * NMSM_BUCKETS);
+    b.offsets = c.words(cnt * NMSM_BUCKETS);
+    b.item_first = c.words(cnt * NMSM_BUCKETS);
+    b.items = c.words(cnt * (size_t)b.max_items);
+    b.item_count = c.words(cnt * 4);                                    // [cnt], four words per signature
+    b.ones_count = c.words(cnt * 4);                                    // likewise
+    b.ones_list = c.words(cnt * (size_t)n);
+    b.entries = c.words(cnt * (size_t)NMSM_W * n);
+    c.align_to(16);                                                     // every term above is a multiple of 4 words per signature but n: at most three words
+    b.partial_items = c.words(cnt * (size_t)b.max_items * bw);
+    b.partial_ones = c.words(cnt * (size_t)b.ones_stride * bw);
+    b.folded_ones = c.words(b.ones_stride > 64 ? cnt * (size_t)64 * bw : 0);     // second stage, only when ones_stride > 64
+    b.bucket_sums = c.words(cnt * (size_t)NMSM_BUCKETS * bw);
+    b.end = (uint32_t *)c.at();
+    b.used = c.off;
+    b.bytes = Carve::up(c.off + 16, 16);        // four words more than the arrays: the pad above was budgeted apart from them, and the sum is what callers were told
+    return b;
+}
+// ... of a bare handle: ONE sort (thirty-two window rows) and the own arrays of `tables` tables.  The entries are budgeted for the worst
+// case, every digit of every scalar non-zero (32 n words); a witness fills a seventieth of that.
+// `sorted`: another layout whose sort this one reads (the G2 sum of a proof reads the G1 sums' sort): only the own arrays are laid out then.
+inline NmsmBufs nmsm_layout_bare(void *ws, size_t tables, uint32_t n, size_t bw, const NmsmBufs *sorted = nullptr)
+{
+    constexpr size_t WIN = NMSM_W;
+    NmsmBufs b;
+    Carve c(ws);
+    if (sorted) {
+        b = *sorted;
+    } else {
+        b.target = nmsm_target_items(n); b.max_items = nmsm_max_items(n); b.ones_stride = nmsm_ones_max(n) / 64; b.n = n;
+        b.entry_base = c.take<unsigned long long>(WIN * 8, 8);             // [32]
+        b.slice_hist = c.words(WIN * (size_t)nmsm_slices(n) * NMSM_BUCKETS);
+        b.counts = c.words(WIN * NMSM_BUCKETS);
+        b.offsets = c.words(WIN * NMSM_BUCKETS);
+        b.item_first = c.words(WIN * NMSM_BUCKETS);
+        b.items = c.words(WIN * (size_t)b.max_items);
+        b.item_count = c.words(WIN * 4);
+        b.ones_count = c.words(4);                                         // [0] is the one in use (every term so far a multiple of four words)
+    }
+    b.partial_items = c.words(tables * WIN * (size_t)b.max_items * bw);
+    b.partial_ones = c.words(tables * (size_t)b.ones_stride * bw);
+    b.folded_ones = c.words(tables * (size_t)64 * bw);
+    b.bucket_sums = c.words(tables * WIN * (size_t)NMSM_BUCKETS * bw);
+    b.window_sums = c.words(tables * WIN * bw);
+    if (!sorted) {
+        b.ones_list = c.words(n);
+        b.entries = c.words(WIN * (size_t)n);
+    }
+    b.end = (uint32_t *)c.at();
+    b.used = c.off;
+    b.bytes = Carve::up(c.off + 16, 16);        // (the window tables' four words more, here too: reported so since bare handles exist)
+    return b;
+}
+inline size_t nmsm_workspace_per_signature(uint32_t n, bool bare, size_t bw) { return bare ? nmsm_layout_bare(nullptr, 1, n, bw).bytes : nmsm_layout(nullptr, 1, n, bw).bytes; }
+
+// ---- the Groth16 prover.  The points of `cnt` proofs: [A | B1' | L] [H] [s A | r B1'] (G1, XYZZ: 240 bytes each), B (G2, affine), r and
+// s, and their split halves
+struct Groth16Points { uint32_t *A, *B1, *L, *H, *SA, *RB1; uint64_t *B2, *rs, *split; };
+constexpr size_t GROTH16_POINTS_BYTES = 6 * (size_t)G1_BK_WORDS * 4 + 192 + 64 + 64;      // (of one proof: tests/test_layout_host.py holds the layout to it)
+inline Groth16Points groth16_points_layout(Carve &c, size_t cnt)
+{
+    Groth16Points p;
+    p.A = c.words(cnt * G1_BK_WORDS); p.B1 = c.words(cnt * G1_BK_WORDS); p.L = c.words(cnt * G1_BK_WORDS);
+    p.H = c.words(cnt * G1_BK_WORDS); p.SA = c.words(cnt * G1_BK_WORDS); p.RB1 = c.words(cnt * G1_BK_WORDS);
+    p.B2 = c.take<uint64_t>(cnt * 192, 8); p.rs = c.take<uint64_t>(cnt * 64, 8); p.split = c.take<uint64_t>(cnt * 64, 8);
+    return p;
+}
+// One chunk of `cnt` proofs with a key of window tables: the witness map's workspace, h, z ++ [1, r, s], the five sums' workspaces
+// (h_query, a_query, b_g1_query, l_query, b_g2_query: each its own, they overlap in time), the points.
+// qap, msm[]: bytes per signature as frw_qap_info / frw_msm_info report them.
+// .qap, .msm[]: per proof (the sums' rounded up to 256); .bytes with cnt = 1: the workspace of one proof in flight
+struct Groth16Bufs { void *qap_ws; uint64_t *h, *zext; char *msm_ws[5]; Groth16Points pts; size_t qap, msm[5], bytes; };
+inline Groth16Bufs groth16_layout(void *ws, size_t cnt, size_t qap, size_t domain, size_t nv, const size_t *msm)
+{
+    Groth16Bufs g{};
+    Carve c(ws);
+    g.qap = qap;
+    g.qap_ws = c.take(cnt * qap, 1);
+    g.h = c.take<uint64_t>(cnt * domain * 32, 1);
+    g.zext = c.take<uint64_t>(cnt * (nv + 3) * 32, 1);
+    for (int i = 0; i < 5; i++) { g.msm[i] = Carve::up(msm[i], 256); g.msm_ws[i] = c.take<char>(cnt * g.msm[i], 1); }
+    g.pts = groth16_points_layout(c, cnt);
+    g.bytes = Carve::up(c.off, 256);
+    return g;
+}
+// The witness-side sums of a key of bare handles: g1, the sort of the slice's `nz` scalars and the own arrays of a_query and l_query; gb,
+// the sort of the scalars of the `b_rows` rows b_g1_query / b_g2_query hold a point in and b_g1_query's own arrays; g2, b_g2_query's own
+// arrays (it reads gb's sort).  Each is rounded up to 256 bytes.
+struct Groth16Sides { NmsmBufs g1, gb, g2; };
+inline Groth16Sides groth16_sides_layout(Carve &c, uint32_t nz, uint32_t b_rows)
+{
+    Groth16Sides s;
+    s.g1 = nmsm_layout_bare(c.at(), 2, nz, G1_BK_WORDS);              c.take(s.g1.used);
+    s.gb = nmsm_layout_bare(c.at(), 1, b_rows, G1_BK_WORDS);          c.take(s.gb.used);
+    s.g2 = nmsm_layout_bare(c.at(), 1, b_rows, G2_BK_WORDS, &s.gb);   c.take(s.g2.used);
+    return s;
+}
+// One proof with a key of bare handles.  The witness map's workspace and the sum over h_query's are ONE region: the sum starts, on the
+// same stream, when the map is through and has left h -- 30 GB of the 2^27 domain's workspace.
+// first_ws: the witness map's, then the sum over h_query's; .qap, .msm_h: their sizes, rounded up to 256
+struct Groth16BareBufs { void *first_ws; uint64_t *h, *zext; Groth16Sides sides; Groth16Points pts; size_t qap, msm_h, bytes; };
+inline Groth16BareBufs groth16_layout_bare(void *ws, size_t qap, size_t msm_h, size_t domain, size_t nv, uint32_t nz, uint32_t b_rows)
+{
+    Groth16BareBufs g{};
+    Carve c(ws);
+    g.qap = Carve::up(qap, 256); g.msm_h = Carve::up(msm_h, 256);
+    g.first_ws = c.take(g.qap > g.msm_h ? g.qap : g.msm_h, 1);
+    g.h = c.take<uint64_t>(domain * 32, 1);
+    g.zext = c.take<uint64_t>((nv + 3) * 32, 1);
+    g.sides = groth16_sides_layout(c, nz, b_rows);
+    g.pts = groth16_points_layout(c, 1);
+    g.bytes = Carve::up(c.off, 256);
+    return g;
+}
+
+// ---- the verification chains, `k` proofs in flight: (from the wire format: the decoded proofs, 384 bytes each, and the decoder's
+// statuses,) the sum's workspace -- one vector's for a bare handle --, the prepared points and the statuses, (on the device: the pairing's
+// per proof and per pass).  msm_per: what frw_msm_info reports for the key's handle, a multiple of 16.
+struct VerifyBufs { uint64_t *decoded, *prepared; int32_t *decode_status, *status; void *msm_ws, *pairing_ws; size_t msm_bytes, bytes; };
+inline VerifyBufs verify_layout(void *ws, size_t k, size_t msm_per, bool bare, size_t proof_bytes = 0, size_t pass_bytes = 0, bool wire = false)
+{
+    VerifyBufs v{};
+    Carve c(ws);
+    if (wire) { v.decoded = c.take<uint64_t>(384 * k, 8); v.decode_status = c.take<int32_t>(4 * k, 16); }
+    v.msm_bytes = msm_per * (bare ? 1 : k);
+    v.msm_ws = c.take(v.msm_bytes, 1);
+    v.prepared = c.take<uint64_t>(96 * k, 8);
+    v.status = c.take<int32_t>(4 * k, 16);
+    v.pairing_ws = c.take(k * proof_bytes + pass_bytes, 1);
+    v.bytes = c.off;
+    return v;
+}
+// the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
+template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
+{
+    if (batch == 0 || size(1) > bytes) return 0;
+    size_t lo = 1, hi = batch;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (size(mid) <= bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+}  // namespace frw

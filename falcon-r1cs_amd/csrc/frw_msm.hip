@@ -32,13 +32,11 @@
 #include "frw_fq29.h"
 #include "frw_quad.h"
 #include "frw_fr29.h"
+#include "frw_layout.h"
 
 namespace frw {
 
-constexpr int MSM_C = 16;                       // window bits
-constexpr int MSM_W = 16;                       // windows: 16 x 16 = 256 >= 255 bits
-constexpr int MSM_BUCKETS = 1 << (MSM_C - 1);   // signed digits: |d| in 1 .. 2^15
-constexpr int MSM_FOLD1_THREADS = 4096;         // partial sums per signature at most (first stage: 8, 32 or 64 buckets per thread)
+// (MSM_C = 16, MSM_W = 16, MSM_BUCKETS = 2^15 and every other constant the workspaces' layouts depend on -- MSM_*, WIDE_*, NMSM_*: frw_layout.h)
 constexpr int MSM_FOLD_THREADS = 512;           // second stage: one workgroup per signature
 // per group (F = FqField: G1, Fq2Field: G2): a table row = x, y limbs (all zero = the point at infinity); a bucket = X, Y, ZZ,
 // ZZZ limbs + the infinity flag (padded to 16 bytes); ark-ff's bytes of an affine point
@@ -259,7 +257,6 @@ __device__ __forceinline__ bool scalar_digits(const uint32_t *src, int montgomer
 // a call with ONE signature (an aggregate statement's sum over 2^22 points) would keep 32 of the 256 CUs busy with them, so it cuts
 // 224, and parks their histograms in the work items' partial sums instead (131,072 x 240 bytes and more: room for 240), which
 // nothing writes before the bucket kernel.
-constexpr int MSM_SLICES = 32, MSM_SLICES_LONE = 224;
 // A BARE handle (round 5) holds the points themselves and nothing else -- 112 bytes a point instead of 1,792: the key of a
 // 1,024-statement aggregate is 2^27 points of h_query alone, whose window tables would be 240 GB.  The sum is then sixteen bucket
 // accumulations, one per 16-bit window, over the SAME rows: grid row y of every kernel below is window y of ONE scalar vector
@@ -366,9 +363,6 @@ __global__ __launch_bounds__(1024) void msm_scatter_digits_kernel(uint32_t n, co
 // S0 = sum B_lo; a window is sum_hi S1_hi + 2^15 sum_hi hi S0_hi (msm_wide_window_kernel), the windows join by Horner's rule with 20
 // doublings each.  The folds of 13 x 2^19 buckets are a fixed 14 ms, three windows' additions 0.18 ns a point: handles of 2^26 points and
 // more take wide windows by themselves (MSM_WIDE_FROM_DEFAULT), smaller ones when loaded so.
-constexpr int WIDE_C = 20, WIDE_W = 13, WIDE_H = 1 << (WIDE_C - MSM_C), WIDE_ROWS = WIDE_W * WIDE_H;
-constexpr uint32_t WIDE_MAX_ITEMS = 65536;       // >= 32,768 + (32,768 / 1.5) 33 / 32 (finer = 1)
-constexpr int WIDE_SLICES = 128;                 // slices of a window in the bins' sort (whole tiles each)
 // signed 20-bit digits, d_j in [-2^19 + 1, 2^19], sum d_j 2^(20 j) = k; the top window (bits 240 ..) takes the last carry
 __device__ __forceinline__ void scalar_digits_wide(const uint32_t *src, int montgomery, int (&d)[WIDE_W])
 {
@@ -392,7 +386,6 @@ __device__ __forceinline__ void scalar_digits_wide(const uint32_t *src, int mont
 //   buckets    per bin (262,000 entries of 1,024 buckets: one workgroup, 4 KB of counters): the 4-byte entries of a bin go into a 1 MB region
 //              whose 1,024 open lines stay in the L2
 // A row's thirty-two bins lie one after the other, so rows and bins share one numbering: bin g = row (g >> 5), buckets [1,024 (g & 31), ..).
-constexpr int WIDE_BINS = 512, WIDE_BIN_BUCKETS = MSM_BUCKETS * WIDE_H / WIDE_BINS, WIDE_ALL_BINS = WIDE_W * WIDE_BINS, WIDE_TILE = 4096;
 static_assert(WIDE_BIN_BUCKETS == 1024 && WIDE_ALL_BINS == WIDE_ROWS * 32, "a row = 32 bins of 1,024 buckets");
 __global__ __launch_bounds__(256) void msm_wide_digits_kernel(uint32_t n, const uint32_t *__restrict__ scalars, int montgomery, int32_t *__restrict__ digits)
 {
@@ -516,7 +509,6 @@ __global__ __launch_bounds__(1024) void msm_wide_bin_scatter_kernel(uint32_t n, 
 // one workgroup each with its cursors in LDS (a part's own first positions come from the parts' histograms), and the parts of a bin run on
 // the SAME XCD at the same time (workgroups go to the XCDs round robin, w % 8): two bins in flight per XCD, their lines complete before
 // they leave its L2.  The order inside a bucket is what the LDS atomics make it within a part; parts in order.
-constexpr int WIDE_PARTS = 32;
 static_assert(WIDE_ALL_BINS % 8 == 0, "bins go to the XCDs eight at a time");
 struct WidePart { size_t g; uint32_t part, lo, hi; };
 __device__ __forceinline__ WidePart wide_part_of(uint32_t w, const uint32_t *__restrict__ bin_count)
@@ -676,7 +668,6 @@ __global__ __launch_bounds__(1024) void msm_scatter_kernel(uint32_t n, const uin
 // size (a counting sort), so the 64 lanes of a wavefront run equally long; a bucket's items are neighbours, and
 // msm_combine_kernel adds them up.  At most 32,768 + 21,845 items whatever the scalars (sum of ceil(c_b / split)).
 constexpr int MSM_SIZE_CLASSES = 1024;         // sizes >= this share the first class
-constexpr int MSM_MAX_ITEMS = 131072;          // >= 32,768 + 32,768 / (1.5 / 4): the finest split (a lone signature), a multiple of 64
 // Sums over more than 2^18 points (an aggregate statement's h_query: ONE signature, 2^22 points, buckets of 2,048 entries) are cut
 // finer still: `finer` = 24 makes a bucket of the mean size 16 items of 128 entries -- 524,288 items, four rounds of the chip's
 // 131,072 thread slots at two wavefronts per SIMD (with 4 it was 98,304 items: a quarter of the slots idle and half the SIMDs with a
@@ -685,13 +676,6 @@ constexpr int MSM_MAX_ITEMS = 131072;          // >= 32,768 + 32,768 / (1.5 / 4)
 // (msm_split_of rounds the split DOWN, by less than one entry in at least 32: 33 / 32 of that bound is what the list must hold; an item is
 // two words, bucket and part -- packed into one, `part << 15` overflowed for a bucket cut into more than 2^17 parts, which one digit repeated
 // in all the scalars of a 2^22-point sum produces: round 4's ADVICE)
-constexpr int MSM_MAX_ITEMS_LARGE = 32768 + (32768 * 24 * 2 / 3) / 32 * 33 + 64;     // 573,504
-static_assert(MSM_MAX_ITEMS_LARGE % 64 == 0 && MSM_MAX_ITEMS >= 32768 + (32768 * 4 * 2 / 3) / 32 * 33 + 64, "whole wavefronts; the finest split fits");
-// a bare handle's rows are windows of one sum: sixteen of them fill the chip with items of the buckets' own size (finer = 1)
-__host__ __device__ constexpr uint32_t msm_max_items(uint32_t n, bool bare = false)
-{
-    return !bare && n > (1u << 18) ? (uint32_t)MSM_MAX_ITEMS_LARGE : (uint32_t)MSM_MAX_ITEMS;
-}
 // `finer`: 1 for a batch, 4 for one or two signatures at a time -- a bucket of the mean size is then three items instead of one
 // (a lone proof waits for ~128 dependent additions otherwise), and msm_combine_kernel adds them up
 __device__ __forceinline__ uint32_t msm_split_of(uint32_t total, uint32_t finer)
@@ -970,12 +954,10 @@ __global__ __launch_bounds__(MSM_FOLD_THREADS) void msm_fold2_kernel(const uint3
 // empty buckets, ten kernels of one wavefront per SIMD each: a third of a whole proof's time for a thirtieth of its
 // arithmetic.  With 8-bit windows (32 of them: a table twice as long) the same scalars are 70,000 additions into 128 buckets
 // per signature, cut into ~2,048 equal work items, and the fold is one workgroup: a suffix scan and a tree over 128 points.
-constexpr int NMSM_C = 8, NMSM_W = 32, NMSM_BUCKETS = 128;
 // slices of the counting sort (a workgroup of 1,024 threads each): 16 per signature, 128 beyond 2^18 scalars (an aggregate statement is
 // one "signature": 16 workgroups for 2.5 M scalars were 1.2 ms at the head of every other kernel of its proof)
 // (1,024 slices for the 2^27-scalar sums were tried: the histogram no faster -- it waited for ONE global counter, see wave_append -- and the
 // scatter three times slower: a slice's run inside a bucket is a 1,024th of it, and the entry array's lines left the L2 half written)
-__host__ __device__ constexpr uint32_t nmsm_slices(uint32_t n) { return n > (1u << 18) ? 128u : 16u; }
 // list[(*count)++] = value for the lanes of a wavefront that ask for it: ONE atomic per wavefront (the scalars equal to one are 55 % of a
 // witness: 65 M increments of one address in the 1,024-statement proof, 20 ms of a histogram pass that computes for two)
 __device__ __forceinline__ void wave_append(bool want, uint32_t *__restrict__ count, uint32_t *__restrict__ list, uint32_t value)
@@ -992,17 +974,8 @@ __device__ __forceinline__ void wave_append(bool want, uint32_t *__restrict__ co
 // Work items per signature: 2,048 for the per-signature circuits (n < 2^18 points), n / 128 rounded up to a multiple of 2,048 beyond
 // (an aggregate statement is ONE "signature" with sixteen times the points: 2,048 items would be 32 wavefronts on 1,024 SIMDs, each
 // a chain of 550 additions); items <= buckets + total / split <= 128 + target, rounded up to whole wavefronts.
-constexpr int NMSM_TARGET_ITEMS_MIN = 2048, NMSM_TARGET_ITEMS_MAX = 65536;
-__host__ __device__ constexpr uint32_t nmsm_target_items(uint32_t n)
-{
-    const uint32_t t = (n / 128 + 2047) / 2048 * 2048;
-    return t < (uint32_t)NMSM_TARGET_ITEMS_MIN ? (uint32_t)NMSM_TARGET_ITEMS_MIN : t > (uint32_t)NMSM_TARGET_ITEMS_MAX ? (uint32_t)NMSM_TARGET_ITEMS_MAX : t;
-}
-__host__ __device__ constexpr uint32_t nmsm_max_items(uint32_t n) { return nmsm_target_items(n) + 256; }
 // the scalars equal to one: 256 .. 4,096 threads per signature, by the batch, one partial sum per 64 of them (<= 64: one per thread of
 // the fold); with more than 2^18 points up to 65,536 threads, whose <= 1,024 partial sums a small kernel brings down to 64 first
-constexpr int NMSM_ONES_MAX = 4096, NMSM_ONES_MAX_LARGE = 65536;
-__host__ __device__ constexpr uint32_t nmsm_ones_max(uint32_t n) { return n > (1u << 18) ? (uint32_t)NMSM_ONES_MAX_LARGE : (uint32_t)NMSM_ONES_MAX; }
 // threads of the one-workgroup fold: 128 for the buckets + 256 (G1) / 128 (G2: four waves = one per SIMD, the whole register file
 // for an addition that needs 300 live registers) for the ones' partial sums
 __device__ __forceinline__ bool scalar_digits8(const uint32_t *src, int montgomery, int (&d)[NMSM_W])
@@ -1570,43 +1543,8 @@ struct frw_msm {
 namespace {
 using frw::FqField;
 using frw::Fq2Field;
-// ---- the dense pipeline's workspace: per grid row (a signature; a bare handle: a window), every array but the last two a multiple of
-// four words per row, so that whatever the number of points everything before them is 16-byte aligned (the items are read two words at a time)
-template <class F> struct MsmBufs {
-    uint32_t *counts, *offsets, *order, *item_first, *item_count, *ones_count, *items, *buckets, *partial, *partial_items, *entries, *ones_list, *end;
-    int16_t *digits;            // a bare handle: int16[16][n], the windows' digits of the scalar vector being summed
-    uint32_t max_items;
-    size_t ent_stride, ones_stride;
-};
-template <class F> MsmBufs<F> msm_carve(void *ws, size_t rows, uint32_t n, bool bare)
-{
-    constexpr size_t BW = frw::Grp<F>::BK_WORDS;
-    static_assert((size_t)frw::MSM_SLICES * 4 <= BW * 4, "the slice histograms borrow the buckets' memory");
-    static_assert((size_t)frw::MSM_SLICES_LONE * frw::MSM_BUCKETS <= (size_t)frw::MSM_MAX_ITEMS * BW, "... or, for a lone signature, the work items'");
-    MsmBufs<F> b;
-    b.max_items = frw::msm_max_items(n, bare);
-    b.ent_stride = bare ? (size_t)n : (size_t)frw::MSM_W * n;
-    b.ones_stride = bare ? 0 : (size_t)n;                               // a bare handle's ones are digits like any other
-    b.counts = (uint32_t *)ws;
-    b.offsets = b.counts + rows * frw::MSM_BUCKETS;
-    b.order = b.offsets + rows * frw::MSM_BUCKETS;
-    b.item_first = b.order + rows * frw::MSM_BUCKETS;
-    b.item_count = b.item_first + rows * frw::MSM_BUCKETS;             // [rows], four words each
-    b.ones_count = b.item_count + rows * 4;                            // likewise
-    b.items = b.ones_count + rows * 4;                                 // [rows][max_items][2]
-    b.buckets = b.items + rows * (size_t)b.max_items * 2;              // the sort's per-slice histograms live here before the buckets are written
-    b.partial = b.buckets + rows * (size_t)frw::MSM_BUCKETS * BW;
-    b.partial_items = b.partial + rows * (size_t)frw::MSM_FOLD1_THREADS * BW;
-    b.entries = b.partial_items + rows * (size_t)b.max_items * BW;
-    b.ones_list = b.entries + rows * b.ent_stride;
-    b.end = b.ones_list + rows * b.ones_stride;
-    b.digits = nullptr;
-    if (bare) {
-        b.digits = (int16_t *)b.end;
-        b.end += ((size_t)frw::MSM_W * n * 2 + 3) / 4;
-    }
-    return b;
-}
+using frw::MsmBufs; using frw::MsmWideBufs; using frw::NmsmBufs;
+static_assert(frw::Grp<FqField>::BK_WORDS == frw::G1_BK_WORDS && frw::Grp<Fq2Field>::BK_WORDS == frw::G2_BK_WORDS, "frw_layout.h lays the workspaces out by these");
 // Wide windows (frw::WIDE_*): bare dense handles of 2^26 points and more, and those LOADED so (frw_msm_g1_load_bare(.., narrow = 2, ..): the
 // tests do, on the small adversarial vectors and on 2^18 points).  Measured on the 2^27-point sum of the 1,024-statement aggregate
 // (profiles/r05_wide_windows_ab.txt): the bucket kernel 350 -> 308 ms, the sort 65 -> 34 ms once every pass of it wrote runs (the first
@@ -1620,139 +1558,6 @@ static uint32_t msm_wide_from()
         return lg >= 10 && lg <= 31 ? ((uint32_t)1 << lg) - 1 : MSM_WIDE_FROM_DEFAULT;
     }();
     return v;
-}
-template <class F> struct MsmWideBufs {
-    MsmBufs<F> rows;                    // the 208 rows' arrays (entries apart: below)
-    uint32_t *partial_plain, *slice_hist, *bin_count, *row_count, *s1, *s0, *window_sums, *entries, *end;
-    unsigned long long *row_start, *bin_start;
-    uint2 *coarse;
-    int32_t *digits;
-};
-template <class F> MsmWideBufs<F> msm_carve_wide(void *ws, uint32_t n)
-{
-    constexpr size_t BW = frw::Grp<F>::BK_WORDS, R = frw::WIDE_ROWS;
-    MsmWideBufs<F> w;
-    MsmBufs<F> &b = w.rows;
-    b.max_items = frw::WIDE_MAX_ITEMS;
-    b.ent_stride = 0; b.ones_stride = 0; b.digits = nullptr;
-    b.counts = (uint32_t *)ws;
-    b.offsets = b.counts + R * frw::MSM_BUCKETS;
-    b.order = b.offsets + R * frw::MSM_BUCKETS;
-    b.item_first = b.order + R * frw::MSM_BUCKETS;
-    b.item_count = b.item_first + R * frw::MSM_BUCKETS;
-    b.ones_count = b.item_count + R * 4;
-    b.items = b.ones_count + R * 4;
-    b.buckets = b.items + R * (size_t)b.max_items * 2;
-    b.partial = b.buckets + R * (size_t)frw::MSM_BUCKETS * BW;
-    w.partial_plain = b.partial + R * (size_t)frw::MSM_FOLD1_THREADS * BW;
-    b.partial_items = w.partial_plain + R * (size_t)frw::MSM_FOLD1_THREADS * BW;
-    w.s1 = b.partial_items + R * (size_t)b.max_items * BW;
-    w.s0 = w.s1 + R * BW;
-    w.window_sums = w.s0 + R * BW;
-    w.row_start = (unsigned long long *)(w.window_sums + (size_t)frw::WIDE_W * BW);     // (every term so far a multiple of four words)
-    w.bin_start = w.row_start + R;
-    w.row_count = (uint32_t *)(w.bin_start + frw::WIDE_ALL_BINS);
-    w.bin_count = w.row_count + R;
-    w.slice_hist = w.bin_count + frw::WIDE_ALL_BINS;
-    w.coarse = (uint2 *)(w.slice_hist + (size_t)frw::WIDE_W * frw::WIDE_SLICES * frw::WIDE_BINS);
-    w.entries = (uint32_t *)(w.coarse + (size_t)frw::WIDE_W * n);
-    w.digits = (int32_t *)w.entries;                  // (the digits are dead once the bins are sorted; the entries are written after that)
-    w.end = w.entries + (size_t)frw::WIDE_W * n;
-    b.entries = w.entries; b.ones_list = w.end; b.end = w.end;
-    return w;
-}
-// a bare handle: sixteen rows (windows) and their sixteen sums
-template <class F> size_t msm_workspace_per_signature(uint32_t n, bool bare = false, bool wide = false)
-{
-    if (wide) {
-        char *const base0 = (char *)(uintptr_t)4096;
-        return ((size_t)((char *)msm_carve_wide<F>(base0, n).end - base0) + 15) & ~(size_t)15;
-    }
-    const size_t rows = bare ? frw::MSM_W : 1;
-    char *const base = (char *)(uintptr_t)4096;                       // (a carve of nothing: only the distance to its end is used)
-    const size_t bytes = (size_t)((char *)msm_carve<F>(base, rows, n, bare).end - base) + (bare ? (size_t)frw::MSM_W * frw::Grp<F>::BK_WORDS * 4 : 0);
-    return (bytes + 15) & ~(size_t)15;
-}
-
-// ---- the narrow pipeline's workspace -----------------------------------------------------------------------------------------------
-struct NmsmBufs {
-    uint32_t *slice_hist, *counts, *offsets, *item_first, *items, *item_count, *ones_count, *ones_list, *entries;      // the sort's
-    uint32_t *partial_items, *partial_ones, *folded_ones, *bucket_sums;                                              // a table's own
-    uint32_t target, max_items, ones_stride;
-    uint32_t n = 0;             // (bare) how many scalars the sort is over: a table's rows, or the rows its index names
-    // a bare handle's sort (rows = the thirty-two windows of one scalar vector): where every window's entries start, and its tables'
-    // window sums [table][32]
-    unsigned long long *entry_base = nullptr;
-    uint32_t *window_sums = nullptr;
-    uint32_t *end = nullptr;
-};
-template <class F> NmsmBufs nmsm_carve(void *d_workspace, size_t cnt, uint32_t n)
-{
-    constexpr int BW = frw::Grp<F>::BK_WORDS;
-    NmsmBufs b;
-    b.target = frw::nmsm_target_items(n); b.max_items = frw::nmsm_max_items(n); b.ones_stride = frw::nmsm_ones_max(n) / 64;
-    b.slice_hist = (uint32_t *)d_workspace;
-    b.counts = b.slice_hist + cnt * (size_t)frw::nmsm_slices(n) * frw::NMSM_BUCKETS;
-    b.offsets = b.counts + cnt * frw::NMSM_BUCKETS;
-    b.item_first = b.offsets + cnt * frw::NMSM_BUCKETS;
-    b.items = b.item_first + cnt * frw::NMSM_BUCKETS;
-    b.item_count = b.items + cnt * (size_t)b.max_items;                    // [cnt], padded to four words per signature in the budget
-    b.ones_count = b.item_count + cnt * 4;                                 // likewise
-    b.ones_list = b.ones_count + cnt * 4;
-    b.entries = b.ones_list + cnt * (size_t)n;
-    b.partial_items = b.entries + cnt * (size_t)frw::NMSM_W * n;           // 16-byte aligned: every term above is a multiple of 4 words per signature but n
-    b.partial_items += (4 - ((uintptr_t)b.partial_items >> 2 & 3)) & 3;    // ... at most three words, out of the four the budget adds to the list for it
-    b.partial_ones = b.partial_items + cnt * (size_t)b.max_items * BW;
-    b.folded_ones = b.partial_ones + cnt * (size_t)b.ones_stride * BW;     // second stage, only when ones_stride > 64
-    b.bucket_sums = b.folded_ones + (b.ones_stride > 64 ? cnt * (size_t)64 * BW : 0);
-    b.end = b.bucket_sums + cnt * (size_t)frw::NMSM_BUCKETS * BW;
-    return b;
-}
-// ... of a bare handle: ONE sort (thirty-two window rows) and the own arrays of `tables` tables.  The entries are budgeted for the worst
-// case, every digit of every scalar non-zero (32 n words); a witness fills a seventieth of that.
-// `sorted`: another carve whose sort this one reads (the G2 sum of a proof reads the G1 sums' sort): only the own arrays are carved then.
-template <class F> NmsmBufs nmsm_carve_bare(void *d_workspace, size_t tables, uint32_t n, const NmsmBufs *sorted = nullptr)
-{
-    constexpr int BW = frw::Grp<F>::BK_WORDS;
-    constexpr size_t WIN = frw::NMSM_W;
-    NmsmBufs b;
-    uint32_t *p = (uint32_t *)d_workspace;
-    if (sorted) {
-        b = *sorted;
-    } else {
-        b.target = frw::nmsm_target_items(n); b.max_items = frw::nmsm_max_items(n); b.ones_stride = frw::nmsm_ones_max(n) / 64;
-        b.n = n;
-        b.entry_base = (unsigned long long *)d_workspace;                  // [32]
-        b.slice_hist = (uint32_t *)(b.entry_base + WIN);
-        b.counts = b.slice_hist + WIN * (size_t)frw::nmsm_slices(n) * frw::NMSM_BUCKETS;
-        b.offsets = b.counts + WIN * frw::NMSM_BUCKETS;
-        b.item_first = b.offsets + WIN * frw::NMSM_BUCKETS;
-        b.items = b.item_first + WIN * frw::NMSM_BUCKETS;
-        b.item_count = b.items + WIN * (size_t)b.max_items;
-        b.ones_count = b.item_count + WIN * 4;                             // [0] is the one in use
-        p = b.ones_count + 4;                                              // (every term so far a multiple of four words: 16-byte aligned)
-    }
-    b.partial_items = p;
-    b.partial_ones = b.partial_items + tables * WIN * (size_t)b.max_items * BW;
-    b.folded_ones = b.partial_ones + tables * (size_t)b.ones_stride * BW;
-    b.bucket_sums = b.folded_ones + tables * (size_t)64 * BW;
-    b.window_sums = b.bucket_sums + tables * WIN * (size_t)frw::NMSM_BUCKETS * BW;
-    b.end = b.window_sums + tables * WIN * BW;
-    if (!sorted) {
-        b.ones_list = b.end;
-        b.entries = b.ones_list + (size_t)n;
-        b.end = b.entries + WIN * (size_t)n;
-    }
-    return b;
-}
-template <class F> size_t nmsm_workspace_per_signature(uint32_t n, bool bare = false)
-{
-    // slice histograms, counts, offsets, first item of every bucket (all x 128), the item list + counter, the ones' list + counter,
-    // the entries (32 n x 4 B), the items' and the ones' partial sums
-    // (four words more than the carve: the alignment pad after the list, budgeted here rather than borrowed)
-    char *const base = (char *)(uintptr_t)4096;
-    const NmsmBufs b = bare ? nmsm_carve_bare<F>(base, 1, n) : nmsm_carve<F>(base, 1, n);
-    return (((size_t)((char *)b.end - base) + 16) + 15) & ~(size_t)15;
 }
 
 template <class F> int msm_load(int device, int group, size_t num_points, const uint64_t *bases, int window_bits, bool bare, frw_msm **out, bool force_wide = false)
@@ -1843,7 +1648,7 @@ hipError_t msm_rows(const frw_msm *m, size_t rows, const uint32_t *sc, size_t st
 {
     const uint32_t n = m->dev.n;
     const bool bare = m->bare;
-    const MsmBufs<F> b = msm_carve<F>(d_workspace, rows, n, bare);
+    const MsmBufs b = frw::msm_layout(d_workspace, rows, n, bare, frw::Grp<F>::BK_WORDS);
     uint32_t *slice_hist = b.buckets;                                // [rows][32][32,768], dead before the first bucket is stored (rows == 1: see below)
     const int slices = rows == 1 ? frw::MSM_SLICES_LONE : frw::MSM_SLICES;
     if (rows == 1) slice_hist = b.partial_items;                     // [224][32,768], dead before the first work item's sum is stored
@@ -1892,8 +1697,8 @@ hipError_t msm_rows_wide(const frw_msm *m, const uint32_t *sc, int montgomery, u
 {
     constexpr unsigned R = frw::WIDE_ROWS;
     const uint32_t n = m->dev.n;
-    const MsmWideBufs<F> w = msm_carve_wide<F>(d_workspace, n);
-    const MsmBufs<F> &b = w.rows;
+    const MsmWideBufs w = frw::msm_layout_wide(d_workspace, n, frw::Grp<F>::BK_WORDS);
+    const MsmBufs &b = w.rows;
     hipError_t e = hipMemsetAsync(b.ones_count, 0, R * 16, st);
     if (e != hipSuccess) return e;
     const dim3 sgrid(frw::WIDE_SLICES, frw::WIDE_W);
@@ -1937,7 +1742,7 @@ int msm_run(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t sc
             void *d_workspace, size_t workspace_bytes, hipStream_t st, bool xyzz_out = false)
 {
     const uint32_t n = m->dev.n;
-    const size_t per = msm_workspace_per_signature<F>(n, m->bare, m->wide);
+    const size_t per = frw::msm_workspace_per_signature(n, m->bare, m->wide, frw::Grp<F>::BK_WORDS);
     size_t chunk = workspace_bytes / per;
     if (chunk == 0 || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
     if (chunk > 32768) chunk = 32768;                                  // grid.y
@@ -1951,7 +1756,7 @@ int msm_run(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t sc
     }
     if (m->bare) {
         // one scalar vector at a time: its sixteen windows fill the grid; the window sums wait at the end of the workspace for Horner's rule
-        uint32_t *window_sums = (uint32_t *)((char *)d_workspace + per) - (size_t)frw::MSM_W * BW;
+        uint32_t *window_sums = frw::msm_layout(d_workspace, frw::MSM_W, n, true, BW).window_sums;
         for (size_t sig = 0; e == hipSuccess && sig < batch; sig++) {
             e = msm_rows<F, PREFETCH>(m, frw::MSM_W, (const uint32_t *)(d_scalars + sig * scalar_stride * 4), 0, montgomery, window_sums, true, d_workspace, st);
             if (e != hipSuccess) break;
@@ -1988,7 +1793,7 @@ hipError_t nmsm_sort(const NmsmBufs &b, uint32_t n, size_t cnt, const uint32_t *
     hipLaunchKernelGGL(frw::nmsm_scatter_kernel, sgrid, dim3(1024), 0, st, n, sc, stride_words, montgomery, b.offsets, b.slice_hist, b.entries);
     return hipGetLastError();
 }
-// ... of ONE scalar vector for bare handles: all thirty-two windows in one pass (`b` from nmsm_carve_bare)
+// ... of ONE scalar vector for bare handles: all thirty-two windows in one pass (`b` from frw::nmsm_layout_bare)
 // `index`: the sum is over the scalars (and rows) index[0 .. n) of `sc` (null: over 0 .. n)
 hipError_t nmsm_sort_bare(const NmsmBufs &b, uint32_t n, const uint32_t *sc, int montgomery, hipStream_t st, const uint32_t *index = nullptr)
 {
@@ -2068,7 +1873,7 @@ hipError_t nmsm_accumulate(const frw_msm *const *ms, int tables, const NmsmBufs 
                        d_out, xyzz_out ? 1 : 0, (uint32_t)cnt, 0);
     return hipGetLastError();
 }
-// The sums of ONE scalar vector over `tables` bare handles that share its sort (`b` from nmsm_carve_bare<F>(.., tables, n): the sort's
+// The sums of ONE scalar vector over `tables` bare handles that share its sort (`b` from frw::nmsm_layout_bare(.., tables, n, ..): the sort's
 // arrays and the tables' own): grid row = (table, window); a window's buckets are cut into work items, combined by a workgroup per bucket
 // (the low windows hold every small value of a witness: a bucket of 250,000 entries is a thousand items), folded by one wavefront per
 // (table, window); the scalars equal to one -- a list -- are summed by up to 65,536 threads per table and join window 0; Horner's rule
@@ -2118,13 +1923,13 @@ int nmsm_run(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t s
              void *d_workspace, size_t workspace_bytes, hipStream_t st)
 {
     const uint32_t n = m->dev.n;
-    const size_t per = nmsm_workspace_per_signature<F>(n, m->bare);
+    const size_t per = frw::nmsm_workspace_per_signature(n, m->bare, frw::Grp<F>::BK_WORDS);
     size_t chunk = workspace_bytes / per;
     if (chunk == 0 || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
     if (chunk > 32768) chunk = 32768;                                  // grid.y
     hipError_t e = hipSetDevice(m->device);
     if (m->bare) {
-        const NmsmBufs b = nmsm_carve_bare<F>(d_workspace, 1, n);
+        const NmsmBufs b = frw::nmsm_layout_bare(d_workspace, 1, n, frw::Grp<F>::BK_WORDS);
         for (size_t sig = 0; e == hipSuccess && sig < batch; sig++) {
             e = nmsm_sort_bare(b, n, (const uint32_t *)(d_scalars + sig * scalar_stride * 4), montgomery, st);
             if (e == hipSuccess) e = nmsm_accumulate_bare<F, PREFETCH>(&m, 1, b, (uint32_t *)(d_out + sig * (frw::Grp<F>::ARK_WORDS / 2)), st, false);
@@ -2133,7 +1938,7 @@ int nmsm_run(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t s
     }
     for (size_t lo = 0; e == hipSuccess && lo < batch; lo += chunk) {
         const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
-        const NmsmBufs b = nmsm_carve<F>(d_workspace, cnt, n);
+        const NmsmBufs b = frw::nmsm_layout(d_workspace, cnt, n, frw::Grp<F>::BK_WORDS);
         e = nmsm_sort(b, n, cnt, (const uint32_t *)(d_scalars + lo * scalar_stride * 4), scalar_stride * 8, montgomery, m->ones_table != nullptr, st);
         if (e == hipSuccess)
             e = nmsm_accumulate<F, PREFETCH>(&m, 1, b, b, cnt, (uint32_t *)(d_out + lo * (frw::Grp<F>::ARK_WORDS / 2)), m->ones_table != nullptr, st);
@@ -2198,8 +2003,8 @@ extern "C" int frw_msm_info(const frw_msm *m, frw_msm_info_t *out)
     if (m->ones_table) out->table_bytes += (uint64_t)((m->dev.n + 7) / 8) * 255 * (g2 ? frw::Grp<Fq2Field>::PT_WORDS : frw::Grp<FqField>::PT_WORDS) * 4;
     const uint32_t n = m->dev.n;
     const bool bare = m->bare;
-    out->workspace_bytes_per_signature = narrow ? (g2 ? nmsm_workspace_per_signature<Fq2Field>(n, bare) : nmsm_workspace_per_signature<FqField>(n, bare))
-                                                : (g2 ? msm_workspace_per_signature<Fq2Field>(n, bare, m->wide) : msm_workspace_per_signature<FqField>(n, bare, m->wide));
+    const size_t bw = g2 ? frw::G2_BK_WORDS : frw::G1_BK_WORDS;
+    out->workspace_bytes_per_signature = narrow ? frw::nmsm_workspace_per_signature(n, bare, bw) : frw::msm_workspace_per_signature(n, bare, m->wide, bw);
     return FRW_OK;
 }
 
@@ -2829,48 +2634,20 @@ extern "C" int frw_groth16_pk_info(const frw_groth16_pk *pk, frw_groth16_pk_info
 }
 
 namespace {
-struct Groth16Sizes { size_t qap, h, zext, msm[5], msm_all, pts, per; };
-Groth16Sizes groth16_sizes(const frw_groth16_pk *pk, const frw_r1cs *r)
+// what the prover's layouts (frw_layout.h) are made of: the bytes per signature of the witness map and of the sums over h_query, a_query,
+// b_g1_query, l_query and b_g2_query, as their handles report them (ok = false: not a usable R1CS handle)
+struct Groth16Parts { bool ok; size_t qap, domain, nv, msm[5]; uint32_t nz, b_rows; };
+Groth16Parts groth16_parts(const frw_groth16_pk *pk, const frw_r1cs *r)
 {
-    Groth16Sizes s{};
+    Groth16Parts s{};
     frw_qap_info_t q;
     frw_msm_info_t mi;
     if (frw_qap_info(r, &q) != FRW_OK) return s;
-    const size_t nv = (size_t)(pk->num_instance + pk->num_witness);
-    s.qap = q.workspace_bytes_per_signature;
-    s.h = (size_t)pk->domain_size * 32;
-    s.zext = (nv + 3) * 32;
-    if (pk->bare) {
-        // msm[0]: the sum over h_query (its window rows); msm[1]: the sort of the slice's scalars and the own arrays of a_query and
-        // l_query; msm[2]: the sort of the scalars of the rows b_g1_query / b_g2_query hold a point in (pk->b_index) and b_g1_query's own
-        // arrays; msm[4]: b_g2_query's own arrays (it reads msm[2]'s sort)
-        const uint32_t nz = pk->a->dev.n;
-        char *const base = (char *)(uintptr_t)4096;
-        frw_msm_info(pk->h, &mi);
-        s.msm[0] = (mi.workspace_bytes_per_signature + 255) & ~(size_t)255;
-        const NmsmBufs g1 = nmsm_carve_bare<FqField>(base, 2, nz);
-        s.msm[1] = ((size_t)((char *)g1.end - base) + 255) & ~(size_t)255;
-        const NmsmBufs gb = nmsm_carve_bare<FqField>(base, 1, pk->b_rows);
-        s.msm[2] = ((size_t)((char *)gb.end - base) + 255) & ~(size_t)255;
-        const NmsmBufs g2 = nmsm_carve_bare<Fq2Field>(base, 1, pk->b_rows, &gb);
-        s.msm[4] = ((size_t)((char *)g2.end - base) + 255) & ~(size_t)255;
-        // (the witness map's workspace and the sum over h_query's are ONE region: the sum starts, on the same stream, when the map is
-        // through and has left h -- 30 GB of the 2^27 domain's workspace)
-        s.qap = (s.qap + 255) & ~(size_t)255;
-        s.msm_all = std::max(s.msm[0], s.qap) - s.qap + s.msm[1] + s.msm[2] + s.msm[4];
-        s.pts = 6 * (size_t)frw::Grp<FqField>::BK_WORDS * 4 + 192 + 64 + 64;
-        s.per = ((s.qap + s.h + s.zext + s.msm_all + s.pts) + 255) & ~(size_t)255;
-        return s;
-    }
+    s.ok = true; s.qap = q.workspace_bytes_per_signature;
+    s.domain = (size_t)pk->domain_size; s.nv = (size_t)(pk->num_instance + pk->num_witness);
+    if (pk->bare) { s.nz = pk->a->dev.n; s.b_rows = pk->b_rows; }         // (the rows of this slice of the key, those b_g2_query holds a point in)
     int i = 0;
-    for (const frw_msm *m : {pk->h, pk->a, pk->b1, pk->l, pk->b2}) {                // each sum has a workspace of its own: they overlap in time
-        frw_msm_info(m, &mi);
-        s.msm[i] = (mi.workspace_bytes_per_signature + 255) & ~(size_t)255;
-        s.msm_all += s.msm[i++];
-    }
-    // A, B1', L, H, s A, r B1' (G1, XYZZ: 240 bytes each), B (G2, affine), r and s, and their split halves
-    s.pts = 6 * (size_t)frw::Grp<FqField>::BK_WORDS * 4 + 192 + 64 + 64;
-    s.per = ((s.qap + s.h + s.zext + s.msm_all + s.pts) + 255) & ~(size_t)255;
+    for (const frw_msm *m : {pk->h, pk->a, pk->b1, pk->l, pk->b2}) { frw_msm_info(m, &mi); s.msm[i++] = mi.workspace_bytes_per_signature; }
     return s;
 }
 }  // namespace
@@ -2878,7 +2655,10 @@ Groth16Sizes groth16_sizes(const frw_groth16_pk *pk, const frw_r1cs *r)
 extern "C" size_t frw_groth16_workspace_bytes(const frw_groth16_pk *pk, const frw_r1cs *r, size_t batch_in_flight)
 {
     if (!pk || !r) return 0;
-    return groth16_sizes(pk, r).per * (pk->bare ? (batch_in_flight ? 1 : 0) : batch_in_flight);     // a bare key proves one statement at a time
+    const Groth16Parts s = groth16_parts(pk, r);
+    if (!s.ok) return 0;
+    if (pk->bare) return batch_in_flight ? frw::groth16_layout_bare(nullptr, s.qap, s.msm[0], s.domain, s.nv, s.nz, s.b_rows).bytes : 0;      // one statement at a time
+    return frw::groth16_layout(nullptr, 1, s.qap, s.domain, s.nv, s.msm).bytes * batch_in_flight;
 }
 
 // (diagnostic: what the witness-side sums of a key of bare handles add up for the scalars z -- the benchmark prices its roofline with these)
@@ -2887,9 +2667,9 @@ extern "C" int frw_diag_groth16_side_counts(const frw_groth16_pk *pk, const uint
 {
     if (!pk || !pk->bare || !d_z || !d_workspace || !out || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
     const uint32_t nz = pk->a->dev.n;
-    const NmsmBufs g1 = nmsm_carve_bare<FqField>(d_workspace, 2, nz);
-    const size_t first = ((size_t)((char *)g1.end - (char *)d_workspace) + 255) & ~(size_t)255;
-    const NmsmBufs gb = nmsm_carve_bare<FqField>((char *)d_workspace + first, 1, pk->b_rows);
+    frw::Carve c(d_workspace);
+    const frw::Groth16Sides sides = frw::groth16_sides_layout(c, nz, pk->b_rows);
+    const NmsmBufs &g1 = sides.g1, &gb = sides.gb;
     if ((size_t)((char *)gb.end - (char *)d_workspace) > workspace_bytes) return FRW_E_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(pk->device);
@@ -2920,8 +2700,12 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
                        const uint64_t *rs_host, const uint64_t *rs_dev, uint64_t *d_proofs, uint64_t *d_partial, uint32_t *d_num_unsatisfied,
                        void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    const Groth16Sizes sz = groth16_sizes(pk, r1cs);
-    if (workspace_bytes < sz.per || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
+    const Groth16Parts parts = groth16_parts(pk, r1cs);
+    const frw::Groth16BareBufs g = frw::groth16_layout_bare(d_workspace, parts.qap, parts.msm[0], parts.domain, parts.nv, parts.nz, parts.b_rows);     // (every statement's)
+    if (workspace_bytes < g.bytes || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
+    uint64_t *const h = g.h, *const zext = g.zext, *const pB2 = g.pts.B2, *const d_rs = g.pts.rs, *const d_split = g.pts.split;
+    uint32_t *const pA = g.pts.A, *const pH = g.pts.H, *const pSA = g.pts.SA, *const pRB1 = g.pts.RB1;      // [A | B1' | L] [H] [s A | r B1']
+    const NmsmBufs &g1 = g.sides.g1, &gb = g.sides.gb, &g2 = g.sides.g2;
     const size_t I = (size_t)pk->num_instance, W = (size_t)pk->num_witness, nv = I + W, n = (size_t)pk->domain_size, stride = nv + 3;
     const uint32_t nz = pk->a->dev.n;                                    // rows of this slice of the witness-side tables
     hipStream_t st = (hipStream_t)stream;
@@ -2931,17 +2715,6 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
     std::unique_lock<std::mutex> lock(const_cast<frw_groth16_pk *>(pk)->enqueue, std::defer_lock);
     for (size_t b = 0; e == hipSuccess && rc == FRW_OK && b < batch; b++) {
         if (lock.owns_lock()) lock.unlock();
-        char *base = (char *)d_workspace;
-        void *qap_ws = base;
-        char *h_ws = base;                            base += std::max(sz.qap, sz.msm[0]);        // one region, one stream: groth16_sizes
-        uint64_t *h = (uint64_t *)base;               base += sz.h;
-        uint64_t *zext = (uint64_t *)base;            base += sz.zext;
-        char *g1_ws = base;                           base += sz.msm[1];
-        char *gb_ws = base;                           base += sz.msm[2];
-        char *g2_ws = base;                           base += sz.msm[4];
-        constexpr size_t XW = frw::Grp<FqField>::BK_WORDS;
-        uint32_t *pA = (uint32_t *)base, *pH = pA + 3 * XW, *pSA = pH + XW, *pRB1 = pSA + XW;      // [A | B1' | L] [H] [s A | r B1']
-        uint64_t *pB2 = (uint64_t *)(pRB1 + XW), *d_rs = pB2 + 24, *d_split = d_rs + 8;
         const uint64_t *wit = d_witness + b * W * 4, *inst = d_instance + b * I * 4;
         const uint64_t *rs_now = rs_dev ? rs_dev + b * 8 : d_rs;
         if (rs_host) {
@@ -2961,9 +2734,6 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
         if (e != hipSuccess) break;
         // the sorts first, on the caller's stream (workgroups of 1,024 threads: they would not start under the bucket kernels): one over
         // all the slice's scalars for a_query and l_query, one over the rows that b_g1_query / b_g2_query hold a point in
-        const NmsmBufs g1 = nmsm_carve_bare<FqField>(g1_ws, 2, nz);
-        const NmsmBufs gb = nmsm_carve_bare<FqField>(gb_ws, 1, pk->b_rows);
-        const NmsmBufs g2 = nmsm_carve_bare<Fq2Field>(g2_ws, 1, pk->b_rows, &gb);
         // (both before any sum starts: a sort's workgroups are 1,024 threads of 70 - 128 registers -- a whole CU's register file -- and
         // with the G2 sum's kernels already on the chip the long sort's scatter took 39 ms instead of 7: profiles/r05_witness_sorts.txt)
         e = nmsm_sort_bare(g1, nz, (const uint32_t *)(zext + pk->z_lo * 4), 1, st);
@@ -2980,12 +2750,12 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
         if (e != hipSuccess) break;
         e = nmsm_accumulate_bare<Fq2Field, false>(&pk->b2, 1, g2, (uint32_t *)pB2, pk->side[2], false);
         if (e != hipSuccess) break;
-        e = nmsm_accumulate_bare<FqField, true>(&pk->b1, 1, gb, pA + XW, pk->side[1], true);
+        e = nmsm_accumulate_bare<FqField, true>(&pk->b1, 1, gb, g.pts.B1, pk->side[1], true);
         if (e != hipSuccess) break;
-        rc = frw_qap_witness_map_dev(r1cs, 1, wit, inst, h, d_num_unsatisfied ? d_num_unsatisfied + b : nullptr, qap_ws, sz.qap, pk->main);
+        rc = frw_qap_witness_map_dev(r1cs, 1, wit, inst, h, d_num_unsatisfied ? d_num_unsatisfied + b : nullptr, g.first_ws, g.qap, pk->main);
         if (rc != FRW_OK) break;
         // h's coefficients [h_lo, h_hi) against this slice of h_query
-        rc = msm_run<FqField, true>(pk->h, 1, h + pk->h_lo * 4, n, 1, (uint64_t *)pH, h_ws, sz.msm[0], pk->main, true);
+        rc = msm_run<FqField, true>(pk->h, 1, h + pk->h_lo * 4, n, 1, (uint64_t *)pH, g.first_ws, g.msm_h, pk->main, true);      // (one region, one stream: frw::groth16_layout_bare)
         if (rc != FRW_OK) break;
         for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventRecord(pk->join[i], pk->side[i]);
         if (e == hipSuccess) e = hipEventRecord(pk->join[3], pk->main);
@@ -2997,7 +2767,7 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
         } else {
             hipLaunchKernelGGL(frw::groth16_scale_quad_kernel, dim3(2), dim3(4), 0, st, (size_t)1, (const uint32_t *)d_split, (const uint32_t *)pA, pSA);
             hipLaunchKernelGGL(frw::groth16_finish_kernel, dim3(1), dim3(64), 0, st, (size_t)1, (const uint32_t *)pA, (const uint32_t *)pSA,
-                               (const uint32_t *)pRB1, (const uint32_t *)(pA + 2 * XW), (const uint32_t *)pH, (const uint32_t *)pB2,
+                               (const uint32_t *)pRB1, (const uint32_t *)g.pts.L, (const uint32_t *)pH, (const uint32_t *)pB2,
                                (uint32_t *)(d_proofs + b * 48));
         }
         e = hipGetLastError();
@@ -3023,8 +2793,8 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
         if (pk->world > 1) return FRW_E_INVALID_ARG;                        // a slice makes partial sums: frw_groth16_prove_partial_dev
         return groth16_prove_bare(pk, r1cs, batch, d_witness, d_instance, rs_host, rs_dev, d_proofs, nullptr, d_num_unsatisfied, d_workspace, workspace_bytes, stream);
     }
-    const Groth16Sizes sz = groth16_sizes(pk, r1cs);
-    const size_t chunk = std::min<size_t>(workspace_bytes / sz.per, 4096);
+    const Groth16Parts parts = groth16_parts(pk, r1cs);
+    const size_t chunk = std::min<size_t>(workspace_bytes / frw::groth16_layout(nullptr, 1, parts.qap, parts.domain, parts.nv, parts.msm).bytes, 4096);
     if (chunk == 0 || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
     const size_t I = (size_t)pk->num_instance, W = (size_t)pk->num_witness, nv = I + W, n = (size_t)pk->domain_size, stride = nv + 3;
     hipStream_t st = (hipStream_t)stream;
@@ -3037,16 +2807,10 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
     for (size_t lo = 0; e == hipSuccess && rc == FRW_OK && lo < batch; lo += chunk) {
         if (lock.owns_lock()) lock.unlock();
         const size_t cnt = std::min(chunk, batch - lo);
-        char *base = (char *)d_workspace;
-        void *qap_ws = base;                          base += cnt * sz.qap;
-        uint64_t *h = (uint64_t *)base;               base += cnt * sz.h;
-        uint64_t *zext = (uint64_t *)base;            base += cnt * sz.zext;
-        char *msm_ws[5];
-        for (int i = 0; i < 5; i++) { msm_ws[i] = base; base += cnt * sz.msm[i]; }
-        constexpr size_t XW = frw::Grp<FqField>::BK_WORDS;               // the G1 points stay in XYZZ coordinates until the proof is put together
-        uint32_t *pA = (uint32_t *)base, *pB1 = pA + cnt * XW, *pL = pB1 + cnt * XW, *pH = pL + cnt * XW, *pSA = pH + cnt * XW, *pRB1 = pSA + cnt * XW;
-        (void)pB1;                                                       // [A | B1' | L] is what the three G1 sums write, [s A | r B1'] the scalar multiplications
-        uint64_t *pB2 = (uint64_t *)(pRB1 + cnt * XW), *d_rs = pB2 + cnt * 24, *d_split = d_rs + cnt * 8;
+        const frw::Groth16Bufs g = frw::groth16_layout(d_workspace, cnt, parts.qap, parts.domain, parts.nv, parts.msm);
+        uint64_t *const h = g.h, *const zext = g.zext, *const pB2 = g.pts.B2, *const d_rs = g.pts.rs, *const d_split = g.pts.split;
+        // the G1 points stay in XYZZ coordinates until the proof is put together: [A | B1' | L] is what the three G1 sums write, [s A | r B1'] the scalar multiplications
+        uint32_t *const pA = g.pts.A, *const pL = g.pts.L, *const pH = g.pts.H, *const pSA = g.pts.SA, *const pRB1 = g.pts.RB1;
         const uint64_t *wit = d_witness + lo * W * 4, *inst = d_instance + lo * I * 4;
         // the blinding factors: a host array (the prover draws them) is uploaded before anything reads them -- and waited for, the
         // array may be pageable and short-lived; factors that are in device memory already cost no wait (and the call is capturable)
@@ -3088,7 +2852,7 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
         if (e != hipSuccess) break;
         // the sort first: its kernels are workgroups of 1,024 threads, which do not start under the sum over h_query's bucket kernel
         // (0.8 ms late in a trace where the host was slow to get to them)
-        const NmsmBufs sorted = nmsm_carve<Fq2Field>(msm_ws[4], cnt, (uint32_t)stride);
+        const NmsmBufs sorted = frw::nmsm_layout(g.msm_ws[4], cnt, (uint32_t)stride, frw::G2_BK_WORDS);
         const bool ones_as_mask = pk->a->ones_table && pk->b1->ones_table && pk->l->ones_table && pk->b2->ones_table;
         e = nmsm_sort(sorted, (uint32_t)stride, cnt, (const uint32_t *)zext, stride * 8, 1, ones_as_mask, st);
         if (e != hipSuccess) break;
@@ -3096,10 +2860,10 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
         for (int i = 0; i < 3 && e == hipSuccess; i++)
             if (i != 1 || lone) e = hipStreamWaitEvent(pk->side[i], pk->sorted, 0);
         if (e != hipSuccess) break;
-        rc = frw_qap_witness_map_dev(r1cs, cnt, wit, inst, h, d_num_unsatisfied ? d_num_unsatisfied + lo : nullptr, qap_ws, cnt * sz.qap, pk->main);
+        rc = frw_qap_witness_map_dev(r1cs, cnt, wit, inst, h, d_num_unsatisfied ? d_num_unsatisfied + lo : nullptr, g.qap_ws, cnt * g.qap, pk->main);
         if (rc != FRW_OK) break;
         const frw_msm *g1s[3] = {pk->a, pk->b1, pk->l};
-        e = nmsm_accumulate<FqField, true>(g1s, 3, sorted, nmsm_carve<FqField>(msm_ws[1], 3 * cnt, (uint32_t)stride), cnt, pA, ones_as_mask, pk->side[0], true,
+        e = nmsm_accumulate<FqField, true>(g1s, 3, sorted, frw::nmsm_layout(g.msm_ws[1], 3 * cnt, (uint32_t)stride, frw::G1_BK_WORDS), cnt, pA, ones_as_mask, pk->side[0], true,
                                            lone, pk->side[1], pk->ones_done);
         if (e != hipSuccess) break;
         hipLaunchKernelGGL(frw::groth16_scale_quad_kernel, dim3((unsigned)(2 * cnt)), dim3(4), 0, pk->side[0], cnt, (const uint32_t *)d_split,
@@ -3107,7 +2871,7 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
         e = nmsm_accumulate<Fq2Field, false>(&pk->b2, 1, sorted, sorted, cnt, (uint32_t *)pB2, ones_as_mask, pk->side[2]);
         if (e != hipSuccess) break;
         // (h_query has n - 1 points and the dense pipeline: frw_groth16_pk_load; the scalars are h's coefficients 0 .. n - 2)
-        rc = msm_run<FqField, true>(pk->h, cnt, h, n, 1, (uint64_t *)pH, msm_ws[0], cnt * sz.msm[0], pk->main, true);
+        rc = msm_run<FqField, true>(pk->h, cnt, h, n, 1, (uint64_t *)pH, g.msm_ws[0], cnt * g.msm[0], pk->main, true);
         if (rc != FRW_OK) break;
         // (side[1] is neither recorded nor waited for: what it carries, if anything, side[0] has waited for -- and inside a stream
         // capture an event of a stream that is not part of the capture could not be waited for)
@@ -3162,15 +2926,16 @@ extern "C" int frw_groth16_prove_partial_dev(const frw_groth16_pk *pk, const frw
 extern "C" int frw_groth16_prove_combine_dev(const frw_groth16_pk *pk, size_t world, const uint64_t *d_partials, const uint64_t *rs, uint64_t *d_proof,
                                              void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    constexpr size_t XW = frw::Grp<FqField>::BK_WORDS;
     if (!pk || world == 0 || world > 65536 || !d_partials || !rs || !d_proof || !d_workspace || workspace_bytes < FRW_GROTH16_COMBINE_WORKSPACE ||
         ((uintptr_t)d_workspace & 255))
         return FRW_E_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(pk->device);
-    uint32_t *pA = (uint32_t *)d_workspace, *pH = pA + 3 * XW, *pSA = pH + XW, *pRB1 = pSA + XW;
-    uint64_t *pB2 = (uint64_t *)(pRB1 + XW), *d_rs = pB2 + 24, *d_split = d_rs + 8;
-    static_assert(6 * XW * 4 + 192 + 64 + 64 <= FRW_GROTH16_COMBINE_WORKSPACE, "the combine step's points fit its workspace");
+    frw::Carve c(d_workspace);
+    const frw::Groth16Points p = frw::groth16_points_layout(c, 1);
+    uint32_t *const pA = p.A, *const pH = p.H, *const pSA = p.SA, *const pRB1 = p.RB1;
+    uint64_t *const pB2 = p.B2, *const d_rs = p.rs, *const d_split = p.split;
+    static_assert(frw::GROTH16_POINTS_BYTES <= FRW_GROTH16_COMBINE_WORKSPACE, "the combine step's points fit its workspace");
     if (e == hipSuccess) e = hipMemcpyAsync(d_rs, rs, 64, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                     // (the array may be short-lived)
     if (e != hipSuccess) return frw::record_hip_error(e, "frw_groth16_prove_combine_dev");
@@ -3178,7 +2943,7 @@ extern "C" int frw_groth16_prove_combine_dev(const frw_groth16_pk *pk, size_t wo
     hipLaunchKernelGGL(frw::groth16_combine_kernel, dim3(1), dim3(64), 0, st, (uint32_t)world, (const uint32_t *)d_partials, pA, (uint32_t *)pB2);
     hipLaunchKernelGGL(frw::groth16_scale_quad_kernel, dim3(2), dim3(4), 0, st, (size_t)1, (const uint32_t *)d_split, (const uint32_t *)pA, pSA);
     hipLaunchKernelGGL(frw::groth16_finish_kernel, dim3(1), dim3(64), 0, st, (size_t)1, (const uint32_t *)pA, (const uint32_t *)pSA, (const uint32_t *)pRB1,
-                       (const uint32_t *)(pA + 2 * XW), (const uint32_t *)pH, (const uint32_t *)pB2, (uint32_t *)d_proof);
+                       (const uint32_t *)p.L, (const uint32_t *)pH, (const uint32_t *)pB2, (uint32_t *)d_proof);
     e = hipGetLastError();
     return e == hipSuccess ? FRW_OK : frw::record_hip_error(e, "frw_groth16_prove_combine_dev");
 }

@@ -20,6 +20,7 @@
 
 #include "../../include/frw.h"
 #include "frw_device.h"
+#include "frw_layout.h"
 #include "frw_pairing_dev.h"
 #include "frw_verify.h"
 #include "frw_wire.h"
@@ -72,24 +73,11 @@ size_t msm_workspace(const frw_groth16_vk *vk)
     return frw_msm_info(vk->msm, &info) == FRW_OK ? (size_t)info.workspace_bytes_per_signature : 0;
 }
 bool msm_bare(const frw_groth16_vk *vk) { return vk->num_instance > VK_TABLE_MAX_POINTS; }
-// the workspace of `k` proofs in flight: the sum's (one vector's for a bare handle), then the prepared points and the statuses
-size_t workspace_bytes(const frw_groth16_vk *vk, size_t k, size_t *msm_part = nullptr)
+// the workspace of `k` proofs in flight (frw::verify_layout); pairing: with the device pairing's part, wire: with the decoder's in front
+VerifyBufs layout(const frw_groth16_vk *vk, void *ws, size_t k, bool pairing = false, int flags = 0, bool wire = false)
 {
-    const size_t m = msm_workspace(vk) * (msm_bare(vk) ? 1 : k);
-    if (msm_part) *msm_part = m;
-    return m + 96 * k + ((4 * k + 15) & ~(size_t)15);
-}
-// proofs in flight for a workspace of `bytes` (0: not even one)
-size_t proofs_in_flight(const frw_groth16_vk *vk, size_t batch, size_t bytes)
-{
-    if (batch == 0 || workspace_bytes(vk, 1) > bytes) return 0;
-    size_t lo = 1, hi = batch;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (workspace_bytes(vk, mid) <= bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
+    return verify_layout(ws, k, msm_workspace(vk), msm_bare(vk), pairing ? pairing_dev::proof_workspace_bytes(flags) : 0,
+                         pairing ? pairing_dev::pass_workspace_bytes(flags) : 0, wire);
 }
 
 int prepare(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, uint64_t *d_prepared, int32_t *d_status,
@@ -166,7 +154,7 @@ extern "C" int frw_groth16_vk_load_dev(int device, const uint64_t *vk, size_t nu
 extern "C" size_t frw_groth16_verify_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight)
 {
     if (!vk || !vk->msm || batch_in_flight == 0) return 0;
-    return frw::workspace_bytes(vk, batch_in_flight);
+    return frw::layout(vk, nullptr, batch_in_flight).bytes;
 }
 
 extern "C" int frw_groth16_prepare_inputs_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, uint64_t *d_prepared,
@@ -176,7 +164,7 @@ extern "C" int frw_groth16_prepare_inputs_dev(const frw_groth16_vk *vk, size_t b
     if (encoding != FRW_ENC_MONTGOMERY && encoding != FRW_ENC_CANONICAL) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_instance || !d_prepared || !d_status || !d_workspace || ((uintptr_t)d_workspace & 15) ||
-        workspace_bytes < frw::workspace_bytes(vk, 1))
+        workspace_bytes < frw::layout(vk, nullptr, 1).bytes)
         return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
@@ -191,25 +179,22 @@ extern "C" int frw_groth16_verify_dev(const frw_groth16_vk *vk, size_t batch, co
     if (encoding != FRW_ENC_MONTGOMERY && encoding != FRW_ENC_CANONICAL) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_instance || !d_proofs || !accepted || !d_workspace || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
-    const size_t chunk = frw::proofs_in_flight(vk, batch, workspace_bytes);
+    const size_t chunk = frw::proofs_in_flight(batch, workspace_bytes, [&](size_t k) { return frw::layout(vk, nullptr, k).bytes; });
     if (chunk == 0) return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
     const hipStream_t st = (hipStream_t)stream;
     const size_t n = vk->num_instance;
     try {
-        size_t msm_part = 0;
-        frw::workspace_bytes(vk, chunk, &msm_part);
-        uint64_t *d_prepared = (uint64_t *)((char *)d_workspace + msm_part);
-        int32_t *d_status = (int32_t *)(d_prepared + 12 * chunk);
+        const frw::VerifyBufs v = frw::layout(vk, d_workspace, chunk);
         std::vector<uint64_t> prepared(12 * chunk), proofs(48 * chunk);
         std::vector<int32_t> status(chunk);
         for (size_t lo = 0; lo < batch; lo += chunk) {
             const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
-            const int rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, d_prepared, d_status, d_workspace, msm_part, st);
+            const int rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, v.prepared, v.status, v.msm_ws, v.msm_bytes, st);
             if (rc != FRW_OK) return rc;
-            e = hipMemcpyAsync(prepared.data(), d_prepared, cnt * 96, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(status.data(), d_status, cnt * 4, hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(prepared.data(), v.prepared, cnt * 96, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(status.data(), v.status, cnt * 4, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipMemcpyAsync(proofs.data(), d_proofs + lo * 48, cnt * 384, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) return frw::record_hip_error(e, "frw_groth16_verify_dev");
@@ -228,41 +213,31 @@ extern "C" int frw_groth16_verify_dev(const frw_groth16_vk *vk, size_t batch, co
 // ---- the whole verification on the device --------------------------------------------------------------------------------------------
 namespace frw {
 namespace {
-size_t full_workspace_bytes(const frw_groth16_vk *vk, size_t k, int flags, size_t *prepare_part = nullptr)
-{
-    const size_t p = workspace_bytes(vk, k);
-    if (prepare_part) *prepare_part = p;
-    return p + k * pairing_dev::proof_workspace_bytes(flags) + pairing_dev::pass_workspace_bytes(flags);
-}
-size_t full_proofs_in_flight(const frw_groth16_vk *vk, size_t batch, int flags, size_t bytes)
-{
-    if (batch == 0 || full_workspace_bytes(vk, 1, flags) > bytes) return 0;
-    size_t lo = 1, hi = batch;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (full_workspace_bytes(vk, mid, flags) <= bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-// frw_groth16_verify_wire_dev: the decoded proofs (384 bytes each) and the decoder's statuses in front of the chain's own workspace
-size_t wire_part_bytes(size_t k) { return 384 * k + ((4 * k + 15) & ~(size_t)15); }
-size_t wire_proofs_in_flight(const frw_groth16_vk *vk, size_t batch, int flags, size_t bytes)
-{
-    if (batch == 0 || wire_part_bytes(1) + full_workspace_bytes(vk, 1, flags) > bytes) return 0;
-    size_t lo = 1, hi = batch;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (wire_part_bytes(mid) + full_workspace_bytes(vk, mid, flags) <= bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 // a proof the decoder refused is malformed for everything that follows (after prepare, which sets d_status from the instance vector)
 __global__ __launch_bounds__(256) void wire_status_kernel(uint64_t n, const int32_t *__restrict__ decoded, int32_t *__restrict__ status)
 {
     const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (g < n && decoded[g]) status[g] = -1;
+}
+// The chain, `chunk` proofs at a time: (d_wire: the decoder, in place of d_proofs,) prepare_inputs, (the decoder's refusals into the
+// statuses,) the proofs' checks and the pairings.  The entry points have validated the arguments and found `chunk`.
+int verify_chain(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint64_t *d_proofs, const uint8_t *d_wire, int mode,
+                 int flags, const uint64_t *seed, int32_t *d_accepted, int32_t *d_batch_passed, void *d_workspace, size_t chunk, hipStream_t st)
+{
+    const bool wire = d_wire != nullptr;
+    const VerifyBufs v = layout(vk, d_workspace, chunk, true, flags, wire);
+    const size_t n = vk->num_instance, wire_bytes = wire ? wire::proof_bytes(mode) : 0;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
+        int rc = wire ? wire::decode_proofs_launch(cnt, d_wire + lo * wire_bytes, mode, v.decoded, v.decode_status, st) : FRW_OK;
+        if (rc == FRW_OK) rc = prepare(vk, cnt, d_instance + lo * n * 4, encoding, v.prepared, v.status, v.msm_ws, v.msm_bytes, st);
+        if (rc != FRW_OK) return rc;
+        if (wire) hipLaunchKernelGGL(wire_status_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (uint64_t)cnt, (const int32_t *)v.decode_status, v.status);
+        rc = pairing_dev::verify_proofs(vk, cnt, lo, wire ? v.decoded : d_proofs + lo * 48, v.prepared, v.status, flags, seed, d_accepted + lo, d_batch_passed,
+                                        v.pairing_ws, st);
+        if (rc != FRW_OK) return rc;
+    }
+    return FRW_OK;
 }
 }  // namespace
 }  // namespace frw
@@ -270,7 +245,7 @@ __global__ __launch_bounds__(256) void wire_status_kernel(uint64_t n, const int3
 extern "C" size_t frw_groth16_verify_full_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags)
 {
     if (!vk || !vk->msm || !vk->d_pairing || batch_in_flight == 0 || (flags & ~(FRW_VERIFY_POINTS_ARE_CHECKED | FRW_VERIFY_BATCHED))) return 0;
-    return frw::full_workspace_bytes(vk, batch_in_flight, flags);
+    return frw::layout(vk, nullptr, batch_in_flight, true, flags).bytes;
 }
 
 extern "C" int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding,
@@ -283,35 +258,19 @@ extern "C" int frw_groth16_verify_full_dev(const frw_groth16_vk *vk, size_t batc
     if ((flags & FRW_VERIFY_BATCHED) && !seed) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_instance || !d_proofs || !d_accepted || !d_workspace || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
-    const size_t chunk = frw::full_proofs_in_flight(vk, batch, flags, workspace_bytes);
+    const size_t chunk = frw::proofs_in_flight(batch, workspace_bytes, [&](size_t k) { return frw::layout(vk, nullptr, k, true, flags).bytes; });
     if (chunk == 0) return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n = vk->num_instance;
-    size_t prepare_part = 0, msm_part = 0;
-    frw::full_workspace_bytes(vk, chunk, flags, &prepare_part);
-    frw::workspace_bytes(vk, chunk, &msm_part);
-    uint64_t *d_prepared = (uint64_t *)((char *)d_workspace + msm_part);
-    int32_t *d_status = (int32_t *)(d_prepared + 12 * chunk);
-    void *d_pairing_ws = (char *)d_workspace + prepare_part;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
-        int rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, d_prepared, d_status, d_workspace, msm_part, st);
-        if (rc == FRW_OK)
-            rc = frw::pairing_dev::verify_proofs(vk, cnt, lo, d_proofs + lo * 48, d_prepared, d_status, flags, seed, d_accepted + lo,
-                                                 d_batch_passed, d_pairing_ws, st);
-        if (rc != FRW_OK) return rc;
-    }
-    return FRW_OK;
+    return frw::verify_chain(vk, batch, d_instance, encoding, d_proofs, nullptr, 0, flags, seed, d_accepted, d_batch_passed, d_workspace, chunk, (hipStream_t)stream);
 }
 
 // ---- the same from proofs in ark-serialize's wire format (frw_wire.h) ----------------------------------------------------------------
 extern "C" size_t frw_groth16_verify_wire_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int flags, int mode)
 {
     if (mode != FRW_WIRE_COMPRESSED && mode != FRW_WIRE_UNCOMPRESSED) return 0;
-    const size_t full = frw_groth16_verify_full_workspace_bytes(vk, batch_in_flight, flags);
-    return full ? frw::wire_part_bytes(batch_in_flight) + full : 0;
+    if (!frw_groth16_verify_full_workspace_bytes(vk, batch_in_flight, flags)) return 0;           // (its checks of vk and flags)
+    return frw::layout(vk, nullptr, batch_in_flight, true, flags, true).bytes;
 }
 
 extern "C" int frw_groth16_verify_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_instance, int encoding, const uint8_t *d_wire,
@@ -325,31 +284,9 @@ extern "C" int frw_groth16_verify_wire_dev(const frw_groth16_vk *vk, size_t batc
     if ((flags & FRW_VERIFY_BATCHED) && !seed) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_instance || !d_wire || !d_accepted || !d_workspace || ((uintptr_t)d_workspace & 15)) return FRW_E_INVALID_ARG;
-    const size_t chunk = frw::wire_proofs_in_flight(vk, batch, flags, workspace_bytes);
+    const size_t chunk = frw::proofs_in_flight(batch, workspace_bytes, [&](size_t k) { return frw::layout(vk, nullptr, k, true, flags, true).bytes; });
     if (chunk == 0) return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t n = vk->num_instance, wire_bytes = frw::wire::proof_bytes(mode);
-    uint64_t *d_decoded = (uint64_t *)d_workspace;
-    int32_t *d_decode_status = (int32_t *)(d_decoded + 48 * chunk);
-    char *ws = (char *)d_workspace + frw::wire_part_bytes(chunk);
-    size_t prepare_part = 0, msm_part = 0;
-    frw::full_workspace_bytes(vk, chunk, flags, &prepare_part);
-    frw::workspace_bytes(vk, chunk, &msm_part);
-    uint64_t *d_prepared = (uint64_t *)(ws + msm_part);
-    int32_t *d_status = (int32_t *)(d_prepared + 12 * chunk);
-    void *d_pairing_ws = ws + prepare_part;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = batch - lo < chunk ? batch - lo : chunk;
-        int rc = frw::wire::decode_proofs_launch(cnt, d_wire + lo * wire_bytes, mode, d_decoded, d_decode_status, st);
-        if (rc == FRW_OK) rc = frw::prepare(vk, cnt, d_instance + lo * n * 4, encoding, d_prepared, d_status, ws, msm_part, st);
-        if (rc != FRW_OK) return rc;
-        hipLaunchKernelGGL(frw::wire_status_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (uint64_t)cnt,
-                           (const int32_t *)d_decode_status, d_status);
-        rc = frw::pairing_dev::verify_proofs(vk, cnt, lo, d_decoded, d_prepared, d_status, flags, seed, d_accepted + lo, d_batch_passed,
-                                             d_pairing_ws, st);
-        if (rc != FRW_OK) return rc;
-    }
-    return FRW_OK;
+    return frw::verify_chain(vk, batch, d_instance, encoding, nullptr, d_wire, mode, flags, seed, d_accepted, d_batch_passed, d_workspace, chunk, (hipStream_t)stream);
 }

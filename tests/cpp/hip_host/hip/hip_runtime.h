@@ -7,5 +7,6 @@
 #define __host__
 #define __global__
 #define __forceinline__ inline
+struct uint2 { uint32_t x, y; };
 struct uint4 { uint32_t x, y, z, w; };
 static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }

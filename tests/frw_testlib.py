@@ -302,3 +302,19 @@ def compact_from_witness(logn, wit, inst, CL=None, status=0):
     out[CL.instance_off: CL.instance_off + iv.nbytes] = iv.view(np.uint8)
     out[CL.status_off: CL.status_off + 4] = np.array([status], dtype=np.uint32).view(np.uint8)
     return out.tobytes()
+
+
+GUARD_BYTES = 4096
+
+
+def guarded_workspace(size, device):
+    """A device workspace of exactly `size` bytes with GUARD_BYTES of 0xA5 right behind it: (the whole buffer, the workspace to hand over --
+    a view, so its numel() is what the entry point is told).  guard_intact(buffer) after the call: nothing wrote past the reported size."""
+    import torch
+    buf = torch.empty(size + GUARD_BYTES, dtype=torch.uint8, device=device)
+    buf[size:] = 0xA5
+    return buf, buf[:size]
+
+
+def guard_intact(buf):
+    return bool((buf[-GUARD_BYTES:] == 0xA5).all())

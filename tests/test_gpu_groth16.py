@@ -260,7 +260,9 @@ def test_blinding_factors_in_device_memory_and_a_captured_call(engine):
     """frw_groth16_prove_rs_dev: the blinding factors in device memory, split by the endomorphism on the device -- the same proofs,
     byte for byte, as frw_groth16_prove_dev with the same factors in host memory (incl. factors beyond the group order and the
     extremes of the split); and the call captured into a HIP graph (torch.cuda.CUDAGraph on a stream of its own: the key's streams
-    join the capture through the call's events) replays to the same proofs, and to the right ones after the factors in d_rs change."""
+    join the capture through the call's events) replays to the same proofs, and to the right ones after the factors in d_rs change.
+    Last, frw_groth16_workspace_bytes is all a call touches: the three proofs in a workspace of exactly two proofs' size (the chunk loop
+    wraps), bytes of 0xA5 behind it untouched, the same proofs; a workspace one byte short of one proof's is refused."""
     import torch
     import falcon_r1cs_amd as frw
     dev = torch.device("cuda:0")
@@ -313,6 +315,16 @@ def test_blinding_factors_in_device_memory_and_a_captured_call(engine):
             graph.replay()
             torch.cuda.synchronize()
             assert torch.equal(got, want[k]), "replay %d" % k
+        ws2_bytes = engine.groth16_workspace_bytes(key, r1cs, 2)
+        buf, ws2 = T.guarded_workspace(ws2_bytes, dev)
+        got.zero_()
+        engine.groth16_prove_dev(key, r1cs, batch, wit, inst, lim(sets[1]), got, ws2, ws2_bytes, None, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert torch.equal(got, want[1]) and T.guard_intact(buf)
+        with pytest.raises(frw.FrwError) as ei:
+            engine.groth16_prove_dev(key, r1cs, 1, wit, inst, lim(sets[1][:1]), got, ws2, engine.groth16_workspace_bytes(key, r1cs, 1) - 1, None,
+                                     torch.cuda.current_stream().cuda_stream)
+        assert ei.value.code == -1
     finally:
         engine.r1cs_free(r1cs)
         engine.groth16_pk_free(key)

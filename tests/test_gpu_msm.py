@@ -38,10 +38,14 @@ def _run(engine, handle, scalars, montgomery, chunk=None):
 HANDLES = [(False, False), (True, False), (False, True), (True, True), (False, "wide")]
 HANDLE_IDS = ["tables-16bit", "tables-8bit", "bare-16bit", "bare-8bit", "bare-20bit"]
 
-@pytest.mark.parametrize("narrow,bare", HANDLES, ids=HANDLE_IDS)
-def test_small_and_adversarial_inputs_equal_the_cpu_bucket_method(engine, oracle, narrow, bare):
-    """Both pipelines (16-bit windows / 32,768 buckets; 8-bit windows / 128 buckets: frw_msm_g1_load_narrow), over window tables and over
-    bare handles (the points only: frw_msm_g1_load_bare -- the sums then run window by window and end in Horner's rule)."""
+_ADVERSARIAL = []
+
+
+def _adversarial(oracle):
+    """300 bases that meet each other inside a bucket, twelve scalar vectors for them and the oracle's sums, made once:
+    (n, bases, vectors, canon, mont, want)"""
+    if _ADVERSARIAL:
+        return _ADVERSARIAL[0]
     rng = random.Random(2026)
     n = 300
     ks = [rng.randrange(1, E.R) for _ in range(n)]
@@ -67,14 +71,23 @@ def test_small_and_adversarial_inputs_equal_the_cpu_bucket_method(engine, oracle
     ]
     vectors[0][3] = vectors[0][10]                                 # the duplicated base with the same scalar: doubling
     vectors[0][11] = vectors[0][4]                                 # the negated base with the same scalar: cancellation
+    canon = np.stack([T.ints_to_limbs(v) for v in vectors])
+    mont = np.stack([T.ints_to_limbs([x * FR_R % E.R for x in v]) for v in vectors])
+    want = [oracle.g1_msm(bases, T.ints_to_limbs([x % E.R for x in v]), 11).tolist() for v in vectors]
+    _ADVERSARIAL.append((n, bases, vectors, canon, mont, want))
+    return _ADVERSARIAL[0]
+
+
+@pytest.mark.parametrize("narrow,bare", HANDLES, ids=HANDLE_IDS)
+def test_small_and_adversarial_inputs_equal_the_cpu_bucket_method(engine, oracle, narrow, bare):
+    """Both pipelines (16-bit windows / 32,768 buckets; 8-bit windows / 128 buckets: frw_msm_g1_load_narrow), over window tables and over
+    bare handles (the points only: frw_msm_g1_load_bare -- the sums then run window by window and end in Horner's rule)."""
+    n, bases, vectors, canon, mont, want = _adversarial(oracle)
     handle = engine.msm_g1_load(bases, narrow=narrow, bare=bool(bare), wide=bare == "wide")
     try:
         info = engine.msm_info(handle)
         assert info.num_points == n and (info.window_bits, info.num_windows) == ((20, 13) if bare == "wide" else (8, 32) if narrow else (16, 16))
         assert info.table_bytes == n * 112 * (1 if bare else info.num_windows) + (0 if bare or not narrow else (n + 7) // 8 * 255 * 112)
-        canon = np.stack([T.ints_to_limbs(v) for v in vectors])
-        mont = np.stack([T.ints_to_limbs([x * FR_R % E.R for x in v]) for v in vectors])
-        want = [oracle.g1_msm(bases, T.ints_to_limbs([x % E.R for x in v]), 11).tolist() for v in vectors]
         assert want[1] == [0] * 12                                 # all-zero scalars: the point at infinity
         for got in (_run(engine, handle, canon, 0), _run(engine, handle, mont, 1), _run(engine, handle, mont, 1, chunk=3)):
             assert [g.tolist() for g in got] == want
@@ -85,6 +98,31 @@ def test_small_and_adversarial_inputs_equal_the_cpu_bucket_method(engine, oracle
         # a longer stride than points: only the first n scalars of each vector count (how h is laid out: n + 1 per signature)
         padded = np.concatenate([canon, np.full((len(vectors), 5, 4), 0xFFFFFFFF, dtype=np.uint64)], axis=1)
         assert [g.tolist() for g in _run(engine, handle, padded, 0)] == want
+    finally:
+        engine.msm_free(handle)
+
+
+@pytest.mark.parametrize("narrow,bare", HANDLES, ids=HANDLE_IDS)
+def test_a_workspace_of_exactly_the_reported_size(engine, oracle, narrow, bare):
+    """frw_msm_info's bytes per signature are all a call touches: the adversarial vectors one signature at a time in a workspace of exactly
+    that size, bytes of 0xA5 behind it -- the oracle's sums, the bytes untouched; and one byte less is refused (FRW_E_INVALID_ARG)."""
+    import torch
+    import falcon_r1cs_amd as frw
+    dev = torch.device("cuda:0")
+    n, bases, vectors, canon, mont, want = _adversarial(oracle)
+    handle = engine.msm_g1_load(bases, narrow=narrow, bare=bool(bare), wide=bare == "wide")
+    try:
+        per = int(engine.msm_info(handle).workspace_bytes_per_signature)
+        buf, ws = T.guarded_workspace(per, dev)
+        d_sc = torch.from_numpy(canon.view(np.int64)).to(dev)
+        out = torch.full((len(vectors), 12), -1, dtype=torch.int64, device=dev)
+        engine.msm_g1_dev(handle, len(vectors), d_sc, n, 0, out, ws, per, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert [g.tolist() for g in out.cpu().numpy().view(np.uint64)] == want
+        assert T.guard_intact(buf)
+        with pytest.raises(frw.FrwError) as ei:
+            engine.msm_g1_dev(handle, 1, d_sc, n, 0, out, ws, per - 1, torch.cuda.current_stream().cuda_stream)
+        assert ei.value.code == -1
     finally:
         engine.msm_free(handle)
 

@@ -275,6 +275,41 @@ def test_streams_graph_capture_and_chunks(oracle):
     ver.close()
 
 
+def _accepted_and_refused(k, n, seed):
+    """two cases for the key: a proof that verifies, and the same with A off its curve (refused: -1) -- (instances, proofs' limbs)"""
+    rng, rs = random.Random(seed), np.random.default_rng(seed)
+    small = rs.integers(0, 1 << 14, n); small[0] = 1
+    good = proof_limbs(k.proof(k.dot(small, {}), rng))
+    off = good.copy(); off[6] ^= np.uint64(1)
+    x = encode(small, {}, True)
+    return np.stack([x, x]), np.stack([good, off])
+
+
+def test_a_workspace_of_exactly_the_reported_size(oracle):
+    """frw_groth16_verify_full_workspace_bytes is all a call touches: an accepted and a refused proof in a workspace of exactly two proofs'
+    size, bytes of 0xA5 behind it -- the host's verdicts, the bytes untouched; one byte short of one proof's is refused (FRW_E_INVALID_ARG)."""
+    import torch
+    import falcon_r1cs_amd as frw
+    n = 1025
+    k = key(oracle, n)
+    inst, proofs = _accepted_and_refused(k, n, 31)
+    host = frw.Groth16Verifier(k.limbs())
+    want = host.verify(inst, proofs).tolist()
+    host.close()
+    assert want == [1, -1]
+    ver = frw.Groth16Verifier(k.limbs(), device=0)
+    dev = torch.device("cuda:0")
+    d_inst, d_proofs = _dev(inst), _dev(proofs)
+    buf, ws = T.guarded_workspace(ver.full_workspace_bytes(2), dev)
+    assert ver.verify_full_dev(d_inst, d_proofs, workspace=ws).cpu().tolist() == want
+    assert T.guard_intact(buf)
+    with pytest.raises(frw.FrwError) as ei:
+        ver.verify_full_dev(d_inst[:1], d_proofs[:1], workspace=buf[:ver.full_workspace_bytes(1) - 1])
+    assert ei.value.code == -1
+    torch.cuda.synchronize()
+    ver.close()
+
+
 def test_a_key_with_gamma_at_infinity(oracle):
     """a pair whose fixed G2 point is the point at infinity contributes one, on the host and on the device alike"""
     import falcon_r1cs_amd as frw

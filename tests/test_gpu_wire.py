@@ -12,7 +12,7 @@ import frw_testlib as T
 import wire_ref as W
 from oracle import bls12_381 as E
 from test_gpu_verify_dev import R, _dev, encode, key, proof_limbs
-from test_gpu_verify_full import _batch, _mixed_cases
+from test_gpu_verify_full import _accepted_and_refused, _batch, _mixed_cases
 from test_wire_codec import g2_points_whose_y_squared_has_no_u_part, malformed_cases
 
 pytestmark = pytest.mark.gpu
@@ -182,6 +182,31 @@ def test_verdicts_from_wire_bytes_equal_verify_full_dev_on_the_decoded_limbs(ora
     assert lib.frw_groth16_verify_wire_dev(*args(ws.data_ptr() + 8, ws.numel() - 8)) == -1
     assert lib.frw_groth16_verify_wire_dev(*args(ws.data_ptr(), ws.numel(), flags=2)) == -1
     assert ver.wire_workspace_bytes(count, 0, compressed) > 0 and lib.frw_groth16_verify_wire_workspace_bytes(ver._h, count, 0, 2) == 0
+    torch.cuda.synchronize()
+    ver.close()
+
+
+def test_a_workspace_of_exactly_the_reported_size(oracle):
+    """frw_groth16_verify_wire_workspace_bytes is all a call touches: an accepted proof and bytes the decoder refuses in a workspace of
+    exactly two proofs' size, bytes of 0xA5 behind it -- accepted and -1, the bytes untouched; one byte short of one proof's is refused."""
+    import torch
+    import falcon_r1cs_amd as frw
+    n = 1025
+    k = key(oracle, n)
+    inst, limbs = _accepted_and_refused(k, n, 37)
+    wire, _ = frw.proofs_to_wire(limbs, True)
+    name, bad = next(iter(malformed_cases(True, bytes(wire[0])).items()))
+    wire[1] = np.frombuffer(bad, dtype=np.uint8)
+    assert frw.proofs_from_wire(wire, True)[1].tolist() == [0, -1], name
+    ver = frw.Groth16Verifier(k.limbs(), device=0)
+    dev = torch.device("cuda:0")
+    d_inst, d_wire = _dev(inst), torch.from_numpy(wire).to(dev)
+    buf, ws = T.guarded_workspace(ver.wire_workspace_bytes(2), dev)
+    assert ver.verify_wire_dev(d_inst, d_wire, True, workspace=ws).cpu().tolist() == [1, -1]
+    assert T.guard_intact(buf)
+    with pytest.raises(frw.FrwError) as ei:
+        ver.verify_wire_dev(d_inst[:1], d_wire[:1], True, workspace=buf[:ver.wire_workspace_bytes(1) - 1])
+    assert ei.value.code == -1
     torch.cuda.synchronize()
     ver.close()
 

@@ -11,7 +11,12 @@
     (a Proof on the wire)                                             -> frw_groth16_proofs_to_wire_dev: the 192 bytes of Proof::serialize,
                                                                         verified from them by frw_groth16_verify_wire_dev
 
-    python examples/pok_sig.py tests/golden/falcon_signed.json [--case 0] [--seed 1] [--json]
+    (a ProvingKey on disk)                                            -> --key-file PATH: the key is read from PATH if it exists
+                                                                        (frw_groth16_pk_load_wire_dev: what pk.serialize(&mut file)
+                                                                        wrote), otherwise made as above and written there
+                                                                        (frw_groth16_pk_to_wire_dev)
+
+    python examples/pok_sig.py tests/golden/falcon_signed.json [--case 0] [--seed 1] [--json] [--key-file PATH]
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--case", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1, help="seed of the toxic waste and the blinding factors (a key whose toxic waste is known proves nothing: demonstration only)")
     ap.add_argument("--json", action="store_true", help="print the verifying key, public inputs and proof as JSON (hex limbs)")
+    ap.add_argument("--key-file", help="the proving key in ark-serialize's compressed format: loaded from here if the file exists, else made and saved here")
     args = ap.parse_args()
     case = json.load(open(args.signed))["cases"][args.case]
     logn = case["logn"]
@@ -54,7 +60,13 @@ def main():
         raise SystemExit("Invalid input: the signature fails its range checks (status %d)" % int(status[0]))
     rng = random.Random(args.seed)
     alpha, beta, gamma, delta, t = (rng.randrange(2, R) for _ in range(5))
-    key, vk = eng.groth16_setup(0, logn, alpha, beta, gamma, delta, t)                       # circuit_specific_setup
+    if args.key_file and os.path.exists(args.key_file):
+        key, vk = eng.groth16_pk_load_wire(open(args.key_file, "rb").read())                 # ProvingKey::deserialize: every point checked
+    else:
+        key, vk = eng.groth16_setup(0, logn, alpha, beta, gamma, delta, t)                   # circuit_specific_setup
+        if args.key_file:
+            with open(args.key_file, "wb") as f:
+                f.write(eng.groth16_pk_to_wire(key, vk))                                     # pk.serialize(&mut file)
     r1cs = eng.r1cs_load(0, logn)
     ws_bytes = eng.groth16_workspace_bytes(key, r1cs, 1)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)

@@ -62,6 +62,12 @@ class Groth16PkInfoStruct(C.Structure):
                 ("h_lo", C.c_uint64), ("h_hi", C.c_uint64), ("key_bytes", C.c_uint64)]
 
 
+class Groth16PkWireInfoStruct(C.Structure):
+    _fields_ = [("num_instance", C.c_uint64), ("num_witness", C.c_uint64), ("domain_size", C.c_uint64),
+                ("a_query_offset", C.c_uint64), ("b_g1_query_offset", C.c_uint64), ("b_g2_query_offset", C.c_uint64),
+                ("h_query_offset", C.c_uint64), ("l_query_offset", C.c_uint64)]
+
+
 class R1csInfoStruct(C.Structure):
     _fields_ = [("num_statements", C.c_uint64), ("count_logn9", C.c_uint64), ("count_logn10", C.c_uint64),
                 ("num_instance", C.c_uint64), ("num_witness", C.c_uint64), ("num_constraints", C.c_uint64),
@@ -149,6 +155,11 @@ PROTOTYPES = {
     "frw_groth16_vk_to_wire": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "frw_groth16_vk_load_wire": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
     "frw_groth16_vk_load_wire_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_groth16_pk_wire_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
+    "frw_groth16_pk_wire_info": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Groth16PkWireInfoStruct)]),
+    "frw_groth16_pk_load_wire_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Groth16KeyOpts), C.POINTER(C.c_void_p),
+                                               C.c_void_p]),
+    "frw_groth16_pk_to_wire_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]),
     "frw_diag_wire_greater": (C.c_int, [C.c_void_p, C.c_void_p]),
     "frw_groth16_verify_full_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int]),
     "frw_groth16_verify_full_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -3,6 +3,7 @@
 // There is deliberately no CPU compute path here: without a HIP device every entry point that
 // would produce a witness returns FRW_E_NO_DEVICE.
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -81,6 +82,13 @@ bool bad_common(const frw_ctx *ctx, int logn, int encoding)
 
 namespace frw {
 int record_hip_error(hipError_t e, const char *what) { return hip_fail(e, what); }
+void record_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
+    va_end(ap);
+}
 }  // namespace frw
 
 extern "C" {

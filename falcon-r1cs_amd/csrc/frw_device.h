@@ -58,6 +58,8 @@ constexpr CompactLayout compact_layout(int logn)
 
 // records the message frw_last_error() returns (thread-local) and maps the HIP error to FRW_E_HIP / FRW_E_OUT_OF_MEMORY
 int record_hip_error(hipError_t e, const char *what);
+// the same message slot for a refusal that is not HIP's (printf-style): which query of a key, which point
+void record_error(const char *fmt, ...);
 void init_launch_config();
 hipError_t launch_witness_ntt_verify_compact(const Tables *tab, int num_cu, int logn, size_t batch,
                                              const uint16_t *sig, const uint16_t *pk, const uint16_t *hm, void *compact,
@@ -248,6 +250,11 @@ hipError_t fixed_base_ark_dev(const FixedBaseGen &g, int group, size_t count, co
 void groth16_shard_range(uint64_t total, uint32_t rank, uint32_t world, uint64_t *lo, uint64_t *hi);
 int groth16_pk_assemble(int device, uint64_t ni, uint64_t nw, uint64_t n, uint32_t rank, uint32_t world, ::frw_msm *h, ::frw_msm *a, ::frw_msm *b1,
                         ::frw_msm *l, ::frw_msm *b2, ::frw_groth16_pk **out);
+// what the wire-format key functions (frw_wire.hip) need of the handles: rows of a bare handle filled from ark-ff points that are in DEVICE
+// memory (null: the point at infinity), a handle's points as table rows (a bare handle's rows or window 0 of a table), a key's counts
+hipError_t msm_fill_ark_dev(::frw_msm *m, size_t first_row, size_t count, const uint32_t *d_ark, hipStream_t st);
+const uint32_t *msm_point_rows(const ::frw_msm *m, int *group, uint64_t *rows);
+void groth16_pk_counts(const ::frw_groth16_pk *pk, int *device, uint64_t *num_instance, uint64_t *num_witness, uint64_t *domain_size);
 hipError_t launch_poly_eval(uint64_t n, const uint32_t *coeffs, const SetupConst &t, const SetupPowTab &tt, uint32_t *part, uint32_t *out, hipStream_t st);
 size_t poly_eval_scratch_bytes(uint64_t n);
 hipError_t diag_valu_rates(int num_cu, void *scratch, double out[4], hipStream_t st);

@@ -33,17 +33,13 @@
 #include "frw_quad.h"
 #include "frw_fr29.h"
 #include "frw_layout.h"
+#include "frw_rows.h"
 
 namespace frw {
 
 // (MSM_C = 16, MSM_W = 16, MSM_BUCKETS = 2^15 and every other constant the workspaces' layouts depend on -- MSM_*, WIDE_*, NMSM_*: frw_layout.h)
 constexpr int MSM_FOLD_THREADS = 512;           // second stage: one workgroup per signature
-// per group (F = FqField: G1, Fq2Field: G2): a table row = x, y limbs (all zero = the point at infinity); a bucket = X, Y, ZZ,
-// ZZZ limbs + the infinity flag (padded to 16 bytes); ark-ff's bytes of an affine point
-template <class F> struct Grp {
-    static constexpr int PT_WORDS = 2 * F::WORDS, BK_WORDS = 4 * F::WORDS + 4, ARK_WORDS = 2 * F::ARK_WORDS;
-    static constexpr uint32_t K_AFFINE_Y = F::K_AFFINE;       // bound of a table row's y: what its negation adds
-};
+// (Grp<F> -- the words of a table row, a bucket, an ark-ff point -- and load_row / store_row / load_ark_point / store_ark_point: frw_rows.h)
 
 struct MsmDev {
     uint32_t n;                 // points
@@ -74,60 +70,6 @@ struct NmsmTables {
     }
 };
 
-template <class F> __device__ __forceinline__ AffineT<F> load_row(const uint32_t *row)
-{
-    constexpr int PW = Grp<F>::PT_WORDS;
-    AffineT<F> p;
-    uint32_t any = 0;
-    const uint4 *v = (const uint4 *)row;
-    uint32_t w[PW];
-#pragma unroll
-    for (int k = 0; k < PW / 4; k++) {
-        const uint4 t = v[k];
-        w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w;
-    }
-#pragma unroll
-    for (int k = 0; k < PW; k++) any |= w[k];
-    p.x = F::load(w);
-    p.y = F::load(w + F::WORDS);
-    p.inf = any == 0;
-    return p;
-}
-// the two-lane Fq2: every lane fetches its own component of x and y (56 bytes each, 8-byte aligned) and the pair agrees on `inf`
-template <> __device__ __forceinline__ AffineT<Fq2PairField> load_row<Fq2PairField>(const uint32_t *row)
-{
-    AffineT<Fq2PairField> p;
-    const uint32_t *mine = row + (Fq2PairField::odd() ? NLQ : 0);
-    uint32_t any = 0;
-#pragma unroll
-    for (int k = 0; k < NLQ / 2; k++) {
-        const uint2 a = *(const uint2 *)(mine + 2 * k), b = *(const uint2 *)(mine + 2 * NLQ + 2 * k);
-        p.x.v.l[2 * k] = a.x; p.x.v.l[2 * k + 1] = a.y;
-        p.y.v.l[2 * k] = b.x; p.y.v.l[2 * k + 1] = b.y;
-        any |= a.x | a.y | b.x | b.y;
-    }
-    any |= pair_swap_u32(any);
-    p.inf = any == 0;
-    return p;
-}
-template <class F> __device__ __forceinline__ void store_row(uint32_t *row, const AffineT<F> &p)
-{
-    uint32_t w[Grp<F>::PT_WORDS];
-    F::store(p.x, w);
-    F::store(p.y, w + F::WORDS);
-#pragma unroll
-    for (int k = 0; k < Grp<F>::PT_WORDS; k++) row[k] = p.inf ? 0u : w[k];
-}
-// the two-lane Fq2: every lane writes its own component of x and of y
-template <> __device__ __forceinline__ void store_row<Fq2PairField>(uint32_t *row, const AffineT<Fq2PairField> &p)
-{
-    uint32_t *mine = row + (Fq2PairField::odd() ? NLQ : 0);
-#pragma unroll
-    for (int k = 0; k < NLQ; k++) {
-        mine[k] = p.inf ? 0u : p.x.v.l[k];
-        mine[2 * NLQ + k] = p.inf ? 0u : p.y.v.l[k];
-    }
-}
 template <class F> __device__ __forceinline__ void store_bucket(uint32_t *b, const XyzzT<F> &p)
 {
     F::store(p.x, b); F::store(p.y, b + F::WORDS); F::store(p.zz, b + 2 * F::WORDS); F::store(p.zzz, b + 3 * F::WORDS);
@@ -139,25 +81,6 @@ template <class F> __device__ __forceinline__ XyzzT<F> load_bucket(const uint32_
     p.x = F::load(b); p.y = F::load(b + F::WORDS); p.zz = F::load(b + 2 * F::WORDS); p.zzz = F::load(b + 3 * F::WORDS);
     p.inf = b[4 * F::WORDS] != 0;
     return p;
-}
-template <class F> __device__ __forceinline__ AffineT<F> load_ark_point(const uint32_t *w)
-{
-    AffineT<F> p;
-    uint32_t any = 0;
-    for (int k = 0; k < Grp<F>::ARK_WORDS; k++) any |= w[k];
-    p.inf = any == 0;
-    p.x = F::from_ark(w);
-    p.y = F::from_ark(w + F::ARK_WORDS);
-    return p;
-}
-template <class F> __device__ __forceinline__ void store_ark_point(uint32_t *o, const AffineT<F> &a)
-{
-    if (a.inf) {
-        for (int k = 0; k < Grp<F>::ARK_WORDS; k++) o[k] = 0;
-    } else {
-        F::to_ark(a.x, o);
-        F::to_ark(a.y, o + F::ARK_WORDS);
-    }
 }
 
 // ---- load time: table[j][i] = 2^(16 j) P_i, affine, Montgomery limbs ----------------------------------------------------------
@@ -2413,6 +2336,28 @@ int msm_alloc_bare(int device, int group, int window_bits, size_t rows, uint64_t
     return group == 1 ? msm_alloc_bare_t<FqField>(device, 1, window_bits, rows, row_lo, out)
                       : msm_alloc_bare_t<Fq2Field>(device, 2, window_bits, rows, row_lo, out);
 }
+// rows [first_row, first_row + count) of a bare handle from `count` ark-ff points in DEVICE memory (msm_upload_rows' device side without
+// its host arrays: the wire-format key loader decodes into such a buffer); d_ark null: the point at infinity in every row.  On `st`.
+hipError_t msm_fill_ark_dev(frw_msm *m, size_t first_row, size_t count, const uint32_t *d_ark, hipStream_t st)
+{
+    if (count == 0) return hipSuccess;
+    if (!m->bare || first_row + count > m->dev.n) return hipErrorInvalidValue;
+    const size_t pw = m->group == 1 ? Grp<FqField>::PT_WORDS : Grp<Fq2Field>::PT_WORDS;
+    uint32_t *rows = (uint32_t *)m->table + first_row * pw;
+    if (!d_ark) return hipMemsetAsync(rows, 0, count * pw * 4, st);
+    if (m->group == 1)
+        hipLaunchKernelGGL(msm_precompute_kernel<FqField>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, (uint32_t)count, d_ark, rows, 256);
+    else
+        hipLaunchKernelGGL(msm_precompute_kernel<Fq2Field>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, (uint32_t)count, d_ark, rows, 256);
+    return hipGetLastError();
+}
+// a handle's points as table rows -- a bare handle's rows, window 0 of a window table (msm_precompute_kernel) -- and how many; *group: 1 or 2
+const uint32_t *msm_point_rows(const frw_msm *m, int *group, uint64_t *rows)
+{
+    *group = m->group;
+    *rows = m->dev.n;
+    return m->dev.table;
+}
 int fixed_base_gen_create(int device, FixedBaseGen *g)
 {
     g->g1 = g->g2 = nullptr;
@@ -2509,6 +2454,11 @@ int groth16_pk_assemble(int device, uint64_t ni, uint64_t nw, uint64_t n, uint32
     }
     *out = pk;
     return FRW_OK;
+}
+void groth16_pk_counts(const frw_groth16_pk *pk, int *device, uint64_t *ni, uint64_t *nw, uint64_t *n)
+{
+    *device = pk->device;
+    *ni = pk->num_instance; *nw = pk->num_witness; *n = pk->domain_size;
 }
 }  // namespace frw
 

@@ -337,6 +337,32 @@ def vk_to_wire(vk, compressed=True):
     return out.tobytes()
 
 
+PK_POINTS_ARE_CHECKED = 1                           # frw.h FRW_PK_POINTS_ARE_CHECKED: skip the subgroup ladders of a key the caller made itself
+
+
+def _vk_flat(vk):
+    if isinstance(vk, dict):
+        vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
+    return np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
+
+
+def groth16_pk_wire_bytes(num_instance, num_witness, domain_size, compressed=True):
+    """Bytes of an ark-groth16 ProvingKey with these counts (I with the constant one, W, n) in ark-serialize's format; 0 for counts no key has."""
+    return int(load_library().frw_groth16_pk_wire_bytes(int(num_instance), int(num_witness), int(domain_size), 0 if compressed else 1))
+
+
+def groth16_pk_wire_info(data, compressed=True):
+    """The framing of a serialised ProvingKey, read on the host without decoding a point (frw_groth16_pk_wire_info): a dict of
+    num_instance, num_witness, domain_size and the byte offset of the first point of each of the five queries.  FrwError
+    (FRW_E_INVALID_ARG) for bytes that are no key: truncated, over-long, lengths that disagree."""
+    from ._lib import Groth16PkWireInfoStruct
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = Groth16PkWireInfoStruct()
+    check(load_library().frw_groth16_pk_wire_info(buf.ctypes.data_as(C.c_void_p), buf.size, 0 if compressed else 1, C.byref(info)),
+          "frw_groth16_pk_wire_info")
+    return {name: int(getattr(info, name)) for name, _ in Groth16PkWireInfoStruct._fields_}
+
+
 def diag_pairing(g1, g2):
     """The verifier's pairing of one pair (ark-ff limbs: 12 and 24 uint64): uint64[12, 6], see frw.h."""
     g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(12)
@@ -740,6 +766,41 @@ class WitnessEngine:
         opts = Groth16KeyOpts(int(mode), int(rank), int(world))
         check(self._lib.frw_groth16_pk_load_opts(self.device, C.byref(d), C.byref(opts), C.byref(h)), "frw_groth16_pk_load")
         return h
+
+    groth16_pk_wire_bytes = staticmethod(groth16_pk_wire_bytes)
+    groth16_pk_wire_info = staticmethod(groth16_pk_wire_info)
+
+    def groth16_pk_load_wire(self, data, compressed=True, checked=True, mode=KEY_AUTO):
+        """A ProvingKey as ark-groth16 serialises it (pk.serialize / serialize_uncompressed) -> (handle, verifying key dict as groth16_setup
+        returns it).  Every point is decoded on the device and, if `checked`, tested for subgroup membership there; checked=False
+        (FRW_PK_POINTS_ARE_CHECKED) skips those ladders only and is unsafe for a key this process did not make.  FrwError
+        (FRW_E_INVALID_ARG) for a malformed or off-subgroup point or bad framing: the message names the query and the first bad index."""
+        from ._lib import Groth16KeyOpts
+        data = bytes(data)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        info = groth16_pk_wire_info(data, compressed)
+        vk = np.zeros(84 + 12 * info["num_instance"], dtype=np.uint64)
+        h = C.c_void_p()
+        opts = Groth16KeyOpts(int(mode), 0, 1)
+        check(self._lib.frw_groth16_pk_load_wire_dev(self.device, buf.ctypes.data_as(C.c_void_p), buf.size, 0 if compressed else 1,
+                                                     0 if checked else PK_POINTS_ARE_CHECKED, C.byref(opts), C.byref(h),
+                                                     vk.ctypes.data_as(C.c_void_p)), "frw_groth16_pk_load_wire_dev")
+        return h, {"alpha_g1": vk[:12], "beta_g2": vk[12:36], "gamma_g2": vk[36:60], "delta_g2": vk[60:84],
+                   "gamma_abc_g1": vk[84:].reshape(-1, 12)}
+
+    def groth16_pk_to_wire(self, pk, vk, compressed=True):
+        """The whole proving key behind a handle (table or bare, made by groth16_setup* or loaded) as the bytes ProvingKey::deserialize
+        reads.  vk: the verifying key that came with the handle (dict or flat limbs): gamma_g2 and gamma_abc_g1 are taken from it."""
+        vk = _vk_flat(vk)
+        if vk.size < 96 or (vk.size - 84) % 12:
+            raise FrwError(-1, "groth16_pk_to_wire", "verifying key: expected 84 + 12 x num_instance uint64 values")
+        ni = (vk.size - 84) // 12
+        info = self.groth16_pk_info(pk)
+        nv = int(info.z_hi) - int(info.z_lo) - 3
+        out = np.zeros(max(groth16_pk_wire_bytes(ni, nv - ni, int(info.h_hi) - int(info.h_lo) + 1, compressed), 1), dtype=np.uint8)
+        check(self._lib.frw_groth16_pk_to_wire_dev(pk, vk.ctypes.data_as(C.c_void_p), ni, 0 if compressed else 1, out.ctypes.data_as(C.c_void_p),
+                                                   out.size), "frw_groth16_pk_to_wire_dev")
+        return out.tobytes()
 
     def groth16_pk_info(self, pk):
         from ._lib import Groth16PkInfoStruct

@@ -694,6 +694,63 @@ int frw_groth16_verify_wire_dev(const frw_groth16_vk *vk, size_t batch, const ui
 int frw_groth16_vk_to_wire(const uint64_t *vk, size_t num_instance, int mode, uint8_t *out);
 int frw_groth16_vk_load_wire(const uint8_t *bytes, size_t len, int mode, frw_groth16_vk **out);
 int frw_groth16_vk_load_wire_dev(int device, const uint8_t *bytes, size_t len, int mode, frw_groth16_vk **out);
+/* PROVING keys: what ark-groth16 0.3.0's ProvingKey<Bls12_381> is after pk.serialize(&mut file) (FRW_WIRE_COMPRESSED) or
+ * pk.serialize_uncompressed(&mut file).  The struct derives CanonicalSerialize, so the bytes are its fields in order:
+ *   vk            the VerifyingKey exactly as frw_groth16_vk_to_wire writes it:
+ *                 alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | le64(I) | gamma_abc_g1[I]
+ *   beta_g1       G1
+ *   delta_g1      G1
+ *   a_query       le64(len) | G1[len]        len = I + W
+ *   b_g1_query    le64(len) | G1[len]        len = I + W
+ *   b_g2_query    le64(len) | G2[len]        len = I + W
+ *   h_query       le64(len) | G1[len]        len = n - 1
+ *   l_query       le64(len) | G1[len]        len = W
+ * with the point encodings, flag bits, "greater" rule and strictness of the block above.  Like the rest of that block this layout is
+ * restated from the crate's source as recalled and is UNPINNED against ark-groth16: the independent check is a second
+ * restatement in Python integers (tests/pk_wire_ref.py), not bytes that the crate wrote.
+ * I (the constant one included), W and n are READ FROM THE BYTES: n = len(h_query) + 1 must be a power of two and at least 2, the three
+ * I + W lengths must agree with each other, with len(l_query) + I and with the verifying key's I (I >= 1), and the total length must be
+ * exactly what those counts imply.  Points at infinity (a variable on no A or B side) load as the all-zero rows the sums skip.
+ *   frw_groth16_pk_wire_bytes   the size for (I, W, n); 0 for a bad mode, I = 0, n < 2 or not a power of two, or counts beyond 2^40
+ *   frw_groth16_pk_wire_info    HOST only, no device, no point decoded: walks the framing, returns the counts and the byte offset of the
+ *                               first point of each of the five runs (after its le64); FRW_E_INVALID_ARG for anything the rules above
+ *                               exclude (truncated, over-long, disagreeing lengths, a length field larger than the buffer, ...) --
+ *                               nothing beyond `len` is read
+ *   frw_groth16_pk_load_wire_dev  `bytes`: host memory, any alignment.  opts: NULL = FRW_KEY_AUTO; FRW_KEY_TABLES / FRW_KEY_BARE are
+ *                               honoured; world > 1 -> FRW_E_INVALID_ARG (a key in slices from wire bytes is OUT OF SCOPE: load the whole
+ *                               key, or slice limbs with frw_groth16_pk_load_opts).  vk_out (optional): 84 + 12 I uint64_t, the embedded
+ *                               verifying key in the layout frw_groth16_setup writes, ready for frw_groth16_vk_load*.  EVERY point of the
+ *                               six runs (gamma_abc_g1 and the five queries) is decoded ON THE DEVICE, a lane per point -- canonical
+ *                               coordinates, the flag rules, the curve equation or the root -- and, unless flags has
+ *                               FRW_PK_POINTS_ARE_CHECKED, tested for membership of the subgroup of order r there too (the 255-bit
+ *                               ladder every other loader runs); the seven fixed points are decoded and checked on the host by the same
+ *                               code.  The bytes go through a device buffer of FRW_PK_WIRE_CHUNK_BYTES at a time and the decoded limbs
+ *                               feed the key's tables in device memory: nothing decoded returns to the host but the verifying key.
+ *                               Any malformed point, any point outside its subgroup, any framing error: FRW_E_INVALID_ARG, *pk_out ==
+ *                               NULL, and frw_last_error() names the query and the first bad index.  No device -> FRW_E_NO_DEVICE (no
+ *                               host fallback).  Allocates and frees its own device memory, takes no workspace, synchronises: NOT
+ *                               capture-safe.
+ *   FRW_PK_POINTS_ARE_CHECKED   skips the subgroup ladders ONLY; the decoder's checks are never skipped.  UNSAFE for a key the caller
+ *                               did not make itself: a query point outside the subgroup makes proofs that leak or fail, and nothing
+ *                               downstream notices.  For a file this process wrote a moment ago.
+ *   frw_groth16_pk_to_wire_dev  the whole key into HOST memory `out` (out_len must be frw_groth16_pk_wire_bytes of the key's counts).
+ *                               vk: the limb layout frw_groth16_setup returns, num_instance = the key's I -- gamma_g2 and gamma_abc_g1
+ *                               are taken from it (the handle does not hold them); everything else, alpha_g1, beta_g2 and delta_g2
+ *                               included, comes from the handle's own rows (window 0 of a table handle, a bare handle's row; the three
+ *                               padding rows of the witness-side tables: frw_groth16_key_opts_t), encoded on the device a lane per row.
+ *                               Table and bare keys, made by frw_groth16_setup* or loaded, alike; a slice of a key (world > 1), a wrong
+ *                               out_len or num_instance -> FRW_E_INVALID_ARG.  Allocates, synchronises: not capture-safe. */
+#define FRW_PK_POINTS_ARE_CHECKED 1
+#define FRW_PK_WIRE_CHUNK_BYTES (32u << 20)
+typedef struct {
+    uint64_t num_instance, num_witness, domain_size;      /* I (with the constant one), W, n */
+    uint64_t a_query_offset, b_g1_query_offset, b_g2_query_offset, h_query_offset, l_query_offset;
+} frw_groth16_pk_wire_info_t;
+size_t frw_groth16_pk_wire_bytes(uint64_t num_instance, uint64_t num_witness, uint64_t domain_size, int mode);
+int frw_groth16_pk_wire_info(const uint8_t *bytes, size_t len, int mode, frw_groth16_pk_wire_info_t *out);
+int frw_groth16_pk_load_wire_dev(int device, const uint8_t *bytes, size_t len, int mode, int flags, const frw_groth16_key_opts_t *opts,
+                                 frw_groth16_pk **pk_out, uint64_t *vk_out);
+int frw_groth16_pk_to_wire_dev(const frw_groth16_pk *pk, const uint64_t *vk, size_t num_instance, int mode, uint8_t *out, size_t out_len);
 /* diagnostics for the codec's tests: the "greater" test on canonical integers (uint64_t[6] each; c1 NULL: the Fq order of c0, else
  * the Fq2 order, c1 first) -> 1 if y > -y, else 0; FRW_E_INVALID_ARG for a null c0 */
 int frw_diag_wire_greater(const uint64_t *c0, const uint64_t *c1);

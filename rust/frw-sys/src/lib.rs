@@ -166,6 +166,21 @@ pub struct frw_groth16_pk_info_t {
     pub h_hi: u64,
     pub key_bytes: u64,
 }
+/// the subgroup ladders of frw_groth16_pk_load_wire_dev are skipped (the decoder's checks never are): unsafe for a key the caller did not make
+pub const FRW_PK_POINTS_ARE_CHECKED: c_int = 1;
+pub const FRW_PK_WIRE_CHUNK_BYTES: u32 = 32 << 20;
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct frw_groth16_pk_wire_info_t {
+    pub num_instance: u64,
+    pub num_witness: u64,
+    pub domain_size: u64,
+    pub a_query_offset: u64,
+    pub b_g1_query_offset: u64,
+    pub b_g2_query_offset: u64,
+    pub h_query_offset: u64,
+    pub l_query_offset: u64,
+}
 
 extern "C" {
     pub fn frw_layout(logn: c_int, out: *mut frw_layout_t) -> c_int;
@@ -307,6 +322,11 @@ extern "C" {
     pub fn frw_groth16_vk_to_wire(vk: *const u64, num_instance: usize, mode: c_int, out: *mut u8) -> c_int;
     pub fn frw_groth16_vk_load_wire(bytes: *const u8, len: usize, mode: c_int, out: *mut *mut frw_groth16_vk) -> c_int;
     pub fn frw_groth16_vk_load_wire_dev(device: c_int, bytes: *const u8, len: usize, mode: c_int, out: *mut *mut frw_groth16_vk) -> c_int;
+    pub fn frw_groth16_pk_wire_bytes(num_instance: u64, num_witness: u64, domain_size: u64, mode: c_int) -> usize;
+    pub fn frw_groth16_pk_wire_info(bytes: *const u8, len: usize, mode: c_int, out: *mut frw_groth16_pk_wire_info_t) -> c_int;
+    pub fn frw_groth16_pk_load_wire_dev(device: c_int, bytes: *const u8, len: usize, mode: c_int, flags: c_int, opts: *const frw_groth16_key_opts_t,
+                                        pk_out: *mut *mut frw_groth16_pk, vk_out: *mut u64) -> c_int;
+    pub fn frw_groth16_pk_to_wire_dev(pk: *const frw_groth16_pk, vk: *const u64, num_instance: usize, mode: c_int, out: *mut u8, out_len: usize) -> c_int;
     pub fn frw_diag_wire_greater(c0: *const u64, c1: *const u64) -> c_int;
     pub fn frw_diag_pairing_dev(device: c_int, count: usize, g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,

@@ -33,6 +33,12 @@ class LayoutDualStruct(C.Structure):
                 ("seg_off", C.c_int32 * 15), ("seg_len", C.c_int32 * 15)]
 
 
+class LayoutSchoolbookStruct(C.Structure):
+    _fields_ = [("logn", C.c_int32), ("n", C.c_int32), ("num_witness", C.c_int32),
+                ("num_instance", C.c_int32), ("num_constraints", C.c_int32), ("column_len", C.c_int32),
+                ("seg_off", C.c_int32 * 5), ("seg_len", C.c_int32 * 5)]
+
+
 class CompactLayoutStruct(C.Structure):
     _fields_ = [("logn", C.c_int32), ("n", C.c_int32), ("bytes_per_signature", C.c_uint64),
                 ("small_off", C.c_uint64), ("num_small", C.c_uint64), ("t_off", C.c_uint64), ("num_t", C.c_uint64),
@@ -176,6 +182,11 @@ PROTOTYPES = {
                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_witness_dual_ntt_verify": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "frw_layout_schoolbook": (C.c_int, [C.c_int, C.POINTER(LayoutSchoolbookStruct)]),
+    "frw_witness_schoolbook_verify_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_witness_schoolbook_verify": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "frw_r1cs_export": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_void_p]),
     "frw_r1cs_load": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "frw_r1cs_free": (None, [C.c_void_p]),

@@ -71,6 +71,7 @@ void build_tables(frw::Tables &t)
         }
         memcpy(t.ck[k], c, sizeof c);
     }
+    frw::schoolbook_inverses(t.sb_qinv, t.sb_nqinv);
 }
 
 bool bad_common(const frw_ctx *ctx, int logn, int encoding)
@@ -221,7 +222,7 @@ int frw_ntt_modq_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_pol
 }
 
 namespace {
-// Host-buffer driver shared by the two circuits.  Working memory comes from the context's arena (grow-only: a call after
+// Host-buffer driver shared by the three circuits.  Working memory comes from the context's arena (grow-only: a call after
 // the first allocates nothing).  Inputs travel through the arena's page-locked buffer, so the three polynomials of a
 // chunk are ONE host-to-device copy whatever memory the caller holds them in.  A batch that fits one chunk -- the
 // reference's own call pattern is one signature per generate_constraints -- runs on one stream: copy in, kernel, copies
@@ -229,10 +230,11 @@ namespace {
 // (5 MB per signature over PCIe), the compute stream already fills chunk k+1.  With output buffers from frw_host_alloc
 // (pinned) every copy out is a true asynchronous DMA; with pageable memory the runtime stages the copies itself and the
 // overlap degrades gracefully, the results are the same.
-int witness_host(frw_ctx *ctx, bool dual, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
+int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
                  const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance, int32_t *status, int strict)
 {
-    const bool compact = !dual && encoding == FRW_ENC_COMPACT;    // `witness` = compact buffer, `instance` unused
+    const bool dual = circuit == FRW_CIRCUIT_DUAL_NTT, schoolbook = circuit == FRW_CIRCUIT_SCHOOLBOOK;
+    const bool compact = circuit == FRW_CIRCUIT_NTT && encoding == FRW_ENC_COMPACT;    // `witness` = compact buffer, `instance` unused
     if (compact ? bad_common(ctx, logn, FRW_ENC_MONTGOMERY) : bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!sig || !pk || !hm || !witness || (!instance && !compact) || !status) return FRW_E_INVALID_ARG;
@@ -242,9 +244,11 @@ int witness_host(frw_ctx *ctx, bool dual, int logn, size_t batch, const uint16_t
     FRW_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)1 << logn;
     const size_t nb = logn == 9 ? 50 : 52;
-    const size_t wbytes = compact ? frw::compact_layout(logn).bytes : (dual ? 186 * n + 4 + nb : 153 * n + nb) * 32;
+    const size_t wbytes = compact ? frw::compact_layout(logn).bytes
+                                  : (schoolbook ? n * n + 99 * n + nb : dual ? 186 * n + 4 + nb : 153 * n + nb) * 32;
     const size_t ibytes = compact ? 0 : (2 * n + 1) * 32;
-    const size_t chunk = std::min<size_t>(batch, compact ? 2048 : 256);      // 2 x (<= 1.6 GB) of device witness
+    // 2 x (<= 1.6 GB) of device witness; a schoolbook witness is 10.0 | 36.8 MB, so a slot holds 128 | 32 of them (1.3 | 1.2 GB)
+    const size_t chunk = std::min<size_t>(batch, compact ? 2048 : schoolbook ? (logn == 9 ? 128 : 32) : 256);
     const int nbuf = batch > chunk ? 2 : 1;
     const size_t in_bytes = 3 * chunk * n * 2;                              // sig | pk | hm of one chunk, contiguous
     struct Slot { uint16_t *in; char *wit, *inst; int32_t *st; } slot[2];
@@ -271,7 +275,10 @@ int witness_host(frw_ctx *ctx, bool dual, int logn, size_t batch, const uint16_t
         for (int j = 0; j < 3; j++) memcpy(stage + (size_t)j * cnt * n, src[j] + lo * n, cnt * n * 2);
         FRW_HIP(hipMemcpyAsync(slot[b].in, stage, 3 * cnt * n * 2, hipMemcpyHostToDevice, A.compute));
         const uint16_t *d_sig = slot[b].in, *d_pk = d_sig + cnt * n, *d_hm = d_pk + cnt * n;
-        if (dual)
+        if (schoolbook)
+            FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, d_sig, d_pk, d_hm,
+                                                          (uint64_t *)slot[b].wit, (uint64_t *)slot[b].inst, slot[b].st, A.compute));
+        else if (dual)
             FRW_HIP(frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, d_sig, d_pk, d_hm,
                                                         (uint64_t *)slot[b].wit, (uint64_t *)slot[b].inst, slot[b].st, A.compute));
         else if (compact)
@@ -305,14 +312,14 @@ int frw_witness_ntt_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t 
                            const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance, int32_t *status,
                            int strict)
 {
-    return witness_host(ctx, false, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
+    return witness_host(ctx, FRW_CIRCUIT_NTT, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
 }
 
 int frw_witness_dual_ntt_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
                                 const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance,
                                 int32_t *status, int strict)
 {
-    return witness_host(ctx, true, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
+    return witness_host(ctx, FRW_CIRCUIT_DUAL_NTT, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
 }
 
 int frw_witness_dual_ntt_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
@@ -502,6 +509,46 @@ int frw_layout_dual(int logn, frw_layout_dual_t *out)
     out->num_instance = 2 * n + 1;
     out->num_constraints = 189 * n + 10 + nb;
     return FRW_OK;
+}
+
+int frw_layout_schoolbook(int logn, frw_layout_schoolbook_t *out)
+{
+    if (!out || (logn != 9 && logn != 10)) return FRW_E_INVALID_ARG;
+    const int n = 1 << logn, nb = logn == 9 ? 50 : 52;
+    const int len[FRW_NUM_SEGMENTS_SCHOOLBOOK] = {n, 28 * n, n * (n + 34), 36 * n, nb};
+    int off = 0;
+    out->logn = logn;
+    out->n = n;
+    for (int i = 0; i < FRW_NUM_SEGMENTS_SCHOOLBOOK; i++) {
+        out->seg_off[i] = off;
+        out->seg_len[i] = len[i];
+        off += len[i];
+    }
+    out->num_witness = off;
+    out->num_instance = 2 * n + 1;
+    out->num_constraints = n * n + 105 * n + nb + 2;
+    out->column_len = n + 34;
+    return FRW_OK;
+}
+
+int frw_witness_schoolbook_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
+                                      const uint16_t *d_hm, int encoding, uint64_t *d_witness, uint64_t *d_instance,
+                                      int32_t *d_status, void *stream)
+{
+    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;       // (no compact form of this circuit)
+    if (batch == 0) return FRW_OK;
+    if (!d_sig || !d_pk || !d_hm || !d_witness || !d_instance || !d_status) return FRW_E_INVALID_ARG;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig,
+                                                  d_pk, d_hm, d_witness, d_instance, d_status, (hipStream_t)stream));
+    return FRW_OK;
+}
+
+int frw_witness_schoolbook_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
+                                  const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance,
+                                  int32_t *status, int strict)
+{
+    return witness_host(ctx, FRW_CIRCUIT_SCHOOLBOOK, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
 }
 
 int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int encoding, uint64_t *witness,

@@ -24,6 +24,8 @@ struct Tables {
     uint16_t tw[1024];      // falcon-rust NTT_TABLE: 7^bitrev10(i) mod q   (misc.rs:72; script/ntt_param.sage:3-132)
     uint16_t itw[1024];     // 7^-bitrev10(i) mod q
     uint32_t ck[11][5];     // C_k = 2^k q^(k+1), 32-bit limbs (falcon_ntt.rs:31-39)
+    // the schoolbook circuit's two is_neq multipliers, q^-1 and (-q)^-1 in Fr, [FRW_ENC_CANONICAL | FRW_ENC_MONTGOMERY][8 x u32]
+    uint32_t sb_qinv[2][8], sb_nqinv[2][8];
 };
 
 // FRW_ENC_COMPACT: one signature = its non-boolean witness elements as plain integers -- the 11 N that fit 32 bits as
@@ -61,6 +63,8 @@ int record_hip_error(hipError_t e, const char *what);
 // the same message slot for a refusal that is not HIP's (printf-style): which query of a key, which point
 void record_error(const char *fmt, ...);
 void init_launch_config();
+// q^-1 and (-q)^-1 in Fr for Tables::sb_qinv / sb_nqinv (frw_r1cs.cpp, which has the field inversion): [canonical | Montgomery][8]
+void schoolbook_inverses(uint32_t qinv[2][8], uint32_t nqinv[2][8]);
 hipError_t launch_witness_ntt_verify_compact(const Tables *tab, int num_cu, int logn, size_t batch,
                                              const uint16_t *sig, const uint16_t *pk, const uint16_t *hm, void *compact,
                                              int32_t *status, hipStream_t st);
@@ -73,6 +77,10 @@ hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, in
 hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int logn, int enc,
                                           size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
                                           uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st);
+// one launch: signatures cut into 1 + N / 32 work items (everything but the columns | 32 columns each), strided over the grid
+hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int logn, int enc,
+                                            size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
+                                            uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st);
 hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, size_t batch, const uint16_t *poly,
                            uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st);
 hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,

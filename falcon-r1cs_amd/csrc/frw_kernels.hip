@@ -417,26 +417,29 @@ template <int BLK> struct TileShape;
 template <> struct TileShape<29> { static constexpr int P = 29, NPER = 2, KSTEP = 32, NVAL = 2, VFIRST = 0, ROW0 = 0; };   // mod_q block
 template <> struct TileShape<30> { static constexpr int P = 15, NPER = 4, KSTEP = 16, NVAL = 3, VFIRST = 0, ROW0 = 29; };  // pointwise block
 template <> struct TileShape<18> { static constexpr int P = 9, NPER = 4, KSTEP = 16, NVAL = 2, VFIRST = 16, ROW0 = 44; };  // l2 block
-constexpr int VTAB_ROWS = 53;
+template <> struct TileShape<28> { static constexpr int P = 14, NPER = 4, KSTEP = 16, NVAL = 1, VFIRST = 0, ROW0 = 53; };  // [v, ltq(v)] block (schoolbook circuit)
+constexpr int VTAB_ROWS = 53;                      // the three shapes of the NTT circuits; shape 28's rows are numbered behind them
 static_assert(TileShape<29>::P * TileShape<29>::NPER == 58 && TileShape<30>::P * TileShape<30>::NPER == 60 &&
-              TileShape<18>::P * TileShape<18>::NPER == 36, "a tile is 2 BLK stores");
+              TileShape<18>::P * TileShape<18>::NPER == 36 && TileShape<28>::P * TileShape<28>::NPER == 56, "a tile is 2 BLK stores");
 
 // vtab[row][lane] = LDS byte offset (relative to B_w) of the 16 bytes lane `lane` stores in store `row - ROW0` of a
 // period when the element's boolean is 0.  Filled once per workgroup (the kernels are persistent).
-__device__ __forceinline__ void init_vtab(uint16_t *vtab, int rows, int tid)
+__device__ __forceinline__ void init_vtab_rows(uint16_t *vtab, int row0, int rows, int tid)
 {
     for (int idx = tid; idx < rows * WAVE; idx += BLOCK) {
-        const int row = idx >> 6, lane = idx & 63;
+        const int row = row0 + (idx >> 6), lane = idx & 63;
         int blk, nval, vfirst, j;
         if (row < TileShape<30>::ROW0) { blk = 29; nval = 2; vfirst = 0; j = row; }
         else if (row < TileShape<18>::ROW0) { blk = 30; nval = 3; vfirst = 0; j = row - TileShape<30>::ROW0; }
-        else { blk = 18; nval = 2; vfirst = 16; j = row - TileShape<18>::ROW0; }
+        else if (row < TileShape<28>::ROW0) { blk = 18; nval = 2; vfirst = 16; j = row - TileShape<18>::ROW0; }
+        else { blk = 28; nval = 1; vfirst = 0; j = row - TileShape<28>::ROW0; }
         const int c = j * WAVE + lane, e = c >> 1, h = c & 1;
         const int k = e / blk, slot = e - k * blk - vfirst;
         vtab[idx] = (uint16_t)((unsigned)slot < (unsigned)nval ? slot * SLAB_SLOT + h * SLAB_HALF + slab_addr(k)
                                                                : h * SLAB_HALF + 256);
     }
 }
+__device__ __forceinline__ void init_vtab(uint16_t *vtab, int rows, int tid) { init_vtab_rows(vtab, 0, rows, tid); }
 
 // the wave's constants: 16 lanes write the four group constants of (slot 0 | 1, half 0 | 1): zero | this half of one
 template <int ENC>
@@ -542,7 +545,9 @@ __device__ __forceinline__ void emit_zeros(__amdgpu_buffer_rsrc_t rsrc, uint32_t
 }
 
 // a tile of 64 blocks of BLK elements; booleans in `mask` (bit pos = element pos, zeros at value positions)
-template <int BLK>
+// (ROWBASE: the first row of the shapes' common numbering that the workgroup's table holds -- a kernel that uses the later
+// shapes only keeps a table that starts there)
+template <int BLK, int ROWBASE = 0>
 __device__ __forceinline__ void emit_tile(__amdgpu_buffer_rsrc_t rsrc, uint32_t soff, uint32_t mask, const WaveCtx &w)
 {
     lds_fence();                           // the slab writes of all lanes have landed
@@ -562,7 +567,8 @@ __device__ __forceinline__ void emit_tile(__amdgpu_buffer_rsrc_t rsrc, uint32_t 
         }
     } else {
         using S = TileShape<BLK>;
-        const uint32_t trow = w.vtab + S::ROW0 * WAVE * 2;
+        static_assert(ROWBASE <= S::ROW0, "the table starts at or before this shape's rows");
+        const uint32_t trow = w.vtab + (S::ROW0 - ROWBASE) * WAVE * 2;
         uint32_t base = w.slab;
 #pragma unroll 1
         for (int per = 0; per < S::NPER; per++) {
@@ -1077,6 +1083,210 @@ __global__ __launch_bounds__(BLOCK) void witness_dual_ntt_verify_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
+// kernel: the schoolbook variant, FalconSchoolBookVerificationCircuit::generate_constraints
+// (circuits/falcon_schoolbook.rs:26-131, gadgets/arithmetics.rs:34-100).  Layout (units: field elements;
+// W = N^2 + 99 N + nb, frw_layout_schoolbook):
+//   B0 0          sig N                                                                        :45-58
+//   B1 N          N blocks [v[i], ltq(v[i]) 27]                                                :86-92
+//   B2 29N        N columns of N + 34: [t, c, prod_0 .. prod_{N-1}, ltq(c) 27, ne1, mult1, ne2, mult2, and]   :105-121
+//   B3 N^2+63N    l2_norm_var over v || sig: 2N blocks of 18                                   :126-130
+//   B4 N^2+99N    norm bound (50 | 52)                                                         :131
+// instance = [1, pk, hm] (coefficients).  Column i is the inner product of sig with b_j = pk[i-j] (j <= i) or
+// q - pk[N+i-j] (j > i, NOT reduced: pk = 0 gives q); sum_j sig[j] b_j = t q + c < 2^38, so c -- which is also
+// (hm[i] - v[i]) mod q -- and t come from one 64-bit sum per column and nothing is reduced N^2 times.  With
+// rhs = hm[i] + q - c the two is_eq gadgets and the or leave [0, 1, 1, (-q)^-1, 0] when hm[i] < c (v[i] = rhs) and
+// [1, q^-1, 0, 1, 0] otherwise (v[i] = rhs - q); the two inverses come from the host (Tables).
+//
+// 97 % of a column is integers below 2^28 with no boolean between them, so B2 does not go through the boolean bit
+// stream: the column range of a work item is ONE run of field elements (32 columns = (N + 34) / 2 tiles of 64 elements,
+// whatever the column boundaries), lane k of a tile works out which element it holds, encodes it (one CIOS round) and
+// the tile leaves through emit_values: two 1 KiB stores.  B0, B1, B3, B4 and the instance vector are work item 0 of a
+// signature, on the blocks of the NTT kernel; items 1 .. N/32 are the column ranges, and they need no NTT at all.
+// ------------------------------------------------------------------------------------------------
+constexpr int SB_COLS = 32;                       // columns of one work item: 32 (N + 34) elements are whole tiles
+
+template <int LOGN>
+struct alignas(16) SmemSchoolbook {
+    static constexpr int N = 1 << LOGN;
+    unsigned char slab[SLAB_BYTES];
+    uint16_t tw[N];
+    uint16_t sig[N], pk[N], hm[N], v[N];          // coefficient domain
+    uint16_t nsig[N], npk[N];                     // NTT domain (item 0 only)
+    static constexpr int VROW0 = TileShape<18>::ROW0;                  // the table holds the rows of shapes 18 and 28 only
+    uint16_t vtab[(TileShape<28>::ROW0 + TileShape<28>::P - VROW0) * WAVE];
+    uint32_t col_t[SB_COLS], col_c[SB_COLS];      // t and c of the item's columns
+    unsigned long long norm;
+    int bad;
+};
+
+template <int LOGN, int ENC>
+__global__ __launch_bounds__(BLOCK) void witness_schoolbook_verify_kernel(
+    const Tables *__restrict__ tab, size_t batch,
+    const uint16_t *__restrict__ g_sig, const uint16_t *__restrict__ g_pk, const uint16_t *__restrict__ g_hm,
+    v4u *__restrict__ g_wit, v4u *__restrict__ g_inst, int32_t *__restrict__ g_status)
+{
+    constexpr int N = 1 << LOGN;
+    constexpr int NB = LOGN == 9 ? 50 : 52;
+    constexpr int COL = N + 34;                                      // elements of one column
+    constexpr size_t W = (size_t)N * N + 99 * (size_t)N + NB;
+    constexpr size_t I = 2 * (size_t)N + 1;
+    constexpr int TILES = N / WAVE;
+    constexpr uint32_t TILE1 = WAVE * 32;
+    constexpr int IPS = N / SB_COLS + 1;                             // work items per signature
+    constexpr int RANGE_TILES = SB_COLS * COL / WAVE;                // tiles of one column range
+    static_assert(SB_COLS * COL % WAVE == 0 && SB_COLS % WAVES == 0, "a column range is whole tiles");
+    constexpr uint32_t B2 = 29 * N, B3 = N * N + 63 * N, B4 = N * N + 99 * N;
+    static_assert(W * 32 < 0xffffffffull, "offsets inside one witness fit 32 bits");
+    __shared__ SmemSchoolbook<LOGN> sm;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    WaveCtx wc;
+    wc.slab = (uint32_t)(uintptr_t)(FRW_LDS void *)sm.slab + wave * SLAB_WBLK;
+    wc.vtab = (uint32_t)(uintptr_t)(FRW_LDS void *)sm.vtab + lane * 2;
+    wc.lane = lane;
+    for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
+    constexpr int VROW0 = SmemSchoolbook<LOGN>::VROW0;
+    init_vtab_rows(sm.vtab, VROW0, TileShape<18>::P + TileShape<28>::P, tid);
+    init_slab_const<ENC>(wc.slab, lane);
+    constexpr uint32_t R[8] = FRW_R32;
+    const int half = lane & 1;
+    const v4u one = ENC == 0 ? (half ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0))
+                             : (half ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+
+    const size_t items = batch * IPS;
+    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const size_t s = item / IPS;
+        const int part = (int)(item - s * IPS);                      // 0: everything but B2; p >= 1: columns [32 (p - 1), 32 p)
+        v4u *wit = g_wit + s * W * 2;
+        v4u *inst = g_inst + s * I * 2;
+        if (tid == 0) { sm.norm = 0; sm.bad = 0; }
+        lds_barrier();
+        int bad = 0;
+        for (int j = tid; j < N; j += BLOCK) {
+            const uint32_t a = g_sig[s * N + j], b = g_pk[s * N + j], c = g_hm[s * N + j];
+            bad |= (a >= Q) | (b >= Q) | (c >= Q);
+            sm.sig[j] = (uint16_t)a; sm.pk[j] = (uint16_t)b; sm.hm[j] = (uint16_t)c;
+            sm.nsig[j] = (uint16_t)a; sm.npk[j] = (uint16_t)b; sm.v[j] = (uint16_t)c;
+        }
+        if (bad) sm.bad = 1;
+        lds_barrier();
+        if (sm.bad) {                                                // every item clears its own share
+            if (part == 0) {
+                if (tid == 0) g_status[s] = ST_COEFF_RANGE;
+                zero_fill(wit, (size_t)B2 * 2, tid);
+                zero_fill(wit + (size_t)B3 * 2, (W - B3) * 2, tid);
+                zero_fill(inst, I * 2, tid);
+            } else {
+                zero_fill(wit + ((size_t)B2 + (size_t)(part - 1) * SB_COLS * COL) * 2, (size_t)SB_COLS * COL * 2, tid);
+            }
+            lds_barrier();
+            continue;
+        }
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(wit, (uint32_t)(W * 32));
+        const __amdgpu_buffer_rsrc_t ri = make_rsrc(inst, (uint32_t)(I * 32));
+        uint32_t e8[8];
+
+        if (part == 0) {
+            // v = hm - sig * pk: one mod-q NTT product                                        falcon_schoolbook.rs:38-39
+            {
+                uint16_t *const polys[3] = {sm.nsig, sm.npk, sm.v};
+                ntt_modq_lds<LOGN, 3>(polys, sm.tw, tid);
+            }
+            for (int j = tid; j < N; j += BLOCK) {
+                uint32_t x = sm.v[j] + Q - mod_q_u32((uint32_t)sm.nsig[j] * sm.npk[j]);
+                sm.v[j] = (uint16_t)(x >= Q ? x - Q : x);
+            }
+            lds_barrier();
+            intt_modq_lds<LOGN>(sm.v, tab->itw, tid);
+            if (tid < 2) inst[tid] = one;                                                   // instance_assignment[0] = 1
+            for (int t = wave; t < TILES; t += WAVES) {
+                const int k = t * WAVE + lane;
+                encode_u32<ENC>(sm.pk[k], e8); slab_put(wc.slab, 0, lane, e8);              // :66-75
+                emit_values(ri, 32 + t * TILE1, wc);
+                encode_u32<ENC>(sm.hm[k], e8); slab_put(wc.slab, 0, lane, e8);              // :78-83
+                emit_values(ri, 32 + (TILES + t) * TILE1, wc);
+                encode_u32<ENC>(sm.sig[k], e8); slab_put(wc.slab, 0, lane, e8);             // B0 :45-58
+                emit_values(rw, t * TILE1, wc);
+                const uint32_t vk = sm.v[k];                                                // B1 :86-92
+                encode_u32<ENC>(vk, e8); slab_put(wc.slab, 0, lane, e8);
+                emit_tile<28, VROW0>(rw, (N + t * WAVE * 28) * 32, ltq_mask(vk) << 1, wc);
+            }
+            // B3 l2_norm_var over v || sig: [a0..a13, w0, w1, r, sq]                          :126-130
+            unsigned long long nrm = 0;
+            for (int t = wave; t < 2 * TILES; t += WAVES) {
+                const int k = t * WAVE + lane;
+                const uint32_t a = k < N ? sm.v[k] : sm.sig[k - N];
+                const uint32_t m = lt6144_mask(a);
+                const uint32_t r = (m >> 15) & 1u ? a : Q - a;
+                const uint32_t sq = r * r;
+                nrm += sq;
+                encode_u32<ENC>(r, e8);  slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(sq, e8); slab_put(wc.slab, 1, lane, e8);
+                emit_tile<18, VROW0>(rw, (B3 + t * WAVE * 18) * 32, m, wc);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor((unsigned long long)nrm, off, WAVE);
+            if (lane == 0) atomicAdd(&sm.norm, nrm);
+            lds_barrier();
+            if (wave == 0) {                                                                // B4 :131
+                const unsigned long long norm = sm.norm;
+                const unsigned long long nm = LOGN == 9 ? norm_mask_512(norm) : norm_mask_1024(norm);
+                v4u *o = wit + (size_t)B4 * 2;
+                for (int c = lane; c < NB * 2; c += WAVE) o[c] = (nm >> (c >> 1)) & 1ull ? one : mk4(0, 0, 0, 0);
+                if (lane == 0) g_status[s] = norm >= (LOGN == 9 ? 34034726ull : 70265242ull) ? ST_NORM_BOUND : ST_OK;
+            }
+        } else {
+            // ---- B2, columns [i0, i0 + 32): the integer sums first (arithmetics.rs:69-80), eight columns a wave
+            const int i0 = (part - 1) * SB_COLS;
+#pragma unroll 1
+            for (int cc = 0; cc < SB_COLS / WAVES; cc++) {
+                const int ci = wave * (SB_COLS / WAVES) + cc, i = i0 + ci;
+                unsigned long long acc = 0;
+                for (int j = lane; j < N; j += WAVE) {
+                    const uint32_t pkv = sm.pk[(i - j) & (N - 1)];               // j > i: index N + i - j
+                    const uint32_t b = j <= i ? pkv : Q - pkv;
+                    acc += (uint32_t)sm.sig[j] * b;
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor((unsigned long long)acc, off, WAVE);
+                if (lane == 0) {
+                    const unsigned long long tq = acc / Q;
+                    sm.col_t[ci] = (uint32_t)tq;                                 // < 2^25
+                    sm.col_c[ci] = (uint32_t)(acc - tq * Q);
+                }
+            }
+            lds_barrier();
+            const uint32_t range_off = (B2 + (uint32_t)i0 * COL) * 32;
+            for (int t = wave; t < RANGE_TILES; t += WAVES) {
+                const uint32_t e = (uint32_t)t * WAVE + lane;                    // element of the range
+                const uint32_t ci = e / COL, pos = e - ci * COL;
+                const int i = i0 + (int)ci;
+                const uint32_t c = sm.col_c[ci], h = sm.hm[i];
+                const uint32_t ge = h >= c ? 1u : 0u;                            // v[i] = rhs - q
+                const int j = (int)pos - 2;
+                const uint32_t pkv = sm.pk[(i - j) & (N - 1)];
+                const uint32_t b = j <= i ? pkv : Q - pkv;
+                uint32_t x = (uint32_t)sm.sig[j & (N - 1)] * b;                  // prod_j  arithmetics.rs:87-90
+                if (pos == 0) x = sm.col_t[ci];                                  // t_var   :83
+                if (pos == 1) x = c;                                             // c_var   :84
+                if (pos >= (uint32_t)N + 2) x = (ltq_mask(c) >> ((pos - (N + 2)) & 31u)) & 1u;    // :97
+                if (pos >= (uint32_t)N + 29) x = pos == (uint32_t)N + 29 ? ge : pos == (uint32_t)N + 31 ? ge ^ 1u : 0u;
+                encode_u32<ENC>(x, e8);
+                if (pos == (uint32_t)N + 30 || pos == (uint32_t)N + 32) {        // the multipliers of the two is_neq
+                    const bool unit = (pos == (uint32_t)N + 30) != (ge != 0);    // operands equal: multiplier one
+                    const uint32_t *inv = pos == (uint32_t)N + 30 ? tab->sb_qinv[ENC] : tab->sb_nqinv[ENC];
+#pragma unroll
+                    for (int k = 0; k < 8; k++) e8[k] = unit ? (ENC == 0 ? (k == 0 ? 1u : 0u) : R[k]) : inv[k];
+                }
+                slab_put(wc.slab, 0, lane, e8);
+                emit_values(rw, range_off + (uint32_t)t * TILE1, wc);
+            }
+        }
+        lds_barrier();                    // sm.norm, sm.bad and the column values are rewritten by the next item
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernel: NTTPolyVar::ntt_circuit alone (poly.rs:104-159): N mod_q blocks + the reduced NTT
 // ------------------------------------------------------------------------------------------------
 template <int LOGN>
@@ -1450,7 +1660,7 @@ hipError_t launch_write_stream(void *buf, size_t bytes, size_t slab_bytes, int n
 // striding over the batch.  Residency is asked from the runtime once per kernel instantiation.
 // Filled exactly once per process (std::call_once in init_launch_config, which every context creation calls before
 // any launch), read-only afterwards: contexts on several devices / threads share it safely.
-static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4];       // resident workgroups per CU, [(LOGN-9)*2 + ENC]
+static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4], g_occ_schoolbook[4];   // resident workgroups per CU, [(LOGN-9)*2 + ENC]
 static int g_occ_compact[2], g_occ_expand[2];                  // [LOGN - 9]
 static std::once_flag g_occ_once;
 
@@ -1503,6 +1713,8 @@ void init_launch_config()
 #undef FRW_QV
         FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 9, 0); FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 9, 1);
         FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 10, 0); FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 10, 1);
+        FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 9, 0); FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 9, 1);
+        FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 10, 0); FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 10, 1);
         FRW_Q(ntt_modq_kernel, g_occ_ntt, 9, 0); FRW_Q(ntt_modq_kernel, g_occ_ntt, 9, 1);
         FRW_Q(ntt_modq_kernel, g_occ_ntt, 10, 0); FRW_Q(ntt_modq_kernel, g_occ_ntt, 10, 1);
 #undef FRW_Q
@@ -1597,6 +1809,26 @@ hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int log
     do {                                                                                                            \
         const int grid = resident_grid(batch, num_cu, g_occ_dual[(LOGN - 9) * 2 + ENC]);                            \
         hipLaunchKernelGGL((witness_dual_ntt_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab,        \
+                           batch, sig, pk, hm, (v4u *)wit, (v4u *)inst, status);                                    \
+    } while (0)
+    if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
+    else if (logn == 9) FRW_LAUNCH(9, 1);
+    else if (enc == 0) FRW_LAUNCH(10, 0);
+    else FRW_LAUNCH(10, 1);
+#undef FRW_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int logn, int enc,
+                                            size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
+                                            uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st)
+{
+    if (batch == 0) return hipSuccess;
+    const size_t items = batch * (((size_t)1 << logn) / SB_COLS + 1);
+#define FRW_LAUNCH(LOGN, ENC)                                                                                       \
+    do {                                                                                                            \
+        const int grid = resident_grid(items, num_cu, g_occ_schoolbook[(LOGN - 9) * 2 + ENC]);                      \
+        hipLaunchKernelGGL((witness_schoolbook_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab,      \
                            batch, sig, pk, hm, (v4u *)wit, (v4u *)inst, status);                                    \
     } while (0)
     if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);

@@ -25,6 +25,7 @@
 #include "host/frw_host.hpp"
 
 namespace {
+bool known_circuit(int circuit) { return circuit == FRW_CIRCUIT_NTT || circuit == FRW_CIRCUIT_DUAL_NTT || circuit == FRW_CIRCUIT_SCHOOLBOOK; }
 frw::host::ConstraintMatrices build_matrices(int circuit, int logn)
 {
     using namespace frw::host;
@@ -33,7 +34,8 @@ frw::host::ConstraintMatrices build_matrices(int circuit, int logn)
     cs->set_setup_mode(true);
     Polynomial z{std::vector<uint16_t>(N, 0)};
     if (circuit == FRW_CIRCUIT_NTT) FalconNTTVerificationCircuit::build_circuit(z, z, z, logn).generate_constraints(cs);
-    else FalconDualNTTVerificationCircuit::build_circuit(z, z, z, logn).generate_constraints(cs);
+    else if (circuit == FRW_CIRCUIT_DUAL_NTT) FalconDualNTTVerificationCircuit::build_circuit(z, z, z, logn).generate_constraints(cs);
+    else FalconSchoolBookVerificationCircuit::build_circuit(z, z, z, logn).generate_constraints(cs);
     return cs->to_matrices();
 }
 }  // namespace
@@ -134,6 +136,18 @@ frw::SetupConst setup_const(const Fr &v)
 }
 }  // namespace
 
+void frw::schoolbook_inverses(uint32_t qinv[2][8], uint32_t nqinv[2][8])
+{
+    const Fr inv = inverse(Fr::from(frw::Q)), both[2] = {inv, -inv};
+    for (int k = 0; k < 2; k++) {
+        uint32_t(*dst)[8] = k ? nqinv : qinv;
+        uint64_t canon[4];
+        both[k].to_canonical(canon);
+        memcpy(dst[0], canon, 32);
+        memcpy(dst[1], both[k].l, 32);
+    }
+}
+
 extern "C" void frw_r1cs_free(frw_r1cs *r)
 {
     if (!r) return;
@@ -233,7 +247,7 @@ void upload_qap_tables(frw_r1cs *r, uint64_t num_constraints, uint64_t num_insta
 
 extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
 {
-    if (!out || (logn != 9 && logn != 10) || (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT)) return FRW_E_INVALID_ARG;
+    if (!out || (logn != 9 && logn != 10) || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FRW_E_NO_DEVICE;
@@ -652,7 +666,7 @@ extern "C" int frw_r1cs_check_dev(const frw_r1cs *r, size_t batch, const uint64_
 extern "C" int frw_r1cs_export(int circuit, int logn, const char *path, uint64_t *counts /* 6 x u64, may be NULL */)
 {
     using namespace frw::host;
-    if ((logn != 9 && logn != 10) || !path || (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT)) return FRW_E_INVALID_ARG;
+    if ((logn != 9 && logn != 10) || !path || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
     try {
         ConstraintMatrices m = build_matrices(circuit, logn);
         if (counts) {
@@ -1009,7 +1023,7 @@ extern "C" int frw_groth16_setup(int device, int circuit, int logn, const uint64
                                  frw_groth16_pk **pk_out, uint64_t *vk_out)
 {
     using namespace frw::host;
-    if (!toxic || !pk_out || (logn != 9 && logn != 10) || (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT)) return FRW_E_INVALID_ARG;
+    if (!toxic || !pk_out || (logn != 9 && logn != 10) || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
     *pk_out = nullptr;
     try {
         const ConstraintMatrices m = build_matrices(circuit, logn);

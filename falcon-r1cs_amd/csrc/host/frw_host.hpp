@@ -14,6 +14,7 @@
 //   gadgets/arithmetics.rs mod_q, add_mod                                          same names
 //   gadgets/poly.rs        PolyVar / NTTPolyVar ::alloc_vars, ::ntt_circuit        same names
 //   circuits/falcon_ntt.rs FalconNTTVerificationCircuit::{build_circuit, generate_constraints}   same names
+//   gadgets/arithmetics.rs inner_product_mod; circuits/falcon_schoolbook.rs FalconSchoolBookVerificationCircuit   same names
 //
 // Division of labour (BASELINE north_star): the host allocates variable indices and emits constraints exactly as
 // arkworks does; it NEVER computes a witness value.  Every `new_witness_variable` takes its value from the engine
@@ -371,6 +372,7 @@ public:
     }
 
     Boolean is_zero() const;       // FieldVar::is_zero = is_eq(&zero): AllocatedFp::is_neq, 2 witnesses / 3 constraints
+    Boolean is_eq(const FpVar &other) const;   // EqGadget::is_eq: AllocatedFp::is_neq(self, other).not()
     static FpVar from_boolean(const Boolean &b);
     static FpVar conditionally_select(const Boolean &cond, const FpVar &t, const FpVar &f);
 
@@ -526,6 +528,22 @@ inline Boolean FpVar::is_zero() const
     LinearCombination diff{{Fr::one(), zero}, {-Fr::one(), variable_}};
     cs_->enforce_constraint(diff, {{Fr::one(), mult}}, is_not_equal.lc());
     cs_->enforce_constraint(diff, is_not_equal.not_().lc(), {});
+    return is_not_equal.not_();
+}
+
+// FpVar::is_eq: constants fold; a Constant operand is wrapped (AllocatedFp::new_constant) and becomes `self` of
+// AllocatedFp::is_neq, whose witnesses and constraints are those of is_zero above with (self - other) as the difference.
+inline Boolean FpVar::is_eq(const FpVar &o) const
+{
+    if (is_constant() && o.is_constant()) return Boolean::constant(value_ == o.value_);
+    const FpVar &x = is_constant() || !o.is_constant() ? *this : o, &y = is_constant() || !o.is_constant() ? o : *this;
+    const ConstraintSystemRef &cs = x.is_constant() ? y.cs_ : x.cs_;
+    Variable xv = x.is_constant() ? cs->new_lc({{x.value_, VarOne()}}) : x.variable_;
+    Boolean is_not_equal = Boolean::new_witness_from_engine(cs, "is_eq is_not_equal");
+    Variable mult = cs->new_witness_variable(cs->pop_feed("is_eq multiplier"));
+    LinearCombination diff{{Fr::one(), xv}, {-Fr::one(), y.variable_}};
+    cs->enforce_constraint(diff, {{Fr::one(), mult}}, is_not_equal.lc());
+    cs->enforce_constraint(diff, is_not_equal.not_().lc(), {});
     return is_not_equal.not_();
 }
 
@@ -754,6 +772,34 @@ inline FpVar add_mod(const ConstraintSystemRef &cs, const FpVar &a, const FpVar 
     FpVar left = (a + b) - t_var * modulus_var;
     left.enforce_equal(c_var);
     enforce_less_than_q(cs, c_var);
+    return c_var;
+}
+
+// arithmetics.rs:34-100: witnesses [t, c], then the products a_i * b_i, then enforce_less_than_q(c).
+// There is no stand-alone engine request for this gadget (no frw_gadget kind): in prove mode its values must already be
+// in the feed, i.e. it runs inside FalconSchoolBookVerificationCircuit::generate_constraints, whose one engine call
+// (frw_witness_schoolbook_verify) produced them; called on its own it throws AssignmentMissing.
+// The reference accumulates `ab_var += a_i * b_i`, N nested symbolic LCs whose inlined form is the one flat sum built
+// here: to_matrices() sees the same row and stays linear in N.
+inline FpVar inner_product_mod(const ConstraintSystemRef &cs, const std::vector<FpVar> &a, const FpVar *b, size_t b_len, const FpVar &modulus_var)
+{
+    if (a.size() != b_len || a.empty()) throw std::invalid_argument("Invalid input length: a " + std::to_string(a.size()) + " vs b " + std::to_string(b_len));
+    if (!cs->is_in_setup_mode() && !cs->feed_remaining())
+        throw SynthesisError(SynthesisError::AssignmentMissing, "inner_product_mod: no engine value (only inside the schoolbook circuit; there is no CPU path)");
+    FpVar t_var = FpVar::new_witness_from_engine(cs, "inner_product_mod t");                  // :83
+    FpVar c_var = FpVar::new_witness_from_engine(cs, "inner_product_mod c");                  // :84
+    LinearCombination sum;
+    Fr sum_val = Fr::zero();
+    for (size_t i = 0; i < a.size(); i++) {                                                   // :87-90
+        FpVar prod = a[i] * b[i];
+        if (prod.is_constant()) throw std::logic_error("inner_product_mod: constant operands are not used on this path");
+        sum.push_back({Fr::one(), prod.variable()});
+        sum_val = sum_val + prod.value();
+    }
+    FpVar ab_var = FpVar::var(cs, sum_val, cs->new_lc(std::move(sum)));
+    FpVar left = ab_var - t_var * modulus_var;                                                // :92-93
+    left.enforce_equal(c_var);                                                                // :94
+    enforce_less_than_q(cs, c_var);                                                           // :97
     return c_var;
 }
 
@@ -1060,6 +1106,90 @@ public:
         for (const auto *part : {&v_vars.neg, &sig_poly_vars.pos, &sig_poly_vars.neg}) all.insert(all.end(), part->coeff().begin(), part->coeff().end());
         FpVar l2 = l2_norm_var_without_range_check(all);
         enforce_less_than_norm_bound(cs, l2, logn);                                                // :131
+        if (!cs->is_in_setup_mode() && cs->feed_remaining())
+            throw SynthesisError(SynthesisError::Engine, "engine produced more values than the circuit allocates");
+    }
+
+private:
+    Polynomial pk_, hm_, sig_;
+    int logn_ = 10;
+    const uint64_t *preset_wit_ = nullptr, *preset_inst_ = nullptr;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// circuits/falcon_schoolbook.rs  (the schoolbook variant: v = hm - sig * pk by N inner products over the coefficients)
+// ---------------------------------------------------------------------------------------------------------------
+class FalconSchoolBookVerificationCircuit {
+public:
+    // falcon_schoolbook.rs:15-17, from the coefficient vectors falcon-rust derives (:27-28,:35)
+    static FalconSchoolBookVerificationCircuit build_circuit(Polynomial pk, Polynomial hm, Polynomial sig, int logn)
+    {
+        const size_t N = (size_t)1 << logn;
+        if (pk.c.size() != N || hm.c.size() != N || sig.c.size() != N) throw std::invalid_argument("input length is not N");
+        FalconSchoolBookVerificationCircuit c;
+        c.pk_ = std::move(pk); c.hm_ = std::move(hm); c.sig_ = std::move(sig); c.logn_ = logn;
+        return c;
+    }
+    void use_engine_output(const uint64_t *witness_slice, const uint64_t *instance_slice) { preset_wit_ = witness_slice; preset_inst_ = instance_slice; }
+
+    // falcon_schoolbook.rs:26-131.  Prove mode: ONE engine call fills every witness value (v, the N^2 products, every t, c,
+    // boolean and multiplier); the structural pass allocates and constrains in the reference's order and pops them.
+    void generate_constraints(const ConstraintSystemRef &cs) const
+    {
+        const int logn = logn_;
+        const size_t N = (size_t)1 << logn;
+        if (!cs->is_in_setup_mode()) {
+            frw_layout_schoolbook_t L;
+            frw_layout_schoolbook(logn, &L);
+            std::vector<uint64_t> wit_buf, inst_buf;
+            const uint64_t *wit = preset_wit_;
+            if (!wit) {
+                detail::require_engine(cs, "FalconSchoolBookVerificationCircuit");
+                wit_buf.resize((size_t)L.num_witness * 4);
+                inst_buf.resize((size_t)L.num_instance * 4);
+                int32_t st = 0;
+                int rc = frw_witness_schoolbook_verify(cs->engine()->get(), logn, 1, sig_.c.data(), pk_.c.data(), hm_.c.data(),
+                                                       FRW_ENC_MONTGOMERY, wit_buf.data(), inst_buf.data(), &st, cs->strict() ? 1 : 0);
+                if (rc == FRW_E_RANGE) throw std::domain_error("Invalid input: range check failed (status " + std::to_string(st) + ")");
+                detail::check(rc, "frw_witness_schoolbook_verify");
+                if (st == FRW_ST_COEFF_RANGE) throw std::domain_error("Invalid input: coefficient >= MODULUS");
+                wit = wit_buf.data();
+            } else if (preset_inst_) {               // a slice of a batched engine call: it must be the instance of THESE public inputs
+                bool same = Fr::from_montgomery(preset_inst_) == Fr::one();
+                for (size_t i = 0; i < N && same; i++)
+                    same = Fr::from_montgomery(preset_inst_ + 4 * (1 + i)) == Fr::from(pk_.c[i]) && Fr::from_montgomery(preset_inst_ + 4 * (1 + N + i)) == Fr::from(hm_.c[i]);
+                if (!same) throw SynthesisError(SynthesisError::Engine, "use_engine_output: the instance slice is not [1, pk, hm] of this circuit");
+            }
+            cs->push_feed(wit, (size_t)L.num_witness);
+        }
+        const FpVar const_q_var = FpVar::new_constant(cs, Fr::from(MODULUS));                          // :30
+        PolyVar sig_poly_vars = PolyVar::alloc_vars(cs, sig_, AllocationMode::Witness);               // :45-58
+        std::vector<FpVar> pk_poly_vars, neg_pk_poly_vars, hm_vars, v_pos_vars;
+        for (uint16_t e : pk_.coeff()) {                                                              // :65-74
+            FpVar tmp = FpVar::new_input(cs, cs->is_in_setup_mode() ? Fr::one() : Fr::from(e));
+            neg_pk_poly_vars.push_back(const_q_var - tmp);
+            pk_poly_vars.push_back(tmp);
+        }
+        for (uint16_t e : hm_.coeff()) hm_vars.push_back(FpVar::new_input(cs, cs->is_in_setup_mode() ? Fr::one() : Fr::from(e)));   // :77-82
+        for (size_t i = 0; i < N; i++) {                                                              // :85-92 (v comes from the engine)
+            FpVar tmp = FpVar::new_witness_from_engine(cs, "v");
+            enforce_less_than_q(cs, tmp);
+            v_pos_vars.push_back(tmp);
+        }
+        std::vector<FpVar> buf = neg_pk_poly_vars;                                                    // :102-103
+        buf.insert(buf.end(), pk_poly_vars.begin(), pk_poly_vars.end());
+        std::reverse(buf.begin(), buf.end());
+        for (size_t i = 0; i < N; i++) {                                                              // :105-121
+            FpVar current_col = inner_product_mod(cs, sig_poly_vars.coeff(), buf.data() + (N - 1 - i), N, const_q_var);
+            FpVar rhs = hm_vars[i] + const_q_var - current_col;
+            Boolean first = rhs.is_eq(v_pos_vars[i]);
+            Boolean second = rhs.is_eq(v_pos_vars[i] + const_q_var);
+            first.or_(second).enforce_equal(Boolean::TRUE_());
+        }
+        std::vector<FpVar> both = v_pos_vars;                                                         // :126-130
+        both.insert(both.end(), sig_poly_vars.coeff().begin(), sig_poly_vars.coeff().end());
+        FpVar l2 = l2_norm_var(cs, both, const_q_var);
+        enforce_less_than_norm_bound(cs, l2, logn);                                                   // :131
         if (!cs->is_in_setup_mode() && cs->feed_remaining())
             throw SynthesisError(SynthesisError::Engine, "engine produced more values than the circuit allocates");
     }

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import CompactLayoutStruct, FrwError, LayoutDualStruct, LayoutStruct, check, load_library
+from ._lib import CompactLayoutStruct, FrwError, LayoutDualStruct, LayoutSchoolbookStruct, LayoutStruct, check, load_library
 
 ENC_CANONICAL, ENC_MONTGOMERY, ENC_COMPACT = 0, 1, 2
 ST_OK, ST_COEFF_RANGE, ST_NORM_BOUND, ST_DECODE = 0, 1, 2, 3
@@ -20,6 +20,7 @@ PK_LEN = {9: 897, 10: 1793}
 SIG_LEN = {9: 666, 10: 1280}
 E_RANGE = -5
 G_LESS_THAN_Q, G_MOD_Q, G_ADD_MOD, G_L2_ELEM, G_NORM_BOUND_512, G_NORM_BOUND_1024 = range(6)
+CIRCUIT_NTT, CIRCUIT_DUAL_NTT, CIRCUIT_SCHOOLBOOK = 0, 1, 2
 
 
 @dataclass(frozen=True)
@@ -44,6 +45,23 @@ def layout_dual(logn) -> Layout:
     s = LayoutDualStruct()
     check(load_library().frw_layout_dual(int(logn), C.byref(s)), "frw_layout_dual")
     return Layout(s.logn, s.n, s.num_witness, s.num_instance, s.num_constraints, tuple(s.seg_off), tuple(s.seg_len))
+
+
+@dataclass(frozen=True)
+class LayoutSchoolbook(Layout):
+    column_len: int = 0
+
+
+def layout_schoolbook(logn) -> LayoutSchoolbook:
+    """Layout of FalconSchoolBookVerificationCircuit's witness (frw_layout_schoolbook; 5 segments, columns of N + 34)."""
+    s = LayoutSchoolbookStruct()
+    check(load_library().frw_layout_schoolbook(int(logn), C.byref(s)), "frw_layout_schoolbook")
+    return LayoutSchoolbook(s.logn, s.n, s.num_witness, s.num_instance, s.num_constraints, tuple(s.seg_off), tuple(s.seg_len), s.column_len)
+
+
+def circuit_layout(circuit, logn) -> Layout:
+    """The layout of circuit 0 (NTT), 1 (dual NTT) or 2 (schoolbook)."""
+    return (layout, layout_dual, layout_schoolbook)[circuit](logn)
 
 
 @dataclass(frozen=True)
@@ -444,10 +462,18 @@ class WitnessEngine:
         """FalconDualNTTVerificationCircuit (falcon_dual_ntt.rs:26-132); same conventions as witness_ntt_verify."""
         return self.witness_ntt_verify(logn, sig, pk, hm, encoding, strict, dual=True)
 
+    def witness_schoolbook_verify(self, logn, sig, pk, hm, encoding=ENC_MONTGOMERY, strict=True):
+        """FalconSchoolBookVerificationCircuit (falcon_schoolbook.rs:26-131); same conventions as witness_ntt_verify
+        (instance = [1, pk, hm] coefficients; 10.0 / 36.8 MB of witness per signature)."""
+        return self._witness_host(CIRCUIT_SCHOOLBOOK, logn, sig, pk, hm, encoding, strict, False)
+
     def witness_ntt_verify(self, logn, sig, pk, hm, encoding=ENC_MONTGOMERY, strict=True, dual=False, pinned=False):
         """-> (witness u64[batch, W, 4], instance u64[batch, I, 4], status i32[batch]).
         pinned=True puts the outputs in page-locked memory so that the D2H copies overlap with the kernels."""
-        L = layout_dual(logn) if dual else layout(logn)
+        return self._witness_host(CIRCUIT_DUAL_NTT if dual else CIRCUIT_NTT, logn, sig, pk, hm, encoding, strict, pinned)
+
+    def _witness_host(self, circuit, logn, sig, pk, hm, encoding, strict, pinned):
+        L = circuit_layout(circuit, logn)
         sig, pk, hm = (_u16(a, L.n) for a in (sig, pk, hm))
         batch = sig.shape[0]
         if pk.shape[0] != batch or hm.shape[0] != batch:
@@ -462,7 +488,7 @@ class WitnessEngine:
             inst = np.zeros((batch, L.num_instance, 4), dtype=np.uint64)
             st = np.zeros(batch, dtype=np.int32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
-        fn = self._lib.frw_witness_dual_ntt_verify if dual else self._lib.frw_witness_ntt_verify
+        fn = (self._lib.frw_witness_ntt_verify, self._lib.frw_witness_dual_ntt_verify, self._lib.frw_witness_schoolbook_verify)[circuit]
         rc = fn(self._ctx, logn, batch, p(sig), p(pk), p(hm), encoding, p(wit), p(inst), p(st), 1 if strict else 0)
         if rc == E_RANGE:
             bad = np.nonzero(st)[0]
@@ -608,6 +634,13 @@ class WitnessEngine:
                                                         self._ptr(d_status), C.c_void_p(stream)),
               "frw_witness_dual_ntt_verify_dev")
 
+    def witness_schoolbook_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_wit, d_inst, d_status,
+                                      encoding=ENC_MONTGOMERY, stream=0):
+        check(self._lib.frw_witness_schoolbook_verify_dev(self._ctx, logn, batch, self._ptr(d_sig), self._ptr(d_pk),
+                                                          self._ptr(d_hm), encoding, self._ptr(d_wit), self._ptr(d_inst),
+                                                          self._ptr(d_status), C.c_void_p(stream)),
+              "frw_witness_schoolbook_verify_dev")
+
     def ntt_modq_dev(self, logn, batch, d_poly, d_wit, d_ntt, d_status, encoding=ENC_MONTGOMERY, stream=0):
         check(self._lib.frw_ntt_modq_dev(self._ctx, logn, batch, self._ptr(d_poly), encoding, self._ptr(d_wit),
                                          self._ptr(d_ntt), self._ptr(d_status), C.c_void_p(stream)),
@@ -618,7 +651,7 @@ class WitnessEngine:
               "frw_diag_write_stream_dev")
 
     def r1cs_load(self, circuit, logn):
-        """Device-resident A/B/C of circuit 0 (NTT) / 1 (dual NTT) for r1cs_check_dev; free with r1cs_free."""
+        """Device-resident A/B/C of circuit 0 (NTT) / 1 (dual NTT) / 2 (schoolbook) for r1cs_check_dev; free with r1cs_free."""
         h = C.c_void_p()
         check(self._lib.frw_r1cs_load(self.device, circuit, logn, C.byref(h)), "frw_r1cs_load")
         return h
@@ -847,7 +880,7 @@ class WitnessEngine:
     def groth16_setup(self, circuit, logn, alpha, beta, gamma, delta, t):
         """generate_parameters with the given toxic waste (Python integers) -> (proving-key handle, verifying key dict of uint64 arrays)."""
         tox = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in (alpha, beta, gamma, delta, t)), dtype=np.uint64).copy()
-        L = layout_dual(logn) if circuit else layout(logn)
+        L = circuit_layout(circuit, logn)
         vk = np.zeros(84 + 12 * L.num_instance, dtype=np.uint64)
         h = C.c_void_p()
         check(self._lib.frw_groth16_setup(self.device, circuit, logn, tox.ctypes.data_as(C.c_void_p), C.byref(h),

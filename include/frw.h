@@ -216,6 +216,37 @@ int frw_witness_dual_ntt_verify(frw_ctx *ctx, int logn, size_t batch,
                                 int encoding, uint64_t *witness, uint64_t *instance,
                                 int32_t *status, int strict);
 
+/* ---- the schoolbook variant: FalconSchoolBookVerificationCircuit (circuits/falcon_schoolbook.rs:26-131) --------
+ * Same statement over the COEFFICIENTS: instance = [1, pk[0..N), hm[0..N)] (no NTT values), and v = hm - sig * pk is
+ * proved by N inner products mod q (gadgets/arithmetics.rs:34-100), one per output coefficient.
+ * W = N^2 + 99 N + {50|52}, I = 2 N + 1, C = N^2 + 105 N + {52|54}.  Segments (allocation order):
+ *   0 sig N
+ *   1 N blocks [v[i], enforce_less_than_q(v[i]) 27]
+ *   2 N columns of column_len = N + 34: [t, c, prod_0 .. prod_{N-1}, enforce_less_than_q(c) 27, ne1, mult1, ne2, mult2, and]
+ *     prod_j = sig[j] * b_j with b_j = pk[i-j] (j <= i) or q - pk[N+i-j] (j > i, not reduced), sum_j prod_j = t q + c; the
+ *     tail is the two is_eq gadgets and the or of rhs = hm[i] + q - c against v[i] and v[i] + q (mult = AllocatedFp::is_neq's
+ *     multiplier: the inverse of the difference, or one where the operands are equal)
+ *   3 l2_norm_var over v || sig, 2N blocks of 18 | 4 norm bound
+ * 10.0 MB per Falcon-512 signature, 36.8 MB per Falcon-1024 signature.  Encodings FRW_ENC_CANONICAL and
+ * FRW_ENC_MONTGOMERY (FRW_ENC_COMPACT: FRW_E_INVALID_ARG); statuses, `strict` and every other convention as for
+ * frw_witness_dual_ntt_verify.  The _dev form is one kernel launch (stream-capture safe). */
+#define FRW_NUM_SEGMENTS_SCHOOLBOOK 5
+typedef struct frw_layout_schoolbook {
+    int32_t logn, n, num_witness, num_instance, num_constraints, column_len;
+    int32_t seg_off[FRW_NUM_SEGMENTS_SCHOOLBOOK];
+    int32_t seg_len[FRW_NUM_SEGMENTS_SCHOOLBOOK];
+} frw_layout_schoolbook_t;
+
+int frw_layout_schoolbook(int logn, frw_layout_schoolbook_t *out);
+int frw_witness_schoolbook_verify_dev(frw_ctx *ctx, int logn, size_t batch,
+                                      const uint16_t *d_sig, const uint16_t *d_pk, const uint16_t *d_hm,
+                                      int encoding, uint64_t *d_witness, uint64_t *d_instance,
+                                      int32_t *d_status, void *stream);
+int frw_witness_schoolbook_verify(frw_ctx *ctx, int logn, size_t batch,
+                                  const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
+                                  int encoding, uint64_t *witness, uint64_t *instance,
+                                  int32_t *status, int strict);
+
 /* ---- R1CS matrix export (structure only; host, no GPU) --------------------------------------------------------
  * What a prover ingests after the hot path (examples/pok_sig.rs:30-32: Groth16 setup/prove call cs.to_matrices()):
  * A, B, C of the chosen circuit with every symbolic linear combination inlined.  Column j < I is instance variable
@@ -224,6 +255,7 @@ int frw_witness_dual_ntt_verify(frw_ctx *ctx, int logn, size_t batch,
  * u32 col[nnz], u64 value[nnz][4] (canonical little-endian).  counts (optional) receives the six header words. */
 #define FRW_CIRCUIT_NTT       0   /* FalconNTTVerificationCircuit      circuits/falcon_ntt.rs      */
 #define FRW_CIRCUIT_DUAL_NTT  1   /* FalconDualNTTVerificationCircuit  circuits/falcon_dual_ntt.rs */
+#define FRW_CIRCUIT_SCHOOLBOOK 2  /* FalconSchoolBookVerificationCircuit circuits/falcon_schoolbook.rs */
 int frw_r1cs_export(int circuit, int logn, const char *path, uint64_t *counts);
 
 /* Batch satisfaction check on the device: the reference's `assert!(cs.is_satisfied())` (falcon_ntt.rs:159) for every

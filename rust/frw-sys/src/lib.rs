@@ -22,6 +22,7 @@ pub const FRW_ST_DECODE: i32 = 3;
 
 pub const FRW_CIRCUIT_NTT: c_int = 0;
 pub const FRW_CIRCUIT_DUAL_NTT: c_int = 1;
+pub const FRW_CIRCUIT_SCHOOLBOOK: c_int = 2;
 pub const FRW_NONCE_LEN: usize = 40;
 
 #[repr(C)]
@@ -34,6 +35,19 @@ pub struct frw_layout_t {
     pub num_constraints: i32,
     pub seg_off: [i32; 8],
     pub seg_len: [i32; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_layout_schoolbook_t {
+    pub logn: i32,
+    pub n: i32,
+    pub num_witness: i32,
+    pub num_instance: i32,
+    pub num_constraints: i32,
+    pub column_len: i32,
+    pub seg_off: [i32; 5],
+    pub seg_len: [i32; 5],
 }
 
 #[repr(C)]
@@ -217,6 +231,13 @@ extern "C" {
     pub fn frw_witness_dual_ntt_verify(ctx: *mut frw_ctx, logn: c_int, batch: usize, sig: *const u16, pk: *const u16,
                                        hm: *const u16, encoding: c_int, witness: *mut u64, instance: *mut u64,
                                        status: *mut i32, strict: c_int) -> c_int;
+    pub fn frw_layout_schoolbook(logn: c_int, out: *mut frw_layout_schoolbook_t) -> c_int;
+    pub fn frw_witness_schoolbook_verify_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_sig: *const u16,
+                                             d_pk: *const u16, d_hm: *const u16, encoding: c_int, d_witness: *mut u64,
+                                             d_instance: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn frw_witness_schoolbook_verify(ctx: *mut frw_ctx, logn: c_int, batch: usize, sig: *const u16, pk: *const u16,
+                                         hm: *const u16, encoding: c_int, witness: *mut u64, instance: *mut u64,
+                                         status: *mut i32, strict: c_int) -> c_int;
     pub fn frw_r1cs_export(circuit: c_int, logn: c_int, path: *const c_char, counts: *mut u64) -> c_int;
     pub fn frw_r1cs_load(device: c_int, circuit: c_int, logn: c_int, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_free(r: *mut frw_r1cs);

@@ -698,6 +698,171 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
     return FRW_OK;
 }
 
+// ---- the verifier's statement: instance_assignment from (pk, hm), or from the key's and the message's bytes; no signature -------------
+namespace {
+bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding)
+{
+    return bad_common(ctx, logn, encoding) ||
+           (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT && circuit != FRW_CIRCUIT_SCHOOLBOOK);
+}
+// the schoolbook circuit's public inputs are the coefficients themselves (falcon_schoolbook.rs:66-83), the NTT circuits' their transforms
+int statement_form(int circuit) { return circuit == FRW_CIRCUIT_SCHOOLBOOK ? 1 : 0; }
+constexpr size_t STATEMENT_CHUNK = 4096;          // statements of one pass of the host-buffer forms: 270 MB of Falcon-1024 instance vectors
+}  // namespace
+
+int frw_statement_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *d_pk, const uint16_t *d_hm, int encoding,
+                      uint64_t *d_instance, int32_t *d_status, void *stream)
+{
+    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    if (!d_pk || !d_hm || !d_instance || !d_status) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, batch, d_pk, d_hm, d_instance,
+                                  nullptr, 1, nullptr, d_status, nullptr, (hipStream_t)stream));
+    return FRW_OK;
+}
+
+size_t frw_statement_workspace_bytes(int logn, size_t batch)
+{
+    if (logn != 9 && logn != 10) return 0;
+    return frw::statement_layout(nullptr, logn, batch).bytes;
+}
+
+int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *d_pk_bytes, const uint8_t *d_nonces,
+                                 const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding, uint64_t *d_instance, int32_t *d_status,
+                                 void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    if (!d_pk_bytes || !d_nonces || !d_msgs || !d_msg_off || !d_instance || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
+    if (((uintptr_t)d_workspace & 15) || workspace_bytes < frw_statement_workspace_bytes(logn, batch)) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    const frw::StatementBufs ws = frw::statement_layout(d_workspace, logn, batch);
+    hipStream_t st = (hipStream_t)stream;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(frw::launch_decode_public_keys(logn, batch, d_pk_bytes, ws.pk, ws.decode_status, st));
+    FRW_HIP(frw::launch_hash_to_point(logn, batch, d_nonces, d_msgs, d_msg_off, ws.hm, st));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, batch, ws.pk, ws.hm, d_instance,
+                                  nullptr, 1, ws.decode_status, d_status, nullptr, st));
+    return FRW_OK;
+}
+
+int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *pk, const uint16_t *hm, int encoding,
+                  uint64_t *instance, int32_t *status, int strict)
+{
+    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    if (!pk || !hm || !instance || !status) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    frw::HostArena &A = ctx->arena;
+    std::lock_guard<std::mutex> lock(A.mu);
+    frw::DrainOnExit drain(A);
+    FRW_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)1 << logn, ibytes = (2 * n + 1) * 32, chunk = std::min(batch, STATEMENT_CHUNK);
+    frw::Carve c(nullptr);
+    const size_t o_in = c.off;   c.take(2 * chunk * n * 2);
+    const size_t o_inst = c.off; c.take(chunk * ibytes);
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    FRW_HIP(A.reserve_device(0, c.off));
+    FRW_HIP(A.reserve_pinned(2 * chunk * n * 2));
+    char *d = (char *)A.d_slot[0];
+    uint16_t *stage = (uint16_t *)A.h_pin, *d_in = (uint16_t *)(d + o_in);
+    hipStream_t st = A.compute;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = std::min(chunk, batch - lo);
+        memcpy(stage, pk + lo * n, cnt * n * 2);
+        memcpy(stage + cnt * n, hm + lo * n, cnt * n * 2);
+        FRW_HIP(hipMemcpyAsync(d_in, stage, 2 * cnt * n * 2, hipMemcpyHostToDevice, st));
+        FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, d_in, d_in + cnt * n,
+                                      (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st));
+        FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
+    }
+    drain.settled = true;
+    bool any_bad = false;
+    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
+    return strict && any_bad ? FRW_E_RANGE : FRW_OK;
+}
+
+int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *nonces,
+                             const uint8_t *msgs, const uint64_t *msg_off, int encoding, uint64_t *instance, int32_t *status, int strict)
+{
+    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    if (!pk_bytes || !nonces || !msg_off || !instance || !status) return FRW_E_INVALID_ARG;
+    for (size_t i = 0; i < batch; i++)
+        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (batch && !msgs && msg_off[batch] != msg_off[0]) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    frw::HostArena &A = ctx->arena;
+    std::lock_guard<std::mutex> lock(A.mu);
+    frw::DrainOnExit drain(A);
+    FRW_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)1 << logn, ibytes = (2 * n + 1) * 32, pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, STATEMENT_CHUNK);
+    size_t max_msg = 1;                                                   // the longest pass's message bytes
+    for (size_t lo = 0; lo < batch; lo += chunk)
+        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
+    // the staged inputs' layout == their device layout: ONE copy in per pass
+    frw::Carve hs(nullptr);
+    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
+    const size_t o_non = hs.off; hs.take(chunk * FRW_NONCE_LEN);
+    const size_t o_msgs = hs.off; hs.take(max_msg);
+    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
+    const size_t in_total = hs.off;
+    frw::Carve c(nullptr);
+    c.take(in_total);
+    const size_t o_ws = c.off;   c.take(frw_statement_workspace_bytes(logn, chunk));
+    const size_t o_inst = c.off; c.take(chunk * ibytes);
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    FRW_HIP(A.reserve_device(0, c.off));
+    FRW_HIP(A.reserve_pinned(in_total));
+    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
+    hipStream_t st = A.compute;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = std::min(chunk, batch - lo);
+        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
+        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
+        memcpy(h + o_non, nonces + lo * FRW_NONCE_LEN, cnt * FRW_NONCE_LEN);
+        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
+        uint64_t *off = (uint64_t *)(h + o_off);
+        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
+        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
+        const frw::StatementBufs ws = frw::statement_layout(d + o_ws, logn, cnt);
+        FRW_HIP(frw::launch_decode_public_keys(logn, cnt, (const uint8_t *)(d + o_pkb), ws.pk, ws.decode_status, st));
+        FRW_HIP(frw::launch_hash_to_point(logn, cnt, (const uint8_t *)(d + o_non), (const uint8_t *)(d + o_msgs),
+                                          (const uint64_t *)(d + o_off), ws.hm, st));
+        FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, ws.pk, ws.hm,
+                                      (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st));
+        FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipStreamSynchronize(st));
+    }
+    drain.settled = true;
+    bool any_bad = false;
+    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
+    return strict && any_bad ? FRW_E_RANGE : FRW_OK;
+}
+
+int frw_aggregate_statement_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint16_t *d_pk_512, const uint16_t *d_hm_512,
+                                const uint16_t *d_pk_1024, const uint16_t *d_hm_1024, int encoding, uint64_t *d_instance,
+                                int32_t *d_status, void *stream)
+{
+    int device = -1;
+    const frw::R1csAgg *agg = frw::r1cs_aggregate(aggregate, &device);
+    if (!agg || bad_common(ctx, 10, encoding) || !d_instance || !d_status || device != ctx->device) return FRW_E_INVALID_ARG;
+    const uint16_t *pk[2] = {d_pk_512, d_pk_1024}, *hm[2] = {d_hm_512, d_hm_1024};
+    for (int g = 0; g < 2; g++)
+        if (agg->set[g].count && (!pk[g] || !hm[g])) return FRW_E_INVALID_ARG;
+    FRW_HIP(hipSetDevice(ctx->device));
+    bool first = true;                  // one launch per parameter set; the first one writes the aggregate's constant
+    for (int g = 0; g < 2; g++) {
+        const frw::R1csAggSet &set = agg->set[g];
+        if (!set.count) continue;
+        FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, 9 + g, 0, encoding, set.count, pk[g], hm[g], d_instance, set.offs,
+                                      first ? 2 : 0, nullptr, d_status, set.stmt, (hipStream_t)stream));
+        first = false;
+    }
+    return FRW_OK;
+}
+
 int frw_gadget_block_len(int kind)
 {
     static const int len[6] = {27, 29, 29, 18, 50, 52};

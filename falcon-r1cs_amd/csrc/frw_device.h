@@ -6,6 +6,7 @@
 
 struct frw_msm;
 struct frw_groth16_pk;
+struct frw_r1cs;
 
 namespace frw {
 
@@ -83,6 +84,13 @@ hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int l
                                             uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st);
 hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, size_t batch, const uint16_t *poly,
                            uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st);
+// the verifier's statement (statement_kernel): form 0 = [1, NTT(pk), NTT(hm)], 1 = [1, pk, hm].  offs null: statement s at element
+// s (2 N + 1) of `out`; else at 1 + offs[3 s + 1] (R1csAggSet::offs).  lead 1: every statement writes its own leading one; 0: none; 2:
+// none, and the launch writes the aggregate's one constant at element 0.  pre (may be null): statuses that refuse a statement before its
+// coefficients are looked at.  status_index (may be null): where statement s's status word goes.
+hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
+                            const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
+                            int32_t *status, const uint32_t *status_index, hipStream_t st);
 hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,
                          int32_t *status, hipStream_t st);
 hipError_t launch_hash_to_point(int logn, size_t batch, const uint8_t *nonces, const uint8_t *msgs, const uint64_t *msg_off,
@@ -175,6 +183,7 @@ struct R1csAggSet {
     const R1csDev *base;
     uint32_t count;
     const uint64_t *offs;       // device memory, [count][3]: R1csView::offs
+    const uint32_t *stmt;       // device memory, [count]: the statements' indices in the aggregate (frw_aggregate_statement_dev's statuses)
 };
 struct R1csAgg {
     uint32_t num_statements;
@@ -182,6 +191,8 @@ struct R1csAgg {
     const R1csAggRun *runs;     // host memory
     R1csAggSet set[2];          // Falcon-512, Falcon-1024 (count 0: none)
 };
+// an aggregate handle's description and device (frw_r1cs.cpp); null for a per-signature handle
+const R1csAgg *r1cs_aggregate(const ::frw_r1cs *r, int *device);
 size_t r1cs_check_scratch_bytes(const R1csDev &r, size_t batch, bool with_abc);
 hipError_t launch_r1cs_check(const R1csDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance,
                              uint32_t *num_unsatisfied, uint64_t *abc, hipStream_t st, void *scratch = nullptr);

@@ -1287,6 +1287,99 @@ __global__ __launch_bounds__(BLOCK) void witness_schoolbook_verify_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
+// kernel: the verifier's statement, instance_assignment without a signature (examples/pok_sig.rs:33-45: pk_ntt and hm_ntt
+// lifted into Fr; the witness kernels above write the same 2 N + 1 elements to g_inst, but need sig and 5 - 37 MB of
+// witness to get there).  FORM 0: [1, NTT(pk), NTT(hm)] (the NTT and dual circuits); FORM 1: [1, pk, hm] (the schoolbook
+// circuit, no transform).  Work item 2 s + p is polynomial p (0 = pk, 1 = hm) of statement s: one mod-q NTT in LDS and N
+// one-element blocks out through the wave's slab and emit_values, as the instance part of the witness kernels.  Both
+// items of a statement check both polynomials, so they reach the same verdict; the pk item owns the leading one and the
+// status word.
+//   destination of statement s   element off = offs ? 1 + offs[3 s + 1] : s (2 N + 1) of g_out.  lead = 1: the statement's
+//                                own one at off and its 2 N values behind it; lead = 0 (an aggregate's R1csAggSet::offs):
+//                                the values at off; lead = 2: as 0, and item 0 writes the aggregate's ONE constant at
+//                                element 0 of g_out whatever its verdict (one launch per parameter set, one of them does)
+//   pre                          (may be null) a non-zero word refuses statement s with that status (FRW_ST_DECODE of the
+//                                key decoder) before its coefficients are looked at
+//   sidx                         (may be null) where statement s's status word goes; null: g_status[s]
+// A refused statement's slot is zeros, its own leading one included.
+// ------------------------------------------------------------------------------------------------
+template <int LOGN>
+struct alignas(16) SmemStatement {
+    static constexpr int N = 1 << LOGN;
+    unsigned char slab[SLAB_SLOT];               // value slot 0 of the four waves: every element is a value
+    uint16_t tw[N];
+    uint16_t poly[N];
+    int bad;
+};
+
+template <int LOGN, int FORM, int ENC>
+__global__ __launch_bounds__(BLOCK) void statement_kernel(
+    const Tables *__restrict__ tab, size_t batch, const uint16_t *__restrict__ g_pk, const uint16_t *__restrict__ g_hm,
+    v4u *__restrict__ g_out, const uint64_t *__restrict__ offs, int lead, const int32_t *__restrict__ pre,
+    int32_t *__restrict__ g_status, const uint32_t *__restrict__ sidx)
+{
+    constexpr int N = 1 << LOGN;
+    constexpr size_t I = 2 * (size_t)N + 1;
+    constexpr int TILES = N / WAVE;
+    constexpr uint32_t TILE1 = WAVE * 32;
+    __shared__ SmemStatement<LOGN> sm;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    WaveCtx wc;
+    wc.slab = (uint32_t)(uintptr_t)(FRW_LDS void *)sm.slab + wave * SLAB_WBLK;
+    wc.vtab = 0;                                 // no address table: emit_values reads the slab directly
+    wc.lane = lane;
+    if constexpr (FORM == 0)
+        for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
+    constexpr uint32_t R[8] = FRW_R32;
+    const v4u one = ENC == 0 ? (tid & 1 ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0))
+                             : (tid & 1 ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+
+    const size_t items = batch * 2;
+    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const size_t s = item >> 1;
+        const int p = (int)(item & 1);
+        const size_t off = offs ? 1 + (size_t)offs[3 * s + 1] : s * I;
+        v4u *const slot = g_out + off * 2;                               // the statement's (own one and) 2 N values
+        v4u *const dst = slot + (size_t)((lead == 1) + p * N) * 2;              // this polynomial's N elements
+        if (tid == 0) sm.bad = pre ? pre[s] : 0;
+        lds_barrier();
+        int bad = 0;
+        for (int j = tid; j < N; j += BLOCK) {
+            const uint32_t b = g_pk[s * N + j], c = g_hm[s * N + j];
+            bad |= (b >= Q) | (c >= Q);
+            sm.poly[j] = (uint16_t)(p ? c : b);
+        }
+        if (bad) atomicCAS(&sm.bad, 0, ST_COEFF_RANGE);                  // (a status the caller passed in stands)
+        lds_barrier();
+        const int verdict = sm.bad;                                     // uniform across the workgroup
+        if (p == 0) {
+            if (tid == 0) g_status[sidx ? sidx[s] : s] = verdict;
+            if (tid < 2) {
+                if (lead == 1) slot[tid] = verdict ? mk4(0, 0, 0, 0) : one;
+                else if (lead == 2 && item == 0) g_out[tid] = one;       // the aggregate's one constant
+            }
+        }
+        if (verdict) {
+            zero_fill(dst, (size_t)N * 2, tid);
+            lds_barrier();                  // every wave has read sm.bad before thread 0 rewrites it for the next item
+            continue;
+        }
+        if constexpr (FORM == 0) {
+            uint16_t *const polys[1] = {sm.poly};
+            ntt_modq_lds<LOGN, 1>(polys, sm.tw, tid);
+        }
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(dst, (uint32_t)(N * 32));
+        uint32_t e8[8];
+        for (int t = wave; t < TILES; t += WAVES) {
+            encode_u32<ENC>(sm.poly[t * WAVE + lane], e8); slab_put(wc.slab, 0, lane, e8);
+            emit_values(ro, t * TILE1, wc);
+        }
+        lds_barrier();                      // sm.poly and sm.bad are rewritten by the next item
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernel: NTTPolyVar::ntt_circuit alone (poly.rs:104-159): N mod_q blocks + the reduced NTT
 // ------------------------------------------------------------------------------------------------
 template <int LOGN>
@@ -1662,6 +1755,7 @@ hipError_t launch_write_stream(void *buf, size_t bytes, size_t slab_bytes, int n
 // any launch), read-only afterwards: contexts on several devices / threads share it safely.
 static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4], g_occ_schoolbook[4];   // resident workgroups per CU, [(LOGN-9)*2 + ENC]
 static int g_occ_compact[2], g_occ_expand[2];                  // [LOGN - 9]
+static int g_occ_statement[8];                                 // [(LOGN - 9) * 4 + FORM * 2 + ENC]
 static std::once_flag g_occ_once;
 
 template <typename K>
@@ -1722,6 +1816,10 @@ void init_launch_config()
         query_residency(witness_ntt_verify_kernel<10, 2>, g_occ_compact[1]);
         query_residency(expand_kernel<9>, g_occ_expand[0]);
         query_residency(expand_kernel<10>, g_occ_expand[1]);
+#define FRW_QS(LOGN, FORM, ENC) query_residency(statement_kernel<LOGN, FORM, ENC>, g_occ_statement[(LOGN - 9) * 4 + FORM * 2 + ENC])
+        FRW_QS(9, 0, 0); FRW_QS(9, 0, 1); FRW_QS(9, 1, 0); FRW_QS(9, 1, 1);
+        FRW_QS(10, 0, 0); FRW_QS(10, 0, 1); FRW_QS(10, 1, 0); FRW_QS(10, 1, 1);
+#undef FRW_QS
     });
 }
 
@@ -1835,6 +1933,31 @@ hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int l
     else if (logn == 9) FRW_LAUNCH(9, 1);
     else if (enc == 0) FRW_LAUNCH(10, 0);
     else FRW_LAUNCH(10, 1);
+#undef FRW_LAUNCH
+    return hipGetLastError();
+}
+
+// one launch: 2 x batch work items (statement, polynomial) strided over the resident grid
+hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
+                            const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
+                            int32_t *status, const uint32_t *status_index, hipStream_t st)
+{
+    if (batch == 0) return hipSuccess;
+    const int grid = resident_grid(batch * 2, num_cu, g_occ_statement[(logn - 9) * 4 + form * 2 + enc]);
+#define FRW_LAUNCH(LOGN, FORM, ENC)                                                                                       \
+    hipLaunchKernelGGL((statement_kernel<LOGN, FORM, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, pk, hm, (v4u *)out, \
+                       offs, lead, pre, status, status_index)
+    switch ((logn - 9) * 4 + form * 2 + enc) {
+    case 0: FRW_LAUNCH(9, 0, 0); break;
+    case 1: FRW_LAUNCH(9, 0, 1); break;
+    case 2: FRW_LAUNCH(9, 1, 0); break;
+    case 3: FRW_LAUNCH(9, 1, 1); break;
+    case 4: FRW_LAUNCH(10, 0, 0); break;
+    case 5: FRW_LAUNCH(10, 0, 1); break;
+    case 6: FRW_LAUNCH(10, 1, 0); break;
+    case 7: FRW_LAUNCH(10, 1, 1); break;
+    default: return hipErrorInvalidValue;
+    }
 #undef FRW_LAUNCH
     return hipGetLastError();
 }

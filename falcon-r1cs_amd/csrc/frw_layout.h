@@ -292,6 +292,19 @@ inline VerifyBufs verify_layout(void *ws, size_t k, size_t msm_per, bool bare, s
     v.bytes = c.off;
     return v;
 }
+// ---- the verifier's statement from bytes (frw_statement_from_bytes_dev): the decoded public keys and the hashed messages as uint16_t
+// [batch][N] each, 16-byte aligned, and the key decoder's statuses, which the statement kernel reads before it looks at a coefficient
+struct StatementBufs { uint16_t *pk, *hm; int32_t *decode_status; size_t bytes; };
+inline StatementBufs statement_layout(void *ws, int logn, size_t batch)
+{
+    StatementBufs b{};
+    Carve c(ws);
+    b.pk = c.take<uint16_t>((batch << logn) * 2, 16);
+    b.hm = c.take<uint16_t>((batch << logn) * 2, 16);
+    b.decode_status = c.take<int32_t>(batch * 4, 16);
+    b.bytes = c.off;
+    return b;
+}
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
 {

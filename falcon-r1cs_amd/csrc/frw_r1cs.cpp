@@ -444,21 +444,27 @@ extern "C" int frw_r1cs_load_aggregate(int device, size_t count, const int32_t *
             // per parameter set: where each of its statements sits (R1csView::offs), for the evaluation kernels' one launch per set
             for (int g = 0; g < 2; g++) {
                 std::vector<uint64_t> offs;
+                std::vector<uint32_t> stmt;
                 for (const frw::R1csAggRun &run : r->runs) {
                     if (run.base != (r->base[g] ? &r->base[g]->dev : nullptr)) continue;
                     for (uint32_t k = 0; k < run.count; k++) {
                         offs.push_back(run.wit_off + (uint64_t)k * run.base->num_witness);
                         offs.push_back(run.pub_off + (uint64_t)k * (run.base->num_instance - 1));
                         offs.push_back(run.row_off + (uint64_t)k * run.base->num_constraints);
+                        stmt.push_back(run.first + k);
                     }
                 }
-                r->agg.set[g] = frw::R1csAggSet{r->base[g] ? &r->base[g]->dev : nullptr, (uint32_t)(offs.size() / 3), nullptr};
+                r->agg.set[g] = frw::R1csAggSet{r->base[g] ? &r->base[g]->dev : nullptr, (uint32_t)(offs.size() / 3), nullptr, nullptr};
                 if (offs.empty()) continue;
                 void *d = nullptr;
                 if (hipMalloc(&d, offs.size() * 8) != hipSuccess) throw std::bad_alloc();
                 r->allocs.push_back(d);
                 if (hipMemcpy(d, offs.data(), offs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy");
                 r->agg.set[g].offs = (const uint64_t *)d;
+                if (hipMalloc(&d, stmt.size() * 4) != hipSuccess) throw std::bad_alloc();
+                r->allocs.push_back(d);
+                if (hipMemcpy(d, stmt.data(), stmt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy");
+                r->agg.set[g].stmt = (const uint32_t *)d;
             }
             r->dev.agg = &r->agg;
             r->dev.num_instance = (uint32_t)(pub + 1);
@@ -477,6 +483,13 @@ extern "C" int frw_r1cs_load_aggregate(int device, size_t count, const int32_t *
     }
     *out = r;
     return FRW_OK;
+}
+
+const frw::R1csAgg *frw::r1cs_aggregate(const frw_r1cs *r, int *device)
+{
+    if (!r || !r->dev.agg) return nullptr;
+    *device = r->device;
+    return &r->agg;
 }
 
 extern "C" int frw_r1cs_info(const frw_r1cs *r, frw_r1cs_info_t *out)

@@ -268,6 +268,24 @@ class Groth16Verifier:
               "frw_groth16_verify_wire_dev")
         return out
 
+    def verify_statements_wire_dev(self, engine, logn, pk_bytes, nonces, msgs, wire, circuit=CIRCUIT_NTT, compressed=True, flags=0,
+                                   batched=False, seed=None, stream=0):
+        """Verification from what a verifier is sent and nothing else: the Falcon public keys' bytes, the signatures' 40-byte nonces
+        (bytes 1 .. 40 of an encoded signature), the messages and the proofs' wire bytes (anything of batch x 192 or 384 bytes).  The
+        statements are made on the device by `engine` (a WitnessEngine on this key's device: statement_from_bytes_dev) and go to
+        verify_wire_dev as they are; batched / seed / flags are passed through.  Returns (statuses, verdicts), device int32 tensors
+        [batch]: FRW_ST_* of the statement and 1 / 0 / -1 -- a refused statement is a zero-filled instance vector, hence -1."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(wire, torch.Tensor):
+            d_wire = wire.to(dev).contiguous().view(torch.uint8).reshape(-1)
+        else:
+            raw = wire if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire, dtype=np.uint8).tobytes()
+            d_wire = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+        d_inst, d_status = engine.statement_from_bytes_dev(circuit, logn, pk_bytes, nonces, msgs, ENC_MONTGOMERY, stream)
+        verdicts = self.verify_wire_dev(d_inst, d_wire, compressed, ENC_MONTGOMERY, flags, batched, seed, stream)
+        return d_status, verdicts
+
     def close(self):
         if self._h:
             self._lib.frw_groth16_vk_free(self._h)
@@ -680,6 +698,94 @@ class WitnessEngine:
         P = lambda t: self._ptr(t) if t is not None else None
         check(self._lib.frw_aggregate_assign_dev(handle, P(d_wit512), P(d_inst512), P(d_wit1024), P(d_inst1024), self._ptr(d_wit),
                                                  self._ptr(d_inst), C.c_void_p(stream)), "frw_aggregate_assign_dev")
+
+    # ---- the verifier's statement: instance vectors without a signature -----------------------------------------------------------
+    def statement_dev(self, circuit, logn, batch, d_pk, d_hm, d_inst, d_status, encoding=ENC_MONTGOMERY, stream=0):
+        """instance_assignment of `batch` statements from (pk, hm) in device memory (frw_statement_dev): the bytes the witness entry
+        points write to d_inst for the same pk and hm, without a signature and without a witness."""
+        check(self._lib.frw_statement_dev(self._ctx, int(circuit), int(logn), batch, self._ptr(d_pk), self._ptr(d_hm), int(encoding),
+                                          self._ptr(d_inst), self._ptr(d_status), C.c_void_p(stream)), "frw_statement_dev")
+
+    def statement(self, circuit, logn, pk, hm, encoding=ENC_MONTGOMERY, strict=True):
+        """Host buffers (frw_statement): pk, hm uint16[batch, N] -> (instance u64[batch, 2 N + 1, 4], status i32[batch])."""
+        n = 1 << logn
+        pk, hm = _u16(pk, n), _u16(hm, n)
+        batch = pk.shape[0]
+        if hm.shape[0] != batch:
+            raise ValueError("batch mismatch")
+        inst = np.zeros((batch, 2 * n + 1, 4), dtype=np.uint64)
+        st = np.zeros(batch, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self._lib.frw_statement(self._ctx, int(circuit), int(logn), batch, p(pk), p(hm), int(encoding), p(inst), p(st), 1 if strict else 0)
+        if rc == E_RANGE:
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, "frw_statement", "Invalid input: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        check(rc, "frw_statement")
+        return inst, st
+
+    @staticmethod
+    def _statement_bytes(logn, pk_bytes, nonces, msgs):
+        batch = len(pk_bytes)
+        if len(nonces) != batch or len(msgs) != batch:
+            raise ValueError("batch mismatch")
+        if any(len(k) != PK_LEN[logn] for k in pk_bytes) or any(len(x) != NONCE_LEN for x in nonces):
+            raise ValueError("public keys must be %d bytes and nonces %d" % (PK_LEN[logn], NONCE_LEN))
+        pkb = np.frombuffer(b"".join(bytes(k) for k in pk_bytes) or b"\0", dtype=np.uint8)
+        non = np.frombuffer(b"".join(bytes(x) for x in nonces) or b"\0", dtype=np.uint8)
+        blob = np.frombuffer(b"".join(bytes(m) for m in msgs) or b"\0", dtype=np.uint8)
+        off = np.zeros(batch + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        return batch, pkb, non, blob, off
+
+    def statement_workspace_bytes(self, logn, batch):
+        return int(self._lib.frw_statement_workspace_bytes(int(logn), int(batch)))
+
+    def statement_from_bytes(self, circuit, logn, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY, strict=True):
+        """Host buffers (frw_statement_from_bytes): lists of encoded public keys, 40-byte nonces and messages -> (instance, status);
+        FRW_ST_DECODE and a zero-filled slot for a malformed key."""
+        batch, pkb, non, blob, off = self._statement_bytes(logn, pk_bytes, nonces, msgs)
+        n = 1 << logn
+        inst = np.zeros((batch, 2 * n + 1, 4), dtype=np.uint64)
+        st = np.zeros(batch, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self._lib.frw_statement_from_bytes(self._ctx, int(circuit), int(logn), batch, p(pkb), p(non), p(blob), p(off), int(encoding),
+                                                p(inst), p(st), 1 if strict else 0)
+        if rc == E_RANGE:
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, "frw_statement_from_bytes", "Invalid input: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        check(rc, "frw_statement_from_bytes")
+        return inst, st
+
+    def statement_from_bytes_dev(self, circuit, logn, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
+        """The same on the device (frw_statement_from_bytes_dev): the bytes are uploaded, the key decoder, SHAKE256 and the statement
+        kernel run on `stream`.  -> (instance int64[batch, 2 N + 1, 4], status int32[batch]) device tensors, not synchronised.
+        pk_bytes may be a device uint8 tensor [batch, PK_LEN] with nonces a device uint8 tensor [batch, 40], msgs a (blob, offsets)
+        pair of device tensors (uint8, int64[batch + 1]): nothing is uploaded then."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(pk_bytes, torch.Tensor):
+            d_pkb, d_non, (d_blob, d_off) = pk_bytes, nonces, msgs
+            batch = d_pkb.numel() // PK_LEN[logn]
+        else:
+            batch, pkb, non, blob, off = self._statement_bytes(logn, pk_bytes, nonces, msgs)
+            d_pkb, d_non, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, non, blob))
+            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        n = 1 << logn
+        d_inst = torch.empty((batch, 2 * n + 1, 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(batch, dtype=torch.int32, device=dev)
+        if workspace is None:
+            workspace = torch.empty(max(self.statement_workspace_bytes(logn, batch), 16), dtype=torch.uint8, device=dev)
+        check(self._lib.frw_statement_from_bytes_dev(self._ctx, int(circuit), int(logn), batch, self._ptr(d_pkb), self._ptr(d_non), self._ptr(d_blob),
+                                                     self._ptr(d_off), int(encoding), self._ptr(d_inst), self._ptr(d_status),
+                                                     self._ptr(workspace), workspace.numel(), C.c_void_p(stream)), "frw_statement_from_bytes_dev")
+        return d_inst, d_status
+
+    def aggregate_statement_dev(self, handle, d_pk512, d_hm512, d_pk1024, d_hm1024, d_inst, d_status, encoding=ENC_MONTGOMERY, stream=0):
+        """instance_assignment of the aggregate from the statements' keys and hashed messages, per parameter set in statement order
+        (either pair may be None): aggregate_assign_dev's d_inst without a witness.  d_status: int32[num_statements]."""
+        P = lambda t: self._ptr(t) if t is not None else None
+        check(self._lib.frw_aggregate_statement_dev(handle, self._ctx, P(d_pk512), P(d_hm512), P(d_pk1024), P(d_hm1024), int(encoding),
+                                                    self._ptr(d_inst), self._ptr(d_status), C.c_void_p(stream)), "frw_aggregate_statement_dev")
 
     def groth16_setup_r1cs(self, handle, alpha, beta, gamma, delta, t, mode=KEY_AUTO, rank=0, world=1, want_vk=True):
         """groth16_setup for the system behind an r1cs handle (a per-signature circuit or an aggregate statement).

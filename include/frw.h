@@ -819,6 +819,54 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
                        size_t sig_len, const uint8_t *msgs, const uint64_t *msg_off, uint16_t *sig, uint16_t *pk,
                        uint16_t *hm, int32_t *status);
 
+/* ---- the verifier's statement: public inputs without a signature -------------------------------------------------
+ * examples/pok_sig.rs:33-45 builds the public inputs from what a verifier holds -- the public key, and the message hashed with
+ * the signature's nonce -- and lifts them into Fr; not knowing the signature is the point of a proof of knowledge.  These calls
+ * write instance_assignment, 2 N + 1 field elements per statement, the exact bytes the witness entry points above write to
+ * d_instance for the same pk and hm, from those alone: one launch of a kernel that does two mod-q NTTs per statement and
+ * writes 33 / 66 KB (Falcon-512 / 1024) where the witness call writes 2.5 - 37 MB besides.
+ *     circuit     FRW_CIRCUIT_NTT, FRW_CIRCUIT_DUAL_NTT: [1, NTT(pk), NTT(hm)]; FRW_CIRCUIT_SCHOOLBOOK: [1, pk, hm]
+ *     encoding    FRW_ENC_CANONICAL or FRW_ENC_MONTGOMERY (there is no compact form of an instance vector)
+ *     d_pk, d_hm  uint16_t[batch][N]
+ *     d_instance  uint64_t[batch][2 N + 1][4]
+ *     d_status    int32_t[batch]: FRW_ST_OK; FRW_ST_COEFF_RANGE for a pk or hm coefficient >= q (the witness kernels' rule);
+ *                 from bytes also FRW_ST_DECODE for a malformed key (its header byte, or a 14-bit coefficient >= q)
+ * A refused statement's slot is all zero bytes, its leading one included, never stale memory.  Nothing downstream needs to be
+ * told: a zero-filled slot has instance[0] != 1, which frw_groth16_verify and every device verifier above report as -1
+ * (malformed).
+ * frw_statement_from_bytes_dev: frw_decode_public_keys_dev and frw_hash_to_point_dev into the caller's workspace, then the
+ * kernel.  d_pk_bytes: batch x FRW_PK_LEN(logn); d_nonces: batch x FRW_NONCE_LEN (bytes 1 .. 40 of an encoded signature); the
+ * messages as for frw_hash_to_point_dev.  d_workspace: frw_statement_workspace_bytes(logn, batch) bytes, 16-byte aligned -- pk
+ * and hm as uint16_t[batch][N], each rounded up to 16 bytes, then the key decoder's int32_t[batch] statuses likewise (0 for a bad
+ * logn).
+ * The _dev forms are stream-ordered on `stream`, allocate nothing and do not synchronise: capture-safe.  The host-buffer forms
+ * take host pointers, go through the context's arena 4,096 statements at a time, and with strict != 0 return FRW_E_RANGE if any
+ * status is non-zero (the buffers are complete all the same).  batch = 0 is a no-op.  FRW_E_INVALID_ARG, before any device is
+ * touched: FRW_ENC_COMPACT or another bad encoding, an unknown circuit, logn outside {9, 10}, a null pointer, a small or
+ * misaligned workspace; host forms: decreasing message offsets.
+ * frw_aggregate_statement_dev: instance_assignment of an aggregate (frw_r1cs_load_aggregate) -- [1, the public inputs of
+ * statement 0, of statement 1, ...] -- from the statements' keys and hashed messages: statement i takes the next unused entry of
+ * its parameter set's arrays, exactly as frw_aggregate_assign_dev does (either pair may be NULL if the aggregate has no such
+ * statement).  The same bytes as frw_aggregate_assign_dev's d_instance after witness calls on the same inputs, in one launch per
+ * parameter set and without a witness.  d_status: int32_t[num_statements], statement order.  The constant one is always
+ * written; a refused statement leaves zeros in its 2 N slots (such an instance vector is well formed and verifies against no
+ * proof).  ctx and the aggregate must be on the same device. */
+int frw_statement_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *d_pk, const uint16_t *d_hm,
+                      int encoding, uint64_t *d_instance, int32_t *d_status, void *stream);
+int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *pk, const uint16_t *hm,
+                  int encoding, uint64_t *instance, int32_t *status, int strict);
+size_t frw_statement_workspace_bytes(int logn, size_t batch);
+int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *d_pk_bytes,
+                                 const uint8_t *d_nonces, const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding,
+                                 uint64_t *d_instance, int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                                 void *stream);
+int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *pk_bytes,
+                             const uint8_t *nonces, const uint8_t *msgs, const uint64_t *msg_off, int encoding,
+                             uint64_t *instance, int32_t *status, int strict);
+int frw_aggregate_statement_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint16_t *d_pk_512, const uint16_t *d_hm_512,
+                                const uint16_t *d_pk_1024, const uint16_t *d_hm_1024, int encoding, uint64_t *d_instance,
+                                int32_t *d_status, void *stream);
+
 /* ---- stand-alone gadget blocks ---------------------------------------------------------------
  * The reference's gadget functions are also called outside the full circuit (its unit tests do; so can any
  * other circuit built from them).  One call fills the witness block of `count` independent gadget invocations,

@@ -360,6 +360,21 @@ extern "C" {
     pub fn frw_prepare_inputs(ctx: *mut frw_ctx, logn: c_int, batch: usize, pk_bytes: *const u8, sig_bytes: *const u8,
                               sig_len: usize, msgs: *const u8, msg_off: *const u64, sig: *mut u16, pk: *mut u16,
                               hm: *mut u16, status: *mut i32) -> c_int;
+    pub fn frw_statement_dev(ctx: *mut frw_ctx, circuit: c_int, logn: c_int, batch: usize, d_pk: *const u16, d_hm: *const u16,
+                             encoding: c_int, d_instance: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn frw_statement(ctx: *mut frw_ctx, circuit: c_int, logn: c_int, batch: usize, pk: *const u16, hm: *const u16,
+                         encoding: c_int, instance: *mut u64, status: *mut i32, strict: c_int) -> c_int;
+    pub fn frw_statement_workspace_bytes(logn: c_int, batch: usize) -> usize;
+    pub fn frw_statement_from_bytes_dev(ctx: *mut frw_ctx, circuit: c_int, logn: c_int, batch: usize, d_pk_bytes: *const u8,
+                                        d_nonces: *const u8, d_msgs: *const u8, d_msg_off: *const u64, encoding: c_int,
+                                        d_instance: *mut u64, d_status: *mut i32, d_workspace: *mut c_void,
+                                        workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_statement_from_bytes(ctx: *mut frw_ctx, circuit: c_int, logn: c_int, batch: usize, pk_bytes: *const u8,
+                                    nonces: *const u8, msgs: *const u8, msg_off: *const u64, encoding: c_int,
+                                    instance: *mut u64, status: *mut i32, strict: c_int) -> c_int;
+    pub fn frw_aggregate_statement_dev(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, d_pk_512: *const u16, d_hm_512: *const u16,
+                                       d_pk_1024: *const u16, d_hm_1024: *const u16, encoding: c_int, d_instance: *mut u64,
+                                       d_status: *mut i32, stream: *mut c_void) -> c_int;
     pub fn frw_gadget_block_len(kind: c_int) -> c_int;
     pub fn frw_gadget_dev(ctx: *mut frw_ctx, kind: c_int, count: usize, d_a: *const c_void, d_b: *const u64,
                           encoding: c_int, d_out: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;

@@ -863,6 +863,161 @@ int frw_aggregate_statement_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const u
     return FRW_OK;
 }
 
+// ---- Falcon verification: the verdict (and the norm) of (sig, pk, hm), or of the encoded key, signature and message; no witness -------
+namespace {
+bool bad_falcon_verify(const frw_ctx *ctx, int logn, int rule)
+{
+    return !ctx || (logn != 9 && logn != 10) || (rule != FRW_RULE_CIRCUIT && rule != FRW_RULE_SPEC);
+}
+constexpr size_t FALCON_VERIFY_CHUNK = 16384;     // signatures of one pass of the host-buffer forms: 100 MB of Falcon-1024 coefficients
+bool any_refused(const int32_t *status, size_t batch)
+{
+    bool any_bad = false;
+    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
+    return any_bad;
+}
+}  // namespace
+
+int frw_falcon_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk, const uint16_t *d_hm,
+                          int rule, int32_t *d_status, uint64_t *d_norm, void *stream)
+{
+    if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
+    if (!d_sig || !d_pk || !d_hm || !d_status) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, logn, rule, batch, d_sig, d_pk, d_hm, nullptr, nullptr, d_status,
+                                      d_norm, (hipStream_t)stream));
+    return FRW_OK;
+}
+
+size_t frw_falcon_verify_workspace_bytes(int logn, size_t batch)
+{
+    if (logn != 9 && logn != 10) return 0;
+    return frw::falcon_verify_layout(nullptr, logn, batch).bytes;
+}
+
+namespace {
+// the four kernels of the bytes path on `st`: both decoders and SHAKE256 into the workspace, then the verdicts.  A signature a decoder
+// refused leaves its nonce and part of its coefficients as the workspace held them: the hash reads 40 bytes that are the workspace's
+// whatever they hold, and the kernel reads the decoders' statuses first and no coefficient of such a signature.
+hipError_t falcon_verify_chain(const frw_ctx *ctx, int logn, size_t batch, const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes,
+                               size_t sig_len, const uint8_t *d_msgs, const uint64_t *d_msg_off, int rule, int32_t *d_status,
+                               uint64_t *d_norm, void *d_workspace, hipStream_t st)
+{
+    const frw::FalconVerifyBufs ws = frw::falcon_verify_layout(d_workspace, logn, batch);
+    hipError_t e = frw::launch_decode_public_keys(logn, batch, d_pk_bytes, ws.pk, ws.pk_status, st);
+    if (e == hipSuccess) e = frw::launch_decode_signatures(logn, batch, d_sig_bytes, sig_len, ws.sig, ws.nonce, ws.sig_status, st);
+    if (e == hipSuccess) e = frw::launch_hash_to_point(logn, batch, ws.nonce, d_msgs, d_msg_off, ws.hm, st);
+    if (e == hipSuccess)
+        e = frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, logn, rule, batch, ws.sig, ws.pk, ws.hm, ws.sig_status, ws.pk_status,
+                                      d_status, d_norm, st);
+    return e;
+}
+}  // namespace
+
+int frw_falcon_verify_from_bytes_dev(frw_ctx *ctx, int logn, size_t batch, const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes,
+                                     size_t sig_len, const uint8_t *d_msgs, const uint64_t *d_msg_off, int rule, int32_t *d_status,
+                                     uint64_t *d_norm, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
+    if (!d_pk_bytes || !d_sig_bytes || !d_msgs || !d_msg_off || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
+    if (sig_len <= 1 + FRW_NONCE_LEN) return FRW_E_INVALID_ARG;
+    if (((uintptr_t)d_workspace & 15) || workspace_bytes < frw_falcon_verify_workspace_bytes(logn, batch)) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(falcon_verify_chain(ctx, logn, batch, d_pk_bytes, d_sig_bytes, sig_len, d_msgs, d_msg_off, rule, d_status, d_norm,
+                                d_workspace, (hipStream_t)stream));
+    return FRW_OK;
+}
+
+int frw_falcon_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm, int rule,
+                      int32_t *status, uint64_t *norm, int strict)
+{
+    if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
+    if (!sig || !pk || !hm || !status) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    frw::HostArena &A = ctx->arena;
+    std::lock_guard<std::mutex> lock(A.mu);
+    frw::DrainOnExit drain(A);
+    FRW_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)1 << logn, chunk = std::min(batch, FALCON_VERIFY_CHUNK);
+    frw::Carve c(nullptr);
+    const size_t o_in = c.off;   c.take(3 * chunk * n * 2);
+    const size_t o_norm = c.off; c.take(chunk * sizeof(uint64_t));
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    FRW_HIP(A.reserve_device(0, c.off));
+    FRW_HIP(A.reserve_pinned(3 * chunk * n * 2));
+    char *d = (char *)A.d_slot[0];
+    uint16_t *stage = (uint16_t *)A.h_pin, *d_in = (uint16_t *)(d + o_in);
+    hipStream_t st = A.compute;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = std::min(chunk, batch - lo);
+        memcpy(stage, sig + lo * n, cnt * n * 2);
+        memcpy(stage + cnt * n, pk + lo * n, cnt * n * 2);
+        memcpy(stage + 2 * cnt * n, hm + lo * n, cnt * n * 2);
+        FRW_HIP(hipMemcpyAsync(d_in, stage, 3 * cnt * n * 2, hipMemcpyHostToDevice, st));
+        FRW_HIP(frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, logn, rule, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, nullptr,
+                                          nullptr, (int32_t *)(d + o_st), (uint64_t *)(d + o_norm), st));
+        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (norm) FRW_HIP(hipMemcpyAsync(norm + lo, d + o_norm, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
+    }
+    drain.settled = true;
+    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+}
+
+int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *sig_bytes, size_t sig_len,
+                                 const uint8_t *msgs, const uint64_t *msg_off, int rule, int32_t *status, uint64_t *norm, int strict)
+{
+    if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
+    if (!pk_bytes || !sig_bytes || !msgs || !msg_off || !status || sig_len <= 1 + FRW_NONCE_LEN) return FRW_E_INVALID_ARG;
+    for (size_t i = 0; i < batch; i++)
+        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (batch == 0) return FRW_OK;
+    frw::HostArena &A = ctx->arena;
+    std::lock_guard<std::mutex> lock(A.mu);
+    frw::DrainOnExit drain(A);
+    FRW_HIP(hipSetDevice(ctx->device));
+    const size_t pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, FALCON_VERIFY_CHUNK);
+    size_t max_msg = 1;                                                   // the longest pass's message bytes
+    for (size_t lo = 0; lo < batch; lo += chunk)
+        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
+    // the staged inputs' layout == their device layout: ONE copy in per pass
+    frw::Carve hs(nullptr);
+    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
+    const size_t o_sigb = hs.off; hs.take(chunk * sig_len);
+    const size_t o_msgs = hs.off; hs.take(max_msg);
+    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
+    const size_t in_total = hs.off;
+    frw::Carve c(nullptr);
+    c.take(in_total);
+    const size_t o_ws = c.off;   c.take(frw_falcon_verify_workspace_bytes(logn, chunk));
+    const size_t o_norm = c.off; c.take(chunk * sizeof(uint64_t));
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    FRW_HIP(A.reserve_device(0, c.off));
+    FRW_HIP(A.reserve_pinned(in_total));
+    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
+    hipStream_t st = A.compute;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = std::min(chunk, batch - lo);
+        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
+        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
+        memcpy(h + o_sigb, sig_bytes + lo * sig_len, cnt * sig_len);
+        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
+        uint64_t *off = (uint64_t *)(h + o_off);
+        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
+        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
+        FRW_HIP(falcon_verify_chain(ctx, logn, cnt, (const uint8_t *)(d + o_pkb), (const uint8_t *)(d + o_sigb), sig_len,
+                                    (const uint8_t *)(d + o_msgs), (const uint64_t *)(d + o_off), rule, (int32_t *)(d + o_st),
+                                    (uint64_t *)(d + o_norm), d + o_ws, st));
+        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (norm) FRW_HIP(hipMemcpyAsync(norm + lo, d + o_norm, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipStreamSynchronize(st));
+    }
+    drain.settled = true;
+    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+}
+
 int frw_gadget_block_len(int kind)
 {
     static const int len[6] = {27, 29, 29, 18, 50, 52};

@@ -91,6 +91,12 @@ hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, siz
 hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
                             const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
                             int32_t *status, const uint32_t *status_index, hipStream_t st);
+// Falcon verification without a witness (falcon_verify_kernel): status[s] = FRW_ST_*, norm[s] (norm may be null) = the squared norm
+// of v || sig under `rule` (0 = the circuits' rule, the witness kernels' status word; 1 = the specification's), all ones where the
+// signature was refused before a norm exists.  pre0, pre1 (may be null): statuses that refuse a signature before its coefficients are read.
+hipError_t launch_falcon_verify(const Tables *tab, int num_cu, int logn, int rule, size_t batch, const uint16_t *sig,
+                                const uint16_t *pk, const uint16_t *hm, const int32_t *pre0, const int32_t *pre1,
+                                int32_t *status, uint64_t *norm, hipStream_t st);
 hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,
                          int32_t *status, hipStream_t st);
 hipError_t launch_hash_to_point(int logn, size_t batch, const uint8_t *nonces, const uint8_t *msgs, const uint64_t *msg_off,

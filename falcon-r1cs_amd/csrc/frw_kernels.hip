@@ -1380,6 +1380,122 @@ __global__ __launch_bounds__(BLOCK) void statement_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
+// kernel: Falcon verification, the verdict without a witness (examples/pok_sig.rs:21, keypair.public_key.verify(msg, &sig):
+// the question the witness kernels answer in g_status beside 2.5 - 37 MB of witness).  One signature per workgroup on a
+// persistent grid: sig, pk, hm into LDS, the range check, NTT(sig) and NTT(pk) in one ntt_modq_lds<LOGN, 2>, their
+// pointwise product, its inverse transform, v = hm - sig*pk in the coefficient domain -- two forward transforms and one
+// inverse, none of hm; the arithmetic mod q is exact, so v is the witness kernel's INTT(NTT(hm) - NTT(sig) NTT(pk)) --
+// then the squared norm of v || sig over centred representatives (per lane in 64 bits, < 2^37 in all, as S6 above) and
+// ONE status word and, if asked, one 64-bit norm out: twelve bytes per signature.
+//   RULE 0 (FRW_RULE_CIRCUIT)   what the three circuits prove, word for word the witness kernels' status: r = a < 6144 ?
+//                               a : q - a (is_less_than_6144, misc.rs:35-46: a = 6144 counts as 6145), refused at norm >=
+//                               34034726 / 70265242
+//   RULE 1 (FRW_RULE_SPEC)      the specification's Verify: r = a <= 6144 ? a : q - a, refused at norm > beta^2 (the same
+//                               two numbers)
+//   pre0, pre1                  (may be null) a non-zero word refuses signature s with that status (FRW_ST_DECODE of the
+//                               two decoders) before a coefficient of it is read
+// A signature refused before a norm exists (pre-status, coefficient >= q) gets all ones in g_norm.
+// The inverse twiddles are read from the table, as the witness kernel reads them: a copy in LDS measured 0.966 / 0.982 of
+// this (profiles/r12_falcon_verify.txt), 0.01 ms of a launch, and was not taken.
+// FRW_FV_STAGE: measurement builds only (tools/time_falcon_verify.py --variant): 1 = without the inverse transform, 2 = loads,
+// range check and norm only.
+// ------------------------------------------------------------------------------------------------
+#ifndef FRW_FV_STAGE
+#define FRW_FV_STAGE 0
+#endif
+
+template <int LOGN>
+struct alignas(16) SmemFalconVerify {
+    static constexpr int N = 1 << LOGN;
+    uint16_t tw[N];
+    uint16_t sig[N];                     // coefficient domain, for the norm
+    uint16_t nsig[N], npk[N];            // NTT domain; nsig becomes the product and then sig*pk
+    uint16_t hm[N];
+    unsigned long long norm;
+    int pre, bad;
+};
+
+template <int LOGN, int RULE>
+__global__ __launch_bounds__(BLOCK) void falcon_verify_kernel(
+    const Tables *__restrict__ tab, size_t batch,
+    const uint16_t *__restrict__ g_sig, const uint16_t *__restrict__ g_pk, const uint16_t *__restrict__ g_hm,
+    const int32_t *__restrict__ pre0, const int32_t *__restrict__ pre1,
+    int32_t *__restrict__ g_status, unsigned long long *__restrict__ g_norm)
+{
+    constexpr int N = 1 << LOGN;
+    constexpr unsigned long long BETA2 = LOGN == 9 ? 34034726ull : 70265242ull;
+    __shared__ SmemFalconVerify<LOGN> sm;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+
+    for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
+
+    for (size_t s = blockIdx.x; s < batch; s += gridDim.x) {
+        // ---- 1. a verdict already reached, else load + range check -------------------------------
+        if (tid == 0) {
+            int p = pre0 ? pre0[s] : 0;
+            if (!p && pre1) p = pre1[s];
+            sm.pre = p; sm.bad = p; sm.norm = 0;
+        }
+        lds_barrier();
+        if (!sm.pre) {                                   // uniform across the workgroup
+            int bad = 0;
+            for (int j = tid; j < N; j += BLOCK) {
+                const uint32_t a = g_sig[s * N + j], b = g_pk[s * N + j], c = g_hm[s * N + j];
+                bad |= (a >= Q) | (b >= Q) | (c >= Q);
+                sm.sig[j] = (uint16_t)a; sm.nsig[j] = (uint16_t)a; sm.npk[j] = (uint16_t)b; sm.hm[j] = (uint16_t)c;
+            }
+            if (bad) sm.bad = ST_COEFF_RANGE;
+        }
+        lds_barrier();
+        if (sm.bad) {                                    // uniform across the workgroup
+            if (tid == 0) {
+                g_status[s] = sm.bad;
+                if (g_norm) g_norm[s] = ~0ull;
+            }
+            lds_barrier();                  // every wave has read sm.pre and sm.bad before thread 0 rewrites them
+            continue;
+        }
+        // ---- 2. sig * pk mod (x^N + 1, q) ---------------------------------------------------------
+#if FRW_FV_STAGE < 2
+        {
+            uint16_t *const polys[2] = {sm.nsig, sm.npk};
+            ntt_modq_lds<LOGN, 2>(polys, sm.tw, tid);
+        }
+        for (int j = tid; j < N; j += BLOCK) sm.nsig[j] = (uint16_t)mod_q_u32((uint32_t)sm.nsig[j] * sm.npk[j]);
+        lds_barrier();
+#if FRW_FV_STAGE < 1
+        intt_modq_lds<LOGN>(sm.nsig, tab->itw, tid);
+#endif
+#endif
+        // ---- 3. v = hm - sig * pk, the squared norm of v || sig -------------------------------------
+        unsigned long long nrm = 0;
+        for (int j = tid; j < N; j += BLOCK) {           // (every lane reads what it wrote itself, or what a barrier is behind)
+            uint32_t v = sm.hm[j] + Q - sm.nsig[j];
+            v = v >= Q ? v - Q : v;
+            const uint32_t a = sm.sig[j];
+            uint32_t rv, ra;
+            if constexpr (RULE == 0) {
+                rv = (lt6144_mask(v) >> 15) & 1u ? v : Q - v;            // misc.rs:35-46
+                ra = (lt6144_mask(a) >> 15) & 1u ? a : Q - a;
+            } else {
+                rv = v <= 6144u ? v : Q - v;
+                ra = a <= 6144u ? a : Q - a;
+            }
+            nrm += (unsigned long long)(rv * rv) + (unsigned long long)(ra * ra);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor((unsigned long long)nrm, off, WAVE);
+        if (lane == 0) atomicAdd(&sm.norm, nrm);
+        lds_barrier();
+        if (tid == 0) {
+            const unsigned long long norm = sm.norm;
+            g_status[s] = (RULE == 0 ? norm >= BETA2 : norm > BETA2) ? ST_NORM_BOUND : ST_OK;
+            if (g_norm) g_norm[s] = norm;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernel: NTTPolyVar::ntt_circuit alone (poly.rs:104-159): N mod_q blocks + the reduced NTT
 // ------------------------------------------------------------------------------------------------
 template <int LOGN>
@@ -1756,6 +1872,7 @@ hipError_t launch_write_stream(void *buf, size_t bytes, size_t slab_bytes, int n
 static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4], g_occ_schoolbook[4];   // resident workgroups per CU, [(LOGN-9)*2 + ENC]
 static int g_occ_compact[2], g_occ_expand[2];                  // [LOGN - 9]
 static int g_occ_statement[8];                                 // [(LOGN - 9) * 4 + FORM * 2 + ENC]
+static int g_occ_falcon_verify[4];                             // [(LOGN - 9) * 2 + RULE]
 static std::once_flag g_occ_once;
 
 template <typename K>
@@ -1820,6 +1937,10 @@ void init_launch_config()
         FRW_QS(9, 0, 0); FRW_QS(9, 0, 1); FRW_QS(9, 1, 0); FRW_QS(9, 1, 1);
         FRW_QS(10, 0, 0); FRW_QS(10, 0, 1); FRW_QS(10, 1, 0); FRW_QS(10, 1, 1);
 #undef FRW_QS
+        query_residency(falcon_verify_kernel<9, 0>, g_occ_falcon_verify[0]);
+        query_residency(falcon_verify_kernel<9, 1>, g_occ_falcon_verify[1]);
+        query_residency(falcon_verify_kernel<10, 0>, g_occ_falcon_verify[2]);
+        query_residency(falcon_verify_kernel<10, 1>, g_occ_falcon_verify[3]);
     });
 }
 
@@ -1956,6 +2077,27 @@ hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, i
     case 5: FRW_LAUNCH(10, 0, 1); break;
     case 6: FRW_LAUNCH(10, 1, 0); break;
     case 7: FRW_LAUNCH(10, 1, 1); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef FRW_LAUNCH
+    return hipGetLastError();
+}
+
+// one launch: the signatures strided over the resident grid, one workgroup a signature
+hipError_t launch_falcon_verify(const Tables *tab, int num_cu, int logn, int rule, size_t batch, const uint16_t *sig,
+                                const uint16_t *pk, const uint16_t *hm, const int32_t *pre0, const int32_t *pre1,
+                                int32_t *status, uint64_t *norm, hipStream_t st)
+{
+    if (batch == 0) return hipSuccess;
+    const int grid = resident_grid(batch, num_cu, g_occ_falcon_verify[(logn - 9) * 2 + rule]);
+#define FRW_LAUNCH(LOGN, RULE)                                                                                            \
+    hipLaunchKernelGGL((falcon_verify_kernel<LOGN, RULE>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, sig, pk, hm, pre0, \
+                       pre1, status, (unsigned long long *)norm)
+    switch ((logn - 9) * 2 + rule) {
+    case 0: FRW_LAUNCH(9, 0); break;
+    case 1: FRW_LAUNCH(9, 1); break;
+    case 2: FRW_LAUNCH(10, 0); break;
+    case 3: FRW_LAUNCH(10, 1); break;
     default: return hipErrorInvalidValue;
     }
 #undef FRW_LAUNCH

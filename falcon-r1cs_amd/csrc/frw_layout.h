@@ -305,6 +305,23 @@ inline StatementBufs statement_layout(void *ws, int logn, size_t batch)
     b.bytes = c.off;
     return b;
 }
+// ---- Falcon verification from bytes (frw_falcon_verify_from_bytes_dev): the decoded signatures, the decoded public keys and the hashed
+// messages as uint16_t[batch][N] each, the signatures' nonces as batch x 40 bytes, then the signature decoder's and the key decoder's
+// int32_t[batch] statuses, which the kernel reads before it looks at a coefficient; every piece rounded up to 16 bytes
+struct FalconVerifyBufs { uint16_t *sig, *pk, *hm; uint8_t *nonce; int32_t *sig_status, *pk_status; size_t bytes; };
+inline FalconVerifyBufs falcon_verify_layout(void *ws, int logn, size_t batch)
+{
+    FalconVerifyBufs b{};
+    Carve c(ws);
+    b.sig = c.take<uint16_t>((batch << logn) * 2, 16);
+    b.pk = c.take<uint16_t>((batch << logn) * 2, 16);
+    b.hm = c.take<uint16_t>((batch << logn) * 2, 16);
+    b.nonce = c.take<uint8_t>(batch * 40, 16);
+    b.sig_status = c.take<int32_t>(batch * 4, 16);
+    b.pk_status = c.take<int32_t>(batch * 4, 16);
+    b.bytes = c.off;
+    return b;
+}
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
 {

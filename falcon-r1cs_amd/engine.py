@@ -21,6 +21,7 @@ SIG_LEN = {9: 666, 10: 1280}
 E_RANGE = -5
 G_LESS_THAN_Q, G_MOD_Q, G_ADD_MOD, G_L2_ELEM, G_NORM_BOUND_512, G_NORM_BOUND_1024 = range(6)
 CIRCUIT_NTT, CIRCUIT_DUAL_NTT, CIRCUIT_SCHOOLBOOK = 0, 1, 2
+RULE_CIRCUIT, RULE_SPEC = 0, 1          # FRW_RULE_*: how falcon_verify* centres a coefficient and compares the norm
 
 
 @dataclass(frozen=True)
@@ -786,6 +787,94 @@ class WitnessEngine:
         P = lambda t: self._ptr(t) if t is not None else None
         check(self._lib.frw_aggregate_statement_dev(handle, self._ctx, P(d_pk512), P(d_hm512), P(d_pk1024), P(d_hm1024), int(encoding),
                                                     self._ptr(d_inst), self._ptr(d_status), C.c_void_p(stream)), "frw_aggregate_statement_dev")
+
+    # ---- Falcon verification: verdicts and norms without a witness -------------------------------------------------------------------
+    def falcon_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_status, d_norm=None, rule=RULE_CIRCUIT, stream=0):
+        """The verdicts of `batch` signatures from (sig, pk, hm) in device memory (frw_falcon_verify_dev): d_status int32[batch] is FRW_ST_*
+        -- under RULE_CIRCUIT the word the witness entry points write for the same inputs --, d_norm (int64[batch] or None) the squared
+        norm under `rule`, all ones where none exists.  Not synchronised."""
+        check(self._lib.frw_falcon_verify_dev(self._ctx, int(logn), batch, self._ptr(d_sig), self._ptr(d_pk), self._ptr(d_hm), int(rule),
+                                              self._ptr(d_status), self._ptr(d_norm) if d_norm is not None else None, C.c_void_p(stream)),
+              "frw_falcon_verify_dev")
+
+    def falcon_verify(self, logn, sig, pk, hm, rule=RULE_CIRCUIT, strict=True, want_norm=True):
+        """Host buffers (frw_falcon_verify): sig, pk, hm uint16[batch, N] -> (status i32[batch], norm u64[batch] or None)."""
+        n = 1 << logn
+        sig, pk, hm = _u16(sig, n), _u16(pk, n), _u16(hm, n)
+        batch = sig.shape[0]
+        if pk.shape[0] != batch or hm.shape[0] != batch:
+            raise ValueError("batch mismatch")
+        st = np.zeros(batch, dtype=np.int32)
+        norm = np.zeros(batch, dtype=np.uint64) if want_norm else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self._lib.frw_falcon_verify(self._ctx, int(logn), batch, p(sig), p(pk), p(hm), int(rule), p(st), p(norm) if want_norm else None,
+                                         1 if strict else 0)
+        if rc == E_RANGE:
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, "frw_falcon_verify", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        check(rc, "frw_falcon_verify")
+        return st, norm
+
+    @staticmethod
+    def _falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs):
+        batch = len(pk_bytes)
+        if len(sig_bytes) != batch or len(msgs) != batch:
+            raise ValueError("batch mismatch")
+        sig_len = len(sig_bytes[0]) if batch else SIG_LEN[logn]
+        if any(len(k) != PK_LEN[logn] for k in pk_bytes) or any(len(x) != sig_len for x in sig_bytes):
+            raise ValueError("public keys must be %d bytes and signatures of one common length" % PK_LEN[logn])
+        pkb = np.frombuffer(b"".join(bytes(k) for k in pk_bytes) or b"\0", dtype=np.uint8)
+        sgb = np.frombuffer(b"".join(bytes(x) for x in sig_bytes) or b"\0", dtype=np.uint8)
+        blob = np.frombuffer(b"".join(bytes(m) for m in msgs) or b"\0", dtype=np.uint8)
+        off = np.zeros(batch + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        return batch, sig_len, pkb, sgb, blob, off
+
+    def falcon_verify_workspace_bytes(self, logn, batch):
+        return int(self._lib.frw_falcon_verify_workspace_bytes(int(logn), int(batch)))
+
+    def falcon_verify_from_bytes(self, logn, pk_bytes, sig_bytes, msgs, rule=RULE_CIRCUIT, strict=True, want_norm=True):
+        """Host buffers (frw_falcon_verify_from_bytes): lists of encoded public keys, encoded signatures of one common length and messages
+        -> (status, norm or None); FRW_ST_DECODE for a malformed key or signature."""
+        batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
+        st = np.zeros(batch, dtype=np.int32)
+        norm = np.zeros(batch, dtype=np.uint64) if want_norm else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self._lib.frw_falcon_verify_from_bytes(self._ctx, int(logn), batch, p(pkb), p(sgb), sig_len, p(blob), p(off), int(rule), p(st),
+                                                    p(norm) if want_norm else None, 1 if strict else 0)
+        if rc == E_RANGE:
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, "frw_falcon_verify_from_bytes", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        check(rc, "frw_falcon_verify_from_bytes")
+        return st, norm
+
+    def falcon_verify_from_bytes_dev(self, logn, pk_bytes, sig_bytes, msgs, rule=RULE_CIRCUIT, stream=0, workspace=None, sig_len=None):
+        """The same on the device (frw_falcon_verify_from_bytes_dev): the bytes are uploaded, both decoders, SHAKE256 and the kernel run
+        on `stream`.  -> (status int32[batch], norm int64[batch]) device tensors, not synchronised.  pk_bytes may be a device uint8
+        tensor [batch, PK_LEN] with sig_bytes a device uint8 tensor [batch, sig_len], msgs a (blob, offsets) pair of device tensors
+        (uint8, int64[batch + 1]): nothing is uploaded then.  The uploaded inputs and a workspace made here are torch's and go back
+        to its allocator when this method returns, with the four kernels possibly still queued: pass torch's current stream (or 0 while
+        that is the default stream), or pass device tensors and a `workspace` of your own and keep them until `stream` has run."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(pk_bytes, torch.Tensor):
+            d_pkb, d_sgb, (d_blob, d_off) = pk_bytes, sig_bytes, msgs
+            batch = d_pkb.numel() // PK_LEN[logn]
+            if sig_len is None:
+                sig_len = d_sgb.numel() // batch if batch else SIG_LEN[logn]
+        else:
+            batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
+            d_pkb, d_sgb, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, sgb, blob))
+            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        d_status = torch.empty(batch, dtype=torch.int32, device=dev)
+        d_norm = torch.empty(batch, dtype=torch.int64, device=dev)
+        if workspace is None:
+            workspace = torch.empty(max(self.falcon_verify_workspace_bytes(logn, batch), 16), dtype=torch.uint8, device=dev)
+        check(self._lib.frw_falcon_verify_from_bytes_dev(self._ctx, int(logn), batch, self._ptr(d_pkb), self._ptr(d_sgb), int(sig_len),
+                                                         self._ptr(d_blob), self._ptr(d_off), int(rule), self._ptr(d_status), self._ptr(d_norm),
+                                                         self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
+              "frw_falcon_verify_from_bytes_dev")
+        return d_status, d_norm
 
     def groth16_setup_r1cs(self, handle, alpha, beta, gamma, delta, t, mode=KEY_AUTO, rank=0, world=1, want_vk=True):
         """groth16_setup for the system behind an r1cs handle (a per-signature circuit or an aggregate statement).

@@ -867,6 +867,56 @@ int frw_aggregate_statement_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const u
                                 const uint16_t *d_pk_1024, const uint16_t *d_hm_1024, int encoding, uint64_t *d_instance,
                                 int32_t *d_status, void *stream);
 
+/* ---- Falcon verification: batch verdicts without a witness --------------------------------------------------------
+ * examples/pok_sig.rs:21 asserts keypair.public_key.verify(msg, &sig) before it builds a circuit.  These calls answer
+ * that question for a batch and write nothing else: one status word and, if asked, one 64-bit squared norm per signature --
+ * twelve bytes where the witness entry points write 2.5 / 5.1 MB (55 / 110 KB in compact form) to reach the same word.  One
+ * kernel, one workgroup per signature: NTT(sig), NTT(pk), their product, one inverse NTT, v = hm - sig*pk, the squared norm
+ * of v || sig over centred representatives.  A screen in front of frw_witness_*_dev and frw_groth16_prove_dev, and a plain
+ * Falcon batch verifier.
+ *     rule        how a coefficient a in [0, q) is centred and how the norm is compared:
+ *                 FRW_RULE_CIRCUIT  what the three circuits prove and what the witness kernels report: r = a < 6144 ? a :
+ *                                   q - a (is_less_than_6144: a = 6144 counts as 6145); refused when norm >= 34034726 /
+ *                                   70265242 (Falcon-512 / 1024).  FRW_ST_OK under this rule: the signature can be proven;
+ *                                   any other status: it cannot.  For every input the status word is the one
+ *                                   frw_witness_ntt_verify_dev writes for the same (sig, pk, hm).
+ *                 FRW_RULE_SPEC     the Falcon specification's Verify: r = a <= 6144 ? a : q - a; refused when norm >
+ *                                   beta^2 (the same two numbers).
+ *                 The two rules differ in exactly two cases: a norm equal to beta^2 (the specification accepts, the
+ *                 circuits do not), and a coefficient equal to 6144 (6144^2 under the specification, 6145^2 under the
+ *                 circuits) -- which can only decide a verdict at Falcon-1024, because 6144^2 > beta^2 at Falcon-512.
+ *     d_sig, d_pk, d_hm   uint16_t[batch][N]
+ *     d_status    int32_t[batch]: FRW_ST_OK, FRW_ST_COEFF_RANGE (a coefficient of sig, pk or hm >= q), FRW_ST_NORM_BOUND; from
+ *                 bytes also FRW_ST_DECODE, raised by either decoder.  FRW_ST_DECODE beats FRW_ST_COEFF_RANGE beats
+ *                 FRW_ST_NORM_BOUND.
+ *     d_norm      (may be NULL) uint64_t[batch]: the squared norm under `rule`; all ones where the signature was refused
+ *                 before a norm exists (FRW_ST_DECODE, FRW_ST_COEFF_RANGE); never stale memory.
+ * frw_falcon_verify_from_bytes_dev: frw_decode_public_keys_dev, frw_decode_signatures_dev (the nonce goes to the workspace)
+ * and frw_hash_to_point_dev into the caller's workspace, then the kernel, which takes the decoders' statuses as verdicts
+ * already reached and reads no coefficient of such a signature.  d_pk_bytes: batch x FRW_PK_LEN(logn); d_sig_bytes: batch x
+ * sig_len, as for frw_decode_signatures_dev; the messages as for frw_hash_to_point_dev.  d_workspace:
+ * frw_falcon_verify_workspace_bytes(logn, batch) bytes, 16-byte aligned -- sig, pk, hm as uint16_t[batch][N], the nonces as
+ * batch x 40 bytes, the two decoders' int32_t[batch] statuses, each piece rounded up to 16 bytes (0 for a bad logn).
+ * The _dev forms are stream-ordered on `stream`, allocate nothing and do not synchronise: capture-safe.  The host-buffer forms
+ * take host pointers, go through the context's arena 16,384 signatures at a time, and with strict != 0 return FRW_E_RANGE if
+ * any status is non-zero (the buffers are complete all the same).  batch = 0 is a no-op.  FRW_E_INVALID_ARG, before any device
+ * is touched: logn outside {9, 10}, an unknown rule, a null pointer other than d_norm / norm, a small or misaligned workspace,
+ * sig_len <= 41; host forms: decreasing message offsets. */
+#define FRW_RULE_CIRCUIT 0
+#define FRW_RULE_SPEC    1
+int frw_falcon_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
+                          const uint16_t *d_hm, int rule, int32_t *d_status, uint64_t *d_norm, void *stream);
+int frw_falcon_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
+                      int rule, int32_t *status, uint64_t *norm, int strict);
+size_t frw_falcon_verify_workspace_bytes(int logn, size_t batch);
+int frw_falcon_verify_from_bytes_dev(frw_ctx *ctx, int logn, size_t batch, const uint8_t *d_pk_bytes,
+                                     const uint8_t *d_sig_bytes, size_t sig_len, const uint8_t *d_msgs,
+                                     const uint64_t *d_msg_off, int rule, int32_t *d_status, uint64_t *d_norm,
+                                     void *d_workspace, size_t workspace_bytes, void *stream);
+int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *sig_bytes,
+                                 size_t sig_len, const uint8_t *msgs, const uint64_t *msg_off, int rule, int32_t *status,
+                                 uint64_t *norm, int strict);
+
 /* ---- stand-alone gadget blocks ---------------------------------------------------------------
  * The reference's gadget functions are also called outside the full circuit (its unit tests do; so can any
  * other circuit built from them).  One call fills the witness block of `count` independent gadget invocations,

@@ -23,6 +23,8 @@ pub const FRW_ST_DECODE: i32 = 3;
 pub const FRW_CIRCUIT_NTT: c_int = 0;
 pub const FRW_CIRCUIT_DUAL_NTT: c_int = 1;
 pub const FRW_CIRCUIT_SCHOOLBOOK: c_int = 2;
+pub const FRW_RULE_CIRCUIT: c_int = 0;
+pub const FRW_RULE_SPEC: c_int = 1;
 pub const FRW_NONCE_LEN: usize = 40;
 
 #[repr(C)]
@@ -375,6 +377,18 @@ extern "C" {
     pub fn frw_aggregate_statement_dev(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, d_pk_512: *const u16, d_hm_512: *const u16,
                                        d_pk_1024: *const u16, d_hm_1024: *const u16, encoding: c_int, d_instance: *mut u64,
                                        d_status: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn frw_falcon_verify_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_sig: *const u16, d_pk: *const u16, d_hm: *const u16,
+                                 rule: c_int, d_status: *mut i32, d_norm: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn frw_falcon_verify(ctx: *mut frw_ctx, logn: c_int, batch: usize, sig: *const u16, pk: *const u16, hm: *const u16,
+                             rule: c_int, status: *mut i32, norm: *mut u64, strict: c_int) -> c_int;
+    pub fn frw_falcon_verify_workspace_bytes(logn: c_int, batch: usize) -> usize;
+    pub fn frw_falcon_verify_from_bytes_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_pk_bytes: *const u8,
+                                            d_sig_bytes: *const u8, sig_len: usize, d_msgs: *const u8, d_msg_off: *const u64,
+                                            rule: c_int, d_status: *mut i32, d_norm: *mut u64, d_workspace: *mut c_void,
+                                            workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_falcon_verify_from_bytes(ctx: *mut frw_ctx, logn: c_int, batch: usize, pk_bytes: *const u8, sig_bytes: *const u8,
+                                        sig_len: usize, msgs: *const u8, msg_off: *const u64, rule: c_int, status: *mut i32,
+                                        norm: *mut u64, strict: c_int) -> c_int;
     pub fn frw_gadget_block_len(kind: c_int) -> c_int;
     pub fn frw_gadget_dev(ctx: *mut frw_ctx, kind: c_int, count: usize, d_a: *const c_void, d_b: *const u64,
                           encoding: c_int, d_out: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;

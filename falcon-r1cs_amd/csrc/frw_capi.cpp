@@ -1018,6 +1018,178 @@ int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uin
     return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
 }
 
+// ---- the prover from bytes: (pk bytes, msg, sig bytes) -> Groth16 proofs on the wire, one call ----------------------------------------
+namespace {
+// what the arguments say about the circuit, before any handle is looked at
+bool bad_pok_prove(const frw_ctx *ctx, int circuit, int logn, int wire_mode, size_t sig_len)
+{
+    return !ctx || (logn != 9 && logn != 10) ||
+           (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT && circuit != FRW_CIRCUIT_SCHOOLBOOK) ||
+           frw_groth16_proof_wire_bytes(wire_mode) == 0 || sig_len <= 1 + FRW_NONCE_LEN;
+}
+// ... and whether the handles are that circuit's: a per-signature system with its I, W, C, and a whole key over it.  W in *num_witness.
+bool pok_prove_shape(const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t *num_witness)
+{
+    if (!pk || !r || (logn != 9 && logn != 10)) return false;
+    const uint64_t n = (uint64_t)1 << logn, nb = logn == 9 ? 50 : 52;
+    uint64_t W, C;
+    switch (circuit) {
+    case FRW_CIRCUIT_NTT: W = 153 * n + nb; C = 159 * n + nb + 2; break;
+    case FRW_CIRCUIT_DUAL_NTT: W = 186 * n + 4 + nb; C = 189 * n + 10 + nb; break;
+    case FRW_CIRCUIT_SCHOOLBOOK: W = n * n + 99 * n + nb; C = n * n + 105 * n + nb + 2; break;
+    default: return false;
+    }
+    frw_r1cs_info_t info;
+    frw_groth16_pk_info_t ki;
+    if (frw_r1cs_info(r, &info) != FRW_OK || frw_groth16_pk_info(pk, &ki) != FRW_OK) return false;
+    if (info.num_statements != 1 || info.num_instance != 2 * n + 1 || info.num_witness != W || info.num_constraints != C) return false;
+    if (ki.world > 1) return false;                                       // a slice of a key proves nothing by itself
+    int device = -1;
+    uint64_t ni = 0, nw = 0, dom = 0;
+    frw::groth16_pk_counts(pk, &device, &ni, &nw, &dom);
+    if (ni != info.num_instance || nw != W || device != frw::r1cs_device(r)) return false;
+    *num_witness = (size_t)W;
+    return true;
+}
+constexpr size_t POK_PROVE_MAX_IN_FLIGHT = 4096;  // (the prover's own bound on a chunk)
+constexpr size_t POK_PROVE_CHUNK = 256;           // slots of one pass of the host-buffer form ...
+constexpr size_t POK_PROVE_HOST_IN_FLIGHT = 8;    // ... and the proofs in flight its share of the arena is sized for
+}  // namespace
+
+size_t frw_pok_prove_workspace_bytes(const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch, size_t in_flight)
+{
+    size_t W = 0;
+    if (in_flight == 0 || !pok_prove_shape(pk, r, circuit, logn, &W)) return 0;
+    const size_t g = frw_groth16_workspace_bytes(pk, r, in_flight);
+    return g ? frw::pok_prove_layout(nullptr, logn, batch, in_flight, W, g).bytes : 0;
+}
+
+int frw_pok_prove_from_bytes_dev(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch,
+                                 const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes, size_t sig_len, const uint8_t *d_msgs,
+                                 const uint64_t *d_msg_off, const uint64_t *d_rs, int wire_mode, uint8_t *d_wire, uint64_t *d_proofs,
+                                 uint64_t *d_instance, int32_t *d_status, uint32_t *d_num_unsatisfied, void *d_workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    if (bad_pok_prove(ctx, circuit, logn, wire_mode, sig_len)) return FRW_E_INVALID_ARG;
+    if (!pk || !r || !d_pk_bytes || !d_sig_bytes || !d_msgs || !d_msg_off || !d_rs || !d_wire || !d_status || !d_workspace)
+        return FRW_E_INVALID_ARG;
+    if ((uintptr_t)d_workspace & 255) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    size_t W = 0;
+    if (!pok_prove_shape(pk, r, circuit, logn, &W) || frw::r1cs_device(r) != ctx->device) return FRW_E_INVALID_ARG;
+    const auto size = [&](size_t k) { return frw::pok_prove_layout(nullptr, logn, batch, k, W, frw_groth16_workspace_bytes(pk, r, k)).bytes; };
+    if (frw_groth16_workspace_bytes(pk, r, 1) == 0) return FRW_E_INVALID_ARG;
+    const size_t k = frw::proofs_in_flight(std::min(batch, POK_PROVE_MAX_IN_FLIGHT), workspace_bytes, size);
+    if (k == 0) return FRW_E_INVALID_ARG;
+    const frw::PokProveBufs ws = frw::pok_prove_layout(d_workspace, logn, batch, k, W, frw_groth16_workspace_bytes(pk, r, k));
+    const int wire_len = (int)frw_groth16_proof_wire_bytes(wire_mode), inst_words = (int)(((size_t)2 << logn) + 1) * 4;
+    hipStream_t st = (hipStream_t)stream;
+    FRW_HIP(hipSetDevice(ctx->device));
+    // decode, hash and screen: d_status is frw_falcon_verify_from_bytes_dev's, word for word
+    FRW_HIP(falcon_verify_chain(ctx, logn, batch, d_pk_bytes, d_sig_bytes, sig_len, d_msgs, d_msg_off, FRW_RULE_CIRCUIT, d_status, nullptr,
+                                ws.screen.sig, st));
+    // the accepted slots, in slot order, and how many they are -- the one value the host needs (chunks are host loops): one wait
+    FRW_HIP(frw::launch_pok_scan(batch, d_status, ws.block_sums, ws.index, ws.count, st));
+    FRW_HIP(frw::launch_pok_zero_refused(batch, d_status, wire_len, inst_words, d_wire, d_proofs, d_instance, d_num_unsatisfied, st));
+    uint32_t count = 0;
+    FRW_HIP(hipMemcpyAsync(&count, ws.count, sizeof count, hipMemcpyDeviceToHost, st));
+    FRW_HIP(hipStreamSynchronize(st));
+    if (count > batch) return FRW_E_HIP;                                  // (cannot happen: the index list has `batch` entries)
+    FRW_HIP(frw::launch_pok_gather_rs(count, ws.index, d_rs, ws.rs, st));
+    for (size_t lo = 0; lo < count; lo += k) {
+        const size_t cnt = std::min<size_t>(k, count - lo);
+        const uint32_t *index = ws.index + lo;
+        FRW_HIP(frw::launch_pok_gather_inputs(logn, cnt, index, ws.screen.sig, ws.screen.pk, ws.screen.hm, ws.sig, ws.pk, ws.hm, st));
+        if (circuit == FRW_CIRCUIT_SCHOOLBOOK)
+            FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
+                                                          ws.witness, ws.instance, ws.witness_status, st));
+        else if (circuit == FRW_CIRCUIT_DUAL_NTT)
+            FRW_HIP(frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
+                                                        ws.witness, ws.instance, ws.witness_status, st));
+        else
+            FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
+                                                   ws.witness, ws.instance, ws.witness_status, st));
+        int rc = frw_groth16_prove_rs_dev(pk, r, cnt, ws.witness, ws.instance, ws.rs + lo * 8, ws.proofs, ws.unsatisfied, ws.groth16_ws,
+                                          ws.groth16_bytes, st);
+        if (rc == FRW_OK) rc = frw_groth16_proofs_to_wire_dev(ctx->device, cnt, ws.proofs, wire_mode, ws.wire, ws.wire_status, st);
+        if (rc != FRW_OK) return rc;
+        FRW_HIP(frw::launch_pok_scatter(cnt, index, wire_len, inst_words, ws.wire, ws.proofs, ws.instance, ws.unsatisfied, d_wire, d_proofs,
+                                        d_instance, d_num_unsatisfied, st));
+    }
+    return FRW_OK;
+}
+
+int frw_pok_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch,
+                             const uint8_t *pk_bytes, const uint8_t *sig_bytes, size_t sig_len, const uint8_t *msgs,
+                             const uint64_t *msg_off, const uint64_t *rs, int wire_mode, uint8_t *wire, uint64_t *proofs,
+                             uint64_t *instance, int32_t *status, uint32_t *num_unsatisfied, int strict)
+{
+    if (bad_pok_prove(ctx, circuit, logn, wire_mode, sig_len)) return FRW_E_INVALID_ARG;
+    if (!pk || !r || !pk_bytes || !sig_bytes || !msgs || !msg_off || !rs || !wire || !status) return FRW_E_INVALID_ARG;
+    for (size_t i = 0; i < batch; i++)
+        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (batch == 0) return FRW_OK;
+    size_t W = 0;
+    if (!pok_prove_shape(pk, r, circuit, logn, &W) || frw::r1cs_device(r) != ctx->device) return FRW_E_INVALID_ARG;
+    frw::HostArena &A = ctx->arena;
+    std::lock_guard<std::mutex> lock(A.mu);
+    frw::DrainOnExit drain(A);
+    FRW_HIP(hipSetDevice(ctx->device));
+    const size_t pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, POK_PROVE_CHUNK), ibytes = (((size_t)2 << logn) + 1) * 32;
+    const size_t wire_len = frw_groth16_proof_wire_bytes(wire_mode);
+    size_t max_msg = 1;                                                   // the longest pass's message bytes
+    for (size_t lo = 0; lo < batch; lo += chunk)
+        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
+    // the staged inputs' layout == their device layout: ONE copy in per pass
+    frw::Carve hs(nullptr);
+    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
+    const size_t o_sigb = hs.off; hs.take(chunk * sig_len);
+    const size_t o_msgs = hs.off; hs.take(max_msg);
+    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
+    const size_t o_rs = hs.off; hs.take(chunk * 64);
+    const size_t in_total = hs.off;
+    const size_t ws_bytes = frw_pok_prove_workspace_bytes(pk, r, circuit, logn, chunk, std::min(chunk, POK_PROVE_HOST_IN_FLIGHT));
+    if (ws_bytes == 0) return FRW_E_INVALID_ARG;
+    frw::Carve c(nullptr);
+    c.take(in_total);
+    const size_t o_ws = c.off;   c.take(ws_bytes);
+    const size_t o_wire = c.off; c.take(chunk * wire_len);
+    const size_t o_prf = c.off;  c.take(chunk * 384);
+    const size_t o_inst = c.off; c.take(instance ? chunk * ibytes : 0);
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    const size_t o_uns = c.off;  c.take(chunk * sizeof(uint32_t));
+    FRW_HIP(A.reserve_device(0, c.off));
+    FRW_HIP(A.reserve_pinned(in_total));
+    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
+    hipStream_t st = A.compute;
+    for (size_t lo = 0; lo < batch; lo += chunk) {
+        const size_t cnt = std::min(chunk, batch - lo);
+        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
+        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
+        memcpy(h + o_sigb, sig_bytes + lo * sig_len, cnt * sig_len);
+        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
+        uint64_t *off = (uint64_t *)(h + o_off);
+        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
+        memcpy(h + o_rs, rs + lo * 8, cnt * 64);
+        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
+        const int rc = frw_pok_prove_from_bytes_dev(ctx, pk, r, circuit, logn, cnt, (const uint8_t *)(d + o_pkb), (const uint8_t *)(d + o_sigb),
+                                                    sig_len, (const uint8_t *)(d + o_msgs), (const uint64_t *)(d + o_off),
+                                                    (const uint64_t *)(d + o_rs), wire_mode, (uint8_t *)(d + o_wire),
+                                                    proofs ? (uint64_t *)(d + o_prf) : nullptr, instance ? (uint64_t *)(d + o_inst) : nullptr,
+                                                    (int32_t *)(d + o_st), num_unsatisfied ? (uint32_t *)(d + o_uns) : nullptr, d + o_ws,
+                                                    ws_bytes, st);
+        if (rc != FRW_OK) return rc;
+        FRW_HIP(hipMemcpyAsync(wire + lo * wire_len, d + o_wire, cnt * wire_len, hipMemcpyDeviceToHost, st));
+        if (proofs) FRW_HIP(hipMemcpyAsync(proofs + lo * 48, d + o_prf, cnt * 384, hipMemcpyDeviceToHost, st));
+        if (instance) FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (num_unsatisfied) FRW_HIP(hipMemcpyAsync(num_unsatisfied + lo, d + o_uns, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
+    }
+    drain.settled = true;
+    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+}
+
 int frw_gadget_block_len(int kind)
 {
     static const int len[6] = {27, 29, 29, 18, 50, 52};

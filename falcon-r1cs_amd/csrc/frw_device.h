@@ -104,6 +104,20 @@ hipError_t launch_hash_to_point(int logn, size_t batch, const uint8_t *nonces, c
 hipError_t launch_decode_public_keys(int logn, size_t batch, const uint8_t *pk_bytes, uint16_t *pk, int32_t *status, hipStream_t st);
 hipError_t launch_decode_signatures(int logn, size_t batch, const uint8_t *sig_bytes, size_t sig_len, uint16_t *sig,
                                     uint8_t *nonce_out, int32_t *status, hipStream_t st);
+// compaction for the prover from bytes (frw_prepare.hip).  launch_pok_scan: index[0 .. count) = the slots whose status is FRW_ST_OK, in
+// slot order, count[0] = their number (block_sums: one word per BLOCK slots of scratch; any batch).  The gathers make the blinding
+// factors of all accepted slots and the (sig, pk, hm) rows of one chunk of them dense; launch_pok_zero_refused writes zeros to every output
+// of every refused slot, launch_pok_scatter result j of a chunk to slot index[j].  wire_len bytes and inst_words uint64_t per slot;
+// proofs, instance and unsatisfied may be null (not asked for).
+hipError_t launch_pok_scan(size_t batch, const int32_t *status, uint32_t *block_sums, uint32_t *index, uint32_t *count, hipStream_t st);
+hipError_t launch_pok_gather_rs(size_t count, const uint32_t *index, const uint64_t *rs, uint64_t *dense_rs, hipStream_t st);
+hipError_t launch_pok_gather_inputs(int logn, size_t cnt, const uint32_t *index, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
+                                    uint16_t *sig_out, uint16_t *pk_out, uint16_t *hm_out, hipStream_t st);
+hipError_t launch_pok_zero_refused(size_t batch, const int32_t *status, int wire_len, int inst_words, uint8_t *wire, uint64_t *proofs,
+                                   uint64_t *instance, uint32_t *unsatisfied, hipStream_t st);
+hipError_t launch_pok_scatter(size_t cnt, const uint32_t *index, int wire_len, int inst_words, const uint8_t *wire_in,
+                              const uint64_t *proofs_in, const uint64_t *instance_in, const uint32_t *unsatisfied_in, uint8_t *wire,
+                              uint64_t *proofs, uint64_t *instance, uint32_t *unsatisfied, hipStream_t st);
 // R1CS matrices resident on the device (frw_r1cs_load): CSR, coefficients in Montgomery form (8 x u32)
 struct R1csMatrixDev {
     const uint64_t *row_ptr;    // num_constraints + 1
@@ -199,6 +213,8 @@ struct R1csAgg {
 };
 // an aggregate handle's description and device (frw_r1cs.cpp); null for a per-signature handle
 const R1csAgg *r1cs_aggregate(const ::frw_r1cs *r, int *device);
+// the device any handle's matrices are on
+int r1cs_device(const ::frw_r1cs *r);
 size_t r1cs_check_scratch_bytes(const R1csDev &r, size_t batch, bool with_abc);
 hipError_t launch_r1cs_check(const R1csDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance,
                              uint32_t *num_unsatisfied, uint64_t *abc, hipStream_t st, void *scratch = nullptr);

@@ -322,6 +322,60 @@ inline FalconVerifyBufs falcon_verify_layout(void *ws, int logn, size_t batch)
     b.bytes = c.off;
     return b;
 }
+// ---- the prover from bytes (frw_pok_prove_from_bytes_dev).  A fixed part proportional to `batch`: the screen's own workspace (the
+// layout above: decoded arrays, nonces, both decoders' statuses), the accepted slots' indices in slot order, one word per block of
+// POK_SCAN_BLOCK slots for the scan, the count (a piece of 16 bytes: the one value the host reads), and the accepted slots' blinding
+// factors, dense.  Then, from a 256-byte boundary, `k` times a per-signature part -- the witness (num_witness elements), the instance
+// vector, the gathered sig, pk, hm rows, the proof's limbs, its wire bytes (384: the longer mode's, the size does not depend on the
+// mode), the witness kernel's and the encoder's status words and the prover's count of violated rows -- and, 256-byte aligned again, the
+// Groth16 prover's workspace for k proofs in flight (groth16_bytes = frw_groth16_workspace_bytes(pk, r, k)).  Every piece is rounded up to
+// 16 bytes at least.
+constexpr size_t POK_SCAN_BLOCK = 256;           // slots per workgroup of the scan kernels (== BLOCK of frw_device.h)
+constexpr size_t POK_WIRE_STAGE = 384;           // staged wire bytes per proof: FRW_WIRE_UNCOMPRESSED's
+struct PokProveBufs {
+    FalconVerifyBufs screen;
+    uint32_t *index, *block_sums, *count;
+    uint64_t *rs;
+    uint64_t *witness, *instance;
+    uint16_t *sig, *pk, *hm;
+    uint64_t *proofs;
+    uint8_t *wire;
+    int32_t *witness_status, *wire_status;
+    uint32_t *unsatisfied;
+    void *groth16_ws;
+    size_t fixed_bytes, per_signature_bytes, groth16_bytes, bytes;
+};
+inline PokProveBufs pok_prove_layout(void *ws, int logn, size_t batch, size_t k, size_t num_witness, size_t groth16_bytes)
+{
+    PokProveBufs b{};
+    Carve c(ws);
+    const size_t n = (size_t)1 << logn;
+    b.screen = falcon_verify_layout(c.at(), logn, batch);
+    c.take(b.screen.bytes, 16);
+    b.index = c.take<uint32_t>(batch * 4, 16);
+    b.block_sums = c.take<uint32_t>((batch + POK_SCAN_BLOCK - 1) / POK_SCAN_BLOCK * 4, 16);
+    b.count = c.take<uint32_t>(16, 16);
+    b.rs = c.take<uint64_t>(batch * 64, 16);
+    b.fixed_bytes = c.off;
+    c.align_to(256);
+    const size_t per0 = c.off;
+    b.witness = c.take<uint64_t>(k * num_witness * 32, 256);
+    b.instance = c.take<uint64_t>(k * (2 * n + 1) * 32, 16);
+    b.sig = c.take<uint16_t>(k * n * 2, 16);
+    b.pk = c.take<uint16_t>(k * n * 2, 16);
+    b.hm = c.take<uint16_t>(k * n * 2, 16);
+    b.proofs = c.take<uint64_t>(k * 384, 16);
+    b.wire = c.take<uint8_t>(k * POK_WIRE_STAGE, 16);
+    b.witness_status = c.take<int32_t>(k * 4, 16);
+    b.wire_status = c.take<int32_t>(k * 4, 16);
+    b.unsatisfied = c.take<uint32_t>(k * 4, 16);
+    b.per_signature_bytes = c.off - per0;          // (of all k)
+    c.align_to(256);
+    b.groth16_ws = c.take(groth16_bytes, 256);
+    b.groth16_bytes = groth16_bytes;
+    b.bytes = c.off;
+    return b;
+}
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
 {

@@ -492,6 +492,8 @@ const frw::R1csAgg *frw::r1cs_aggregate(const frw_r1cs *r, int *device)
     return &r->agg;
 }
 
+int frw::r1cs_device(const frw_r1cs *r) { return r->device; }
+
 extern "C" int frw_r1cs_info(const frw_r1cs *r, frw_r1cs_info_t *out)
 {
     if (!r || !out) return FRW_E_INVALID_ARG;

@@ -876,6 +876,77 @@ class WitnessEngine:
               "frw_falcon_verify_from_bytes_dev")
         return d_status, d_norm
 
+    # ---- the prover from bytes: encoded signatures in, proofs on the wire out ---------------------------------------------------------
+    def pok_prove_workspace_bytes(self, pk, r1cs, circuit, logn, batch, in_flight):
+        """Bytes of frw_pok_prove_from_bytes_dev's workspace for `batch` slots with `in_flight` proofs in flight (0: the handles are not
+        that circuit's, or a bad argument)."""
+        return int(self._lib.frw_pok_prove_workspace_bytes(pk, r1cs, int(circuit), int(logn), int(batch), int(in_flight)))
+
+    def pok_prove_from_bytes(self, pk, r1cs, circuit, logn, pk_bytes, sig_bytes, msgs, rs, compressed=True, strict=True, want_proofs=True,
+                             want_instance=True):
+        """Host buffers (frw_pok_prove_from_bytes): lists of encoded public keys, encoded signatures of one common length and messages,
+        rs uint64[batch, 2, 4] -> dict(wire uint8[batch, 192 | 384], proofs uint64[batch, 48] or None, instance uint64[batch, 2 N + 1, 4]
+        or None, status int32[batch], num_unsatisfied uint32[batch]).  A refused slot (status != 0) is all zeros in every output."""
+        batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
+        rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
+        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+        out = {"wire": np.zeros((batch, proof_wire_bytes(compressed)), dtype=np.uint8),
+               "proofs": np.zeros((batch, 48), dtype=np.uint64) if want_proofs else None,
+               "instance": np.zeros((batch, (2 << logn) + 1, 4), dtype=np.uint64) if want_instance else None,
+               "status": np.zeros(batch, dtype=np.int32), "num_unsatisfied": np.zeros(batch, dtype=np.uint32)}
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        rc = self._lib.frw_pok_prove_from_bytes(self._ctx, pk, r1cs, int(circuit), int(logn), batch, p(pkb), p(sgb), sig_len, p(blob), p(off),
+                                                p(rs), mode, p(out["wire"]), p(out["proofs"]), p(out["instance"]), p(out["status"]),
+                                                p(out["num_unsatisfied"]), 1 if strict else 0)
+        if rc == E_RANGE:
+            st = out["status"]
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, "frw_pok_prove_from_bytes", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        check(rc, "frw_pok_prove_from_bytes")
+        return out
+
+    def pok_prove_from_bytes_dev(self, pk, r1cs, circuit, logn, pk_bytes, sig_bytes, msgs, rs, compressed=True, in_flight=None, workspace=None,
+                                 want_proofs=True, want_instance=True, want_unsatisfied=True, stream=0, sig_len=None):
+        """The same on the device (frw_pok_prove_from_bytes_dev) -> dict of device tensors: wire uint8[batch, 192 | 384], proofs
+        int64[batch, 48], instance int64[batch, 2 N + 1, 4], status int32[batch], num_unsatisfied int32[batch] (None where not asked
+        for).  The inputs as for falcon_verify_from_bytes_dev (lists of bytes, or device tensors with msgs a (blob, offsets) pair); rs:
+        uint64[batch, 2, 4] on the host or an int64 device tensor.  workspace: a uint8 device tensor (256-byte aligned, as torch's
+        are), or None for one that holds `in_flight` proofs (default: min(batch, 4)).  The call waits on `stream` once, for the number
+        of accepted signatures; its results are ordered on `stream` and not synchronised."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(pk_bytes, torch.Tensor):
+            d_pkb, d_sgb, (d_blob, d_off) = pk_bytes, sig_bytes, msgs
+            batch = d_pkb.numel() // PK_LEN[logn]
+            if sig_len is None:
+                sig_len = d_sgb.numel() // batch if batch else SIG_LEN[logn]
+        else:
+            batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
+            d_pkb, d_sgb, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, sgb, blob))
+            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        if isinstance(rs, torch.Tensor):
+            d_rs = rs
+        else:
+            rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
+            d_rs = torch.from_numpy(rs.view(np.int64).copy()).to(dev) if batch else torch.zeros(8, dtype=torch.int64, device=dev)
+        wire_len = proof_wire_bytes(compressed)
+        rows = max(batch, 1)                    # (an empty tensor has no address: the call refuses null pointers whatever the batch)
+        out = {"wire": torch.empty((rows, wire_len), dtype=torch.uint8, device=dev),
+               "proofs": torch.empty((rows, 48), dtype=torch.int64, device=dev) if want_proofs else None,
+               "instance": torch.empty((rows, (2 << logn) + 1, 4), dtype=torch.int64, device=dev) if want_instance else None,
+               "status": torch.empty(rows, dtype=torch.int32, device=dev),
+               "num_unsatisfied": torch.empty(rows, dtype=torch.int32, device=dev) if want_unsatisfied else None}
+        if workspace is None:
+            k = max(1, min(batch, 4) if in_flight is None else int(in_flight))
+            workspace = torch.empty(max(self.pok_prove_workspace_bytes(pk, r1cs, circuit, logn, batch, k), 256), dtype=torch.uint8, device=dev)
+        P = lambda t: self._ptr(t) if t is not None else None
+        check(self._lib.frw_pok_prove_from_bytes_dev(self._ctx, pk, r1cs, int(circuit), int(logn), batch, self._ptr(d_pkb), self._ptr(d_sgb),
+                                                     int(sig_len), self._ptr(d_blob), self._ptr(d_off), self._ptr(d_rs),
+                                                     WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, P(out["wire"]), P(out["proofs"]),
+                                                     P(out["instance"]), P(out["status"]), P(out["num_unsatisfied"]), self._ptr(workspace),
+                                                     workspace.numel(), C.c_void_p(stream)), "frw_pok_prove_from_bytes_dev")
+        return {k: (v[:batch] if v is not None else None) for k, v in out.items()}
+
     def groth16_setup_r1cs(self, handle, alpha, beta, gamma, delta, t, mode=KEY_AUTO, rank=0, world=1, want_vk=True):
         """groth16_setup for the system behind an r1cs handle (a per-signature circuit or an aggregate statement).
         mode: KEY_TABLES (window tables), KEY_BARE (the points only, made on the device end to end), KEY_AUTO by size;

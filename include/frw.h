@@ -917,6 +917,61 @@ int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uin
                                  size_t sig_len, const uint8_t *msgs, const uint64_t *msg_off, int rule, int32_t *status,
                                  uint64_t *norm, int strict);
 
+/* ---- the prover from bytes: encoded Falcon signatures in, Groth16 proofs on the wire out -----------------------------------
+ * The prover's half of examples/pok_sig.rs (:21-32 and Proof::serialize) as ONE call: what a caller otherwise chains from
+ * frw_prepare_inputs, a screen, frw_witness_*_dev, frw_groth16_prove_rs_dev, frw_groth16_proofs_to_wire_dev and a statement call,
+ * with the witness buffers, the compaction of the accepted signatures and the chunking done here.  For a batch, on `stream`:
+ *   1. both decoders and SHAKE256 into the workspace, then the Falcon verification kernel under FRW_RULE_CIRCUIT with the
+ *      decoders' statuses as verdicts already reached: d_status[i] is exactly the word frw_falcon_verify_from_bytes_dev writes;
+ *   2. an order-preserving scan over the statuses lists the accepted slots (any batch: three small launches); every output of every
+ *      refused slot is zero-filled;
+ *   3. THE ONE HOST WAIT: the number of accepted slots is copied to the host and `stream` is synchronised (hipStreamSynchronize) --
+ *      the chunk loop below is a host loop and the witness and prover launches are sized by it.  So the call also waits for
+ *      whatever `stream` held before, and like frw_groth16_prove_dev it is NOT stream-capture safe;
+ *   4. for each chunk of at most k accepted signatures: their (sig, pk, hm) rows are gathered, the circuit's witness kernel
+ *      (FRW_ENC_MONTGOMERY) fills the workspace, then the prover of frw_groth16_prove_rs_dev and the wire encoder run on it, and
+ *      a scatter writes every result into its slot.  k = the most proofs in flight the caller's workspace holds (at most 4,096).
+ *     circuit, logn   FRW_CIRCUIT_*, 9 | 10: must be what `r` was loaded for, and `pk` a whole key over `r`
+ *     d_pk_bytes, d_sig_bytes, sig_len, d_msgs, d_msg_off   as for frw_falcon_verify_from_bytes_dev
+ *     d_rs            uint64_t[batch][2][4]: the blinding factors of slot i at d_rs[i], as for frw_groth16_prove_rs_dev (a refused
+ *                     slot's are not read)
+ *     d_wire          batch x frw_groth16_proof_wire_bytes(wire_mode) bytes, any alignment
+ *     d_proofs        (may be NULL) uint64_t[batch][48], the limbs frw_groth16_prove_rs_dev writes
+ *     d_instance      (may be NULL) uint64_t[batch][2 N + 1][4], FRW_ENC_MONTGOMERY: the verifier's statement
+ *     d_status        int32_t[batch], FRW_ST_*; FRW_ST_OK: the slot holds a proof
+ *     d_num_unsatisfied  (may be NULL) uint32_t[batch]: the prover's count of violated rows (0 for every accepted slot)
+ *     d_workspace     256-byte aligned, at least frw_pok_prove_workspace_bytes(pk, r, circuit, logn, batch, 1) bytes; with
+ *                     (..., batch, in_flight) bytes, in_flight proofs are in flight at a time.  The layout (csrc/frw_layout.h
+ *                     pok_prove_layout): a part proportional to batch (the screen's workspace, the index list, the scan's words, the
+ *                     count, the dense blinding factors), in_flight times a per-signature part (witness, instance, gathered inputs,
+ *                     limbs, wire bytes, status words) and frw_groth16_workspace_bytes(pk, r, in_flight)
+ * THE CONTRACT: the bytes written for slot i depend only on slot i's inputs and d_rs[i] -- not on the batch, on which neighbours
+ * were refused, or on the workspace's size.  An accepted slot holds byte for byte what the chained calls give for that signature
+ * alone with the same (r, s); a refused slot holds zero bytes in every output (a zero instance vector has instance[0] != 1 and
+ * zero wire bytes are no encoding of a proof: every verifier above reports -1), never stale memory; nothing beyond `batch` entries
+ * of any output is written.
+ * A batch with nothing accepted launches no witness or prover kernel and returns FRW_OK.  Allocates nothing.
+ * FRW_E_INVALID_ARG before any device work: logn outside {9, 10}, an unknown circuit or wire mode, sig_len <= 41, a null pointer
+ * other than d_proofs / d_instance / d_num_unsatisfied, a workspace that is not 256-byte aligned; then batch = 0 is a no-op
+ * (FRW_OK; the handles are not looked at); then: circuit / logn that are not the handle's (its I, W, C: frw_r1cs_info), an
+ * aggregate handle, a key for another system or in slices (world > 1), ctx, pk and r on different devices, a workspace smaller
+ * than that of one proof in flight.  frw_pok_prove_workspace_bytes returns 0 for the same mismatches, for a null handle and for
+ * in_flight = 0.
+ * frw_pok_prove_from_bytes: the same with HOST pointers for every array (rs, the outputs and the statuses too), through the
+ * context's arena 256 slots at a time with up to 8 proofs in flight; decreasing message offsets -> FRW_E_INVALID_ARG; with
+ * strict != 0 it returns FRW_E_RANGE if any status is non-zero (all outputs are complete all the same). */
+size_t frw_pok_prove_workspace_bytes(const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch,
+                                     size_t in_flight);
+int frw_pok_prove_from_bytes_dev(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch,
+                                 const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes, size_t sig_len, const uint8_t *d_msgs,
+                                 const uint64_t *d_msg_off, const uint64_t *d_rs, int wire_mode, uint8_t *d_wire,
+                                 uint64_t *d_proofs, uint64_t *d_instance, int32_t *d_status, uint32_t *d_num_unsatisfied,
+                                 void *d_workspace, size_t workspace_bytes, void *stream);
+int frw_pok_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t batch,
+                             const uint8_t *pk_bytes, const uint8_t *sig_bytes, size_t sig_len, const uint8_t *msgs,
+                             const uint64_t *msg_off, const uint64_t *rs, int wire_mode, uint8_t *wire, uint64_t *proofs,
+                             uint64_t *instance, int32_t *status, uint32_t *num_unsatisfied, int strict);
+
 /* ---- stand-alone gadget blocks ---------------------------------------------------------------
  * The reference's gadget functions are also called outside the full circuit (its unit tests do; so can any
  * other circuit built from them).  One call fills the witness block of `count` independent gadget invocations,

@@ -389,6 +389,18 @@ extern "C" {
     pub fn frw_falcon_verify_from_bytes(ctx: *mut frw_ctx, logn: c_int, batch: usize, pk_bytes: *const u8, sig_bytes: *const u8,
                                         sig_len: usize, msgs: *const u8, msg_off: *const u64, rule: c_int, status: *mut i32,
                                         norm: *mut u64, strict: c_int) -> c_int;
+    pub fn frw_pok_prove_workspace_bytes(pk: *const frw_groth16_pk, r: *const frw_r1cs, circuit: c_int, logn: c_int, batch: usize,
+                                         in_flight: usize) -> usize;
+    pub fn frw_pok_prove_from_bytes_dev(ctx: *mut frw_ctx, pk: *const frw_groth16_pk, r: *const frw_r1cs, circuit: c_int, logn: c_int,
+                                        batch: usize, d_pk_bytes: *const u8, d_sig_bytes: *const u8, sig_len: usize,
+                                        d_msgs: *const u8, d_msg_off: *const u64, d_rs: *const u64, wire_mode: c_int,
+                                        d_wire: *mut u8, d_proofs: *mut u64, d_instance: *mut u64, d_status: *mut i32,
+                                        d_num_unsatisfied: *mut u32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                        stream: *mut c_void) -> c_int;
+    pub fn frw_pok_prove_from_bytes(ctx: *mut frw_ctx, pk: *const frw_groth16_pk, r: *const frw_r1cs, circuit: c_int, logn: c_int,
+                                    batch: usize, pk_bytes: *const u8, sig_bytes: *const u8, sig_len: usize, msgs: *const u8,
+                                    msg_off: *const u64, rs: *const u64, wire_mode: c_int, wire: *mut u8, proofs: *mut u64,
+                                    instance: *mut u64, status: *mut i32, num_unsatisfied: *mut u32, strict: c_int) -> c_int;
     pub fn frw_gadget_block_len(kind: c_int) -> c_int;
     pub fn frw_gadget_dev(ctx: *mut frw_ctx, kind: c_int, count: usize, d_a: *const c_void, d_b: *const u64,
                           encoding: c_int, d_out: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;

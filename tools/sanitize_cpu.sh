@@ -42,3 +42,7 @@ g++ -O1 -g -std=c++17 -shared -fPIC -fsanitize=address,undefined -fno-sanitize-r
 (cd "$ROOT" && FRW_TEST_FQ29_SO="$SO" ASAN_OPTIONS=detect_leaks=0 LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) \
     python -m pytest tests/test_fq29_host.py -x -q 2>&1 | tail -1)
 echo "fq29 / quad headers: clean"
+# the workspace layout of the prover from bytes (frw_layout.h pok_prove_layout): a program of its own that carves real memory by it
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" \
+    -o /tmp/frw_pok_prove_layout_asan "$ROOT/tests/cpp/test_pok_prove_layout.cpp"
+ASAN_OPTIONS=detect_leaks=0 /tmp/frw_pok_prove_layout_asan | tail -1

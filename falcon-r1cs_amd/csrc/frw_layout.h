@@ -292,6 +292,27 @@ inline VerifyBufs verify_layout(void *ws, size_t k, size_t msm_per, bool bare, s
     v.bytes = c.off;
     return v;
 }
+// ---- re-randomising proofs (frw_rerand.hip), `k` proofs in flight: the sixteen scalar words of a proof (the split halves of r1^-1 and
+// r2, then r1 and r1 r2), A' and C' as the ladders leave them (G1, XYZZ: two buckets a proof), B' likewise (G2), and for the wire form
+// the decoded limbs, which the chain re-randomises in place, with the decoder's and the encoder's statuses.  The proofs' own statuses
+// live in the caller's array.  Every piece is rounded up to 16 bytes.
+struct RerandBufs { uint64_t *scalars; uint32_t *g1_points, *g2_points; uint64_t *decoded; int32_t *decode_status, *encode_status; size_t bytes; };
+constexpr size_t RERAND_SCALAR_BYTES = 128;
+inline RerandBufs rerand_layout(void *ws, size_t k, bool wire)
+{
+    RerandBufs b{};
+    Carve c(ws);
+    b.scalars = c.take<uint64_t>(k * RERAND_SCALAR_BYTES, 16);
+    b.g1_points = c.take<uint32_t>(k * 2 * (size_t)G1_BK_WORDS * 4, 16);
+    b.g2_points = c.take<uint32_t>(k * (size_t)G2_BK_WORDS * 4, 16);
+    if (wire) {
+        b.decoded = c.take<uint64_t>(k * 384, 16);
+        b.decode_status = c.take<int32_t>(k * 4, 16);
+        b.encode_status = c.take<int32_t>(k * 4, 16);
+    }
+    b.bytes = c.off;
+    return b;
+}
 // ---- the verifier's statement from bytes (frw_statement_from_bytes_dev): the decoded public keys and the hashed messages as uint16_t
 // [batch][N] each, 16-byte aligned, and the key decoder's statuses, which the statement kernel reads before it looks at a coefficient
 struct StatementBufs { uint16_t *pk, *hm; int32_t *decode_status; size_t bytes; };

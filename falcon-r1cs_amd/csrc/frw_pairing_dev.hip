@@ -365,6 +365,7 @@ __device__ inline pairing::G2 g2_strict_from_ark(const uint64_t *w)
     return p;
 }
 // status[g] = -1 where check_proof would refuse proof g.  Two lanes per proof: A (even lane) or C (odd lane), then B over both.
+// (frw_rerand.hip's rerand_check_kernel is this kernel's twin: change them together.)
 __global__ __launch_bounds__(64) void proof_check_kernel(uint64_t n, const uint64_t *__restrict__ proofs, int check_subgroup, int32_t *__restrict__ status)
 {
     const uint64_t g = ((uint64_t)blockIdx.x * 64 + threadIdx.x) >> 1;

@@ -98,6 +98,7 @@ int frw::verify::vk_load(const uint64_t *vk, size_t num_instance, bool check_gam
         if (!ok) { delete k; return FRW_E_INVALID_ARG; }
         k->gamma_neg = g2_neg(gamma);
         k->delta_neg = g2_neg(delta);
+        std::memcpy(k->delta_ark, vk + 60, sizeof(k->delta_ark));
         const G1 a = g1_strict(alpha);
         k->alpha_beta = final_exponentiation(miller_loop(&a, &beta, 1), k->fc);
     } catch (...) {

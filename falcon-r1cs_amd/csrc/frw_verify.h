@@ -21,10 +21,13 @@ struct frw_groth16_vk {
     frw_msm *msm = nullptr;                 // ... and gamma_abc_g1 there, as a narrow MSM handle (frw_verify_dev.hip says which kind)
     uint32_t *d_pairing = nullptr;          // ... and the device pairing's fixed part there (frw_pairing_dev.hip: line tables, constants)
     unsigned pairing_inf = 0;               // ... bit j: the fixed G2 point j (-gamma, -delta, beta) is the point at infinity
+    uint64_t delta_ark[24] = {};            // delta_g2 as the key gave it (ark-ff's limbs): what frw_groth16_rerandomize adds multiples of
+    uint64_t *d_delta = nullptr;            // frw_groth16_vk_load_dev: ... and the same 24 words on the device (frw_rerand.hip)
     ~frw_groth16_vk()
     {
         if (msm) frw_msm_free(msm);
         if (d_pairing) (void)hipFree(d_pairing);
+        if (d_delta) (void)hipFree(d_delta);
     }
 };
 

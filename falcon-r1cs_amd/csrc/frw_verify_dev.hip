@@ -22,6 +22,7 @@
 #include "frw_device.h"
 #include "frw_layout.h"
 #include "frw_pairing_dev.h"
+#include "frw_rerand.h"
 #include "frw_verify.h"
 #include "frw_wire.h"
 
@@ -143,6 +144,7 @@ extern "C" int frw_groth16_vk_load_dev(int device, const uint64_t *vk, size_t nu
     k->msm = m;
     // the device pairing's fixed part: -gamma, -delta and beta's line tables, the Frobenius constants, e(alpha, beta)^3
     rc = frw::pairing_dev::upload_key(k, vk, vk + 12);
+    if (rc == FRW_OK) rc = frw::rerand::upload_key(k);             // delta_g2 for frw_groth16_rerandomize_dev
     if (rc != FRW_OK) {
         frw_groth16_vk_free(k);
         return rc;

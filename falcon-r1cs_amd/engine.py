@@ -109,6 +109,7 @@ def synth_triples(logn, batch, seed=0x46414C434F4E, first_index=0):
 
 VERIFY_POINTS_ARE_CHECKED = 1
 VERIFY_BATCHED = 2
+RERAND_ZERO_FACTOR = -2                            # frw.h FRW_RERAND_ZERO_FACTOR
 VK_POINTS_ARE_CHECKED = 1
 KEY_AUTO, KEY_TABLES, KEY_BARE = 0, 1, 2           # frw.h FRW_KEY_*: window tables, or the points only (keys that would not fit)
 GROTH16_PARTIAL_WORDS = 72
@@ -286,6 +287,67 @@ class Groth16Verifier:
         d_inst, d_status = engine.statement_from_bytes_dev(circuit, logn, pk_bytes, nonces, msgs, ENC_MONTGOMERY, stream)
         verdicts = self.verify_wire_dev(d_inst, d_wire, compressed, ENC_MONTGOMERY, flags, batched, seed, stream)
         return d_status, verdicts
+
+    def rerandomize(self, proofs, factors, flags=0):
+        """ark-groth16's rerandomize_proof on the host (frw_groth16_rerandomize): A' = A / r1, B' = r1 B + r1 r2 delta_g2,
+        C' = C + r2 A.  proofs: uint64[batch, 48]; factors: uint64[batch, 2, 4], r1 and r2 of every proof, any 256-bit values (taken
+        modulo the group order).  Returns (proofs uint64[batch, 48], status int32[batch]): 0, -1 for a malformed proof, RERAND_ZERO_FACTOR
+        where r1 or r2 is zero; a refused slot is all zero.  The new proofs are unlinkable to the old ones only for factors that are
+        uniform, secret and fresh."""
+        proofs = np.ascontiguousarray(proofs).view(np.uint64).reshape(-1, 48)
+        batch = proofs.shape[0]
+        factors = np.ascontiguousarray(factors).view(np.uint64).reshape(batch, 2, 4)
+        out = np.zeros((batch, 48), dtype=np.uint64)
+        status = np.zeros(batch, dtype=np.int32)
+        check(self._lib.frw_groth16_rerandomize(self._h, batch, proofs.ctypes.data_as(C.c_void_p), factors.ctypes.data_as(C.c_void_p), int(flags),
+                                                out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_rerandomize")
+        return out, status
+
+    def rerandomize_workspace_bytes(self, in_flight, wire_mode=None):
+        """Device workspace of rerandomize_dev (wire_mode None) or rerandomize_wire_dev (WIRE_COMPRESSED / WIRE_UNCOMPRESSED) for
+        `in_flight` proofs."""
+        return int(self._lib.frw_groth16_rerandomize_workspace_bytes(self._h, int(in_flight), -1 if wire_mode is None else int(wire_mode)))
+
+    def rerandomize_dev(self, d_proofs, d_factors, flags=0, out=None, stream=0, workspace=None):
+        """rerandomize() on the device (frw_groth16_rerandomize_dev): d_proofs a device tensor [batch, 48] of 64-bit limbs, d_factors
+        [batch, 2, 4].  Returns (proofs int64[batch, 48], status int32[batch]), device tensors, ordered on `stream`, nothing
+        synchronised or allocated by the call itself: capture-safe when `out` and `workspace` are given.  out may be d_proofs (in
+        place); workspace: a device tensor (16-byte aligned) or None for one of the whole batch -- a smaller one runs the batch in
+        chunks."""
+        import torch
+        batch = d_proofs.shape[0]
+        if out is None:
+            out = torch.empty((batch, 48), dtype=torch.int64, device=d_proofs.device)
+        status = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
+        if workspace is None:
+            workspace = torch.empty(max(self.rerandomize_workspace_bytes(batch), 16), dtype=torch.uint8, device=d_proofs.device)
+        ws_bytes = workspace.numel() * workspace.element_size()
+        check(self._lib.frw_groth16_rerandomize_dev(self._h, batch, C.c_void_p(d_proofs.data_ptr()), C.c_void_p(d_factors.data_ptr()), int(flags),
+                                                    C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                                    ws_bytes, C.c_void_p(stream)), "frw_groth16_rerandomize_dev")
+        return out, status
+
+    def rerandomize_wire_dev(self, d_wire, d_factors, compressed=True, flags=0, out=None, stream=0, workspace=None):
+        """rerandomize_dev with the proofs as ark-serialize's bytes, in and out (frw_groth16_rerandomize_wire_dev): d_wire a device
+        uint8 tensor of batch x 192 (compressed) or 384 bytes.  Returns (bytes uint8[batch, 192 or 384], status int32[batch]); -1 also
+        where the decoder refuses the bytes; a refused slot is all zero bytes.  out may be d_wire."""
+        import torch
+        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+        per = 192 if compressed else 384
+        if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
+            raise FrwError(-1, "rerandomize_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
+        batch = d_wire.numel() // per
+        if out is None:
+            out = torch.empty((batch, per), dtype=torch.uint8, device=d_wire.device)
+        status = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
+        if workspace is None:
+            workspace = torch.empty(max(self.rerandomize_workspace_bytes(batch, mode), 16), dtype=torch.uint8, device=d_wire.device)
+        ws_bytes = workspace.numel() * workspace.element_size()
+        check(self._lib.frw_groth16_rerandomize_wire_dev(self._h, batch, C.c_void_p(d_wire.data_ptr()), mode, C.c_void_p(d_factors.data_ptr()),
+                                                         int(flags), C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()),
+                                                         C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_rerandomize_wire_dev")
+        return out, status
 
     def close(self):
         if self._h:

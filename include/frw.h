@@ -791,6 +791,51 @@ int frw_diag_wire_greater(const uint64_t *c0, const uint64_t *c1);
  * device -> FRW_E_NO_DEVICE (no host fallback). */
 int frw_diag_pairing_dev(int device, size_t count, const uint64_t *g1, const uint64_t *g2, uint64_t *out);
 
+/* ---- re-randomising proofs (frw_rerand.hip): ark-groth16 0.3.0 prover.rs, rerandomize_proof(rng, vk, proof) ---------------------------------
+ * Restated from the crate's source (parity unpinned: DESIGN.md 5.11):
+ *     A' = r1^-1 A          B' = r1 B + (r1 r2) delta_g2          C' = C + r2 A
+ * A proof of the same statement that looks new: whoever holds (vk, proof) -- no signature, no witness, no proving key -- can present it
+ * again, or forward it, without the 192 bytes being a stable identifier.  ark draws r1, r2 itself; here the CALLER supplies them, as with
+ * the blinding factors of frw_groth16_prove_rs_dev: the new proof is unlinkable to the old one only if the pair is uniform, secret and
+ * FRESH -- the same proof with the same pair gives the same bytes.
+ *     proofs      uint64_t[batch][48]: A | B | C as frw_groth16_prove_dev writes them.  Each of the three may be the point at infinity
+ *                 (all zero): the formulas are defined for it, and so may each result be (written as all zero)
+ *     factors     uint64_t[batch][2][4]: r1, r2 of every proof, ANY 256-bit values, taken modulo the group order r
+ *     flags       0 or FRW_VERIFY_POINTS_ARE_CHECKED (any other bit -> FRW_E_INVALID_ARG): skips the subgroup ladders of A, B, C.  The
+ *                 result for a point vouched for WRONGLY is unspecified -- the G1 multiples are computed through the endomorphism
+ *                 phi(P) = lambda P, which holds in the subgroup only -- but the call stays memory-safe and deterministic (some point of the
+ *                 curve, status 0)
+ *     out         uint64_t[batch][48], affine points in ark-ff's limbs -- one representation per point, so equal across host, device, batch
+ *                 size and chunking, bit for bit.  IN PLACE is allowed (out == proofs): a slot is read whole before any of it is written
+ *     status      int32_t[batch]: 0 re-randomised; -1 malformed -- exactly what frw_groth16_verify calls malformed in a proof: a coordinate
+ *                 >= q, a point off its curve, a point outside its subgroup (and, in the wire form, whatever the decoder refuses);
+ *                 FRW_RERAND_ZERO_FACTOR: r1 or r2 is 0 modulo r (of a proof that is not malformed).  A refused slot's output is all
+ *                 zero bytes; the call itself returns FRW_OK
+ * A slot's output depends on its own proof and factors alone.  batch = 0 is a no-op that returns before anything else is looked at.
+ * frw_groth16_rerandomize: HOST code, any handle from frw_groth16_vk_load*, one proof per host thread.  For a single proof it is the
+ * faster route: a device call's time is that of its longest chain whatever the batch (DESIGN.md 5.11 has the figures).
+ * The factors' arithmetic (r1^-1, r1 r2) is NOT constant-time, on the host or on the device: its branches and trip counts depend on r1, r2.
+ * Where an observer of timing is part of the threat, draw the factors and call where that observer is not.
+ * The _dev calls: the key must come from frw_groth16_vk_load_dev or frw_groth16_vk_load_wire_dev (they put delta_g2 on the device; any
+ * other key -> FRW_E_INVALID_ARG, no device -> FRW_E_NO_DEVICE, no host fallback).  Stream-ordered on `stream` ALONE, nothing is
+ * allocated or copied, nothing synchronises: capture-safe, and a captured graph has no parallel branches.  d_workspace:
+ * frw_groth16_rerandomize_workspace_bytes(vk, batch_in_flight, wire_mode) bytes, 16-byte aligned -- 1,072 bytes a proof in flight (its
+ * sixteen scalar words, A' and C' in XYZZ coordinates, B' likewise), with wire_mode FRW_WIRE_* 392 more (the decoded limbs and the two
+ * codec statuses), each piece rounded up to 16; wire_mode -1: the limb form; 0 for a null key, batch_in_flight = 0 or a bad mode.  A
+ * workspace smaller than the batch needs runs it in chunks.  FRW_E_INVALID_ARG: a null pointer, a bad flag or mode, a misaligned
+ * workspace, one too small for one proof.
+ * frw_groth16_rerandomize_wire_dev: d_wire_in, d_wire_out: batch x frw_groth16_proof_wire_bytes(mode) bytes, any alignment; every chunk is
+ * decoded into the workspace (frw_groth16_proofs_from_wire_dev's kernels), re-randomised there and encoded
+ * (frw_groth16_proofs_to_wire_dev's kernel).  In place is allowed (d_wire_out == d_wire_in). */
+#define FRW_RERAND_ZERO_FACTOR (-2)
+int frw_groth16_rerandomize(const frw_groth16_vk *vk, size_t batch, const uint64_t *proofs, const uint64_t *factors, int flags, uint64_t *out,
+                            int32_t *status);
+size_t frw_groth16_rerandomize_workspace_bytes(const frw_groth16_vk *vk, size_t batch_in_flight, int wire_mode);
+int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint64_t *d_factors, int flags,
+                                uint64_t *d_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint64_t *d_factors,
+                                     int flags, uint8_t *d_wire_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- input preparation (what the reference does with falcon-rust before any gadget runs) ---------------------
  * falcon_ntt.rs:27-28,44: sig_poly = Polynomial::from(&sig), pk_poly = Polynomial::from(&pk),
  * hm = Polynomial::from_hash_of_message(msg, sig.nonce()).  Formats are the Falcon specification's:

@@ -139,6 +139,7 @@ pub const FRW_VERIFY_POINTS_ARE_CHECKED: c_int = 1;
 pub const FRW_VERIFY_BATCHED: c_int = 2;
 pub const FRW_WIRE_COMPRESSED: c_int = 0;
 pub const FRW_WIRE_UNCOMPRESSED: c_int = 1;
+pub const FRW_RERAND_ZERO_FACTOR: c_int = -2;
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct frw_groth16_pk_desc_t {
@@ -351,6 +352,15 @@ extern "C" {
                                         pk_out: *mut *mut frw_groth16_pk, vk_out: *mut u64) -> c_int;
     pub fn frw_groth16_pk_to_wire_dev(pk: *const frw_groth16_pk, vk: *const u64, num_instance: usize, mode: c_int, out: *mut u8, out_len: usize) -> c_int;
     pub fn frw_diag_wire_greater(c0: *const u64, c1: *const u64) -> c_int;
+    pub fn frw_groth16_rerandomize(vk: *const frw_groth16_vk, batch: usize, proofs: *const u64, factors: *const u64, flags: c_int,
+                                   out: *mut u64, status: *mut i32) -> c_int;
+    pub fn frw_groth16_rerandomize_workspace_bytes(vk: *const frw_groth16_vk, batch_in_flight: usize, wire_mode: c_int) -> usize;
+    pub fn frw_groth16_rerandomize_dev(vk: *const frw_groth16_vk, batch: usize, d_proofs: *const u64, d_factors: *const u64, flags: c_int,
+                                       d_out: *mut u64, d_status: *mut i32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                       stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_rerandomize_wire_dev(vk: *const frw_groth16_vk, batch: usize, d_wire_in: *const u8, mode: c_int, d_factors: *const u64,
+                                            flags: c_int, d_wire_out: *mut u8, d_status: *mut i32, d_workspace: *mut c_void,
+                                            workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_diag_pairing_dev(device: c_int, count: usize, g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,
                                  d_msg_off: *const u64, d_hm: *mut u16, stream: *mut c_void) -> c_int;

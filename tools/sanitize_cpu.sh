@@ -46,3 +46,8 @@ echo "fq29 / quad headers: clean"
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" \
     -o /tmp/frw_pok_prove_layout_asan "$ROOT/tests/cpp/test_pok_prove_layout.cpp"
 ASAN_OPTIONS=detect_leaks=0 /tmp/frw_pok_prove_layout_asan | tail -1
+# re-randomisation (frw_rerand.h's host path: the factors' arithmetic, the three chains over equal / opposite operands and points at
+# infinity, in place; frw_layout.h rerand_layout): a program of its own
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wno-unknown-pragmas -fno-strict-aliasing \
+    -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" -o /tmp/frw_rerand_host_asan "$ROOT/tests/cpp/test_rerand_host.cpp"
+ASAN_OPTIONS=detect_leaks=0 /tmp/frw_rerand_host_asan | tail -1

@@ -8,12 +8,14 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
 #include "../../include/frw.h"
 #include "frw_arena.h"
 #include "frw_device.h"
+#include "frw_stage.h"
 
 struct frw_ctx {
     int device;
@@ -79,6 +81,28 @@ bool bad_common(const frw_ctx *ctx, int logn, int encoding)
     return !ctx || (logn != 9 && logn != 10) || (encoding != FRW_ENC_CANONICAL && encoding != FRW_ENC_MONTGOMERY);
 }
 
+
+// frw_layout*: the segment table of a circuit's witness laid end to end.  The counts are frw::circuit_shape's; the table has to add up
+// to its witness count.
+template <class Layout, int N> int fill_layout(int circuit, int logn, const int (&len)[N], Layout *out)
+{
+    const frw::CircuitShape shape = frw::circuit_shape(circuit, logn);
+    int off = 0;
+    out->logn = logn;
+    out->n = (int)shape.n;
+    for (int i = 0; i < N; i++) {
+        out->seg_off[i] = off;
+        out->seg_len[i] = len[i];
+        off += len[i];
+    }
+    out->num_witness = (int)shape.num_witness;
+    out->num_instance = (int)shape.num_instance;
+    out->num_constraints = (int)shape.num_constraints;
+    if ((size_t)off == shape.num_witness) return FRW_OK;
+    snprintf(g_last_error, sizeof g_last_error, "frw_layout: the segments of circuit %d add up to %d, not to its %zu witness variables", circuit, off,
+             shape.num_witness);
+    return FRW_E_INVALID_ARG;
+}
 }  // namespace
 
 namespace frw {
@@ -99,18 +123,7 @@ int frw_layout(int logn, frw_layout_t *out)
     if (!out || (logn != 9 && logn != 10)) return FRW_E_INVALID_ARG;
     const int n = 1 << logn, nb = logn == 9 ? 50 : 52;
     const int len[FRW_NUM_SEGMENTS] = {n, n, 27 * n, 29 * n, 29 * n, 30 * n, 36 * n, nb};
-    int off = 0;
-    out->logn = logn;
-    out->n = n;
-    for (int i = 0; i < FRW_NUM_SEGMENTS; i++) {
-        out->seg_off[i] = off;
-        out->seg_len[i] = len[i];
-        off += len[i];
-    }
-    out->num_witness = off;
-    out->num_instance = 2 * n + 1;
-    out->num_constraints = 159 * n + nb + 2;
-    return FRW_OK;
+    return fill_layout(FRW_CIRCUIT_NTT, logn, len, out);
 }
 
 const char *frw_strerror(int code)
@@ -222,89 +235,79 @@ int frw_ntt_modq_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_pol
 }
 
 namespace {
-// Host-buffer driver shared by the three circuits.  Working memory comes from the context's arena (grow-only: a call after
-// the first allocates nothing).  Inputs travel through the arena's page-locked buffer, so the three polynomials of a
-// chunk are ONE host-to-device copy whatever memory the caller holds them in.  A batch that fits one chunk -- the
-// reference's own call pattern is one signature per generate_constraints -- runs on one stream: copy in, kernel, copies
-// out, one synchronisation.  Longer batches use two device slots and two streams: while the copy stream drains chunk k
-// (5 MB per signature over PCIe), the compute stream already fills chunk k+1.  With output buffers from frw_host_alloc
-// (pinned) every copy out is a true asynchronous DMA; with pageable memory the runtime stages the copies itself and the
-// overlap degrades gracefully, the results are the same.
+bool any_refused(const int32_t *status, size_t batch)
+{
+    bool any_bad = false;
+    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
+    return any_bad;
+}
+// what a strict host-buffer call returns once its passes are through: the buffers are complete either way
+int strict_verdict(int rc, int strict, const int32_t *status, size_t batch)
+{
+    return rc != FRW_OK ? rc : strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+}
+// rows lo .. lo + cnt - 1 of each of `src` (uint16_t[batch][n]) one after the other into the page-locked `stage`, and from there to d_in:
+// ONE host-to-device copy whatever memory the caller holds the polynomials in
+hipError_t stage_rows(std::initializer_list<const uint16_t *> src, size_t n, size_t lo, size_t cnt, char *stage, void *d_in, hipStream_t st)
+{
+    char *h = stage;
+    for (const uint16_t *rows : src) {
+        memcpy(h, rows + lo * n, cnt * n * 2);
+        h += cnt * n * 2;
+    }
+    return hipMemcpyAsync(d_in, stage, (size_t)(h - stage), hipMemcpyHostToDevice, st);
+}
+// the witness kernel of a circuit (FRW_ENC_COMPACT: the NTT circuit's compact form; d_witness is the compact buffer, d_instance unused)
+hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, int encoding, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
+                          const uint16_t *d_hm, void *d_witness, uint64_t *d_instance, int32_t *d_status, hipStream_t st)
+{
+    if (circuit == FRW_CIRCUIT_SCHOOLBOOK)
+        return frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
+                                                     d_instance, d_status, st);
+    if (circuit == FRW_CIRCUIT_DUAL_NTT)
+        return frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
+                                                   d_instance, d_status, st);
+    if (encoding == FRW_ENC_COMPACT)
+        return frw::launch_witness_ntt_verify_compact(ctx->d_tables, ctx->num_cu, logn, batch, d_sig, d_pk, d_hm, d_witness, d_status, st);
+    return frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness, d_instance,
+                                          d_status, st);
+}
+
+// The host-buffer witness calls of the three circuits.  The pass loop is frw::host_passes (frw_arena.h); this says what a pass is: the
+// three polynomials of a chunk staged and copied in at once, the circuit's kernel, and witness, instance and status on the way out.  A
+// batch that fits one chunk -- the reference's own call pattern is one signature per generate_constraints -- takes one slot and one
+// stream: copy in, kernel, copies out, one synchronisation.  A longer one takes two, so that a chunk's witness leaves while the next
+// one is computed.
 int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
                  const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance, int32_t *status, int strict)
 {
-    const bool dual = circuit == FRW_CIRCUIT_DUAL_NTT, schoolbook = circuit == FRW_CIRCUIT_SCHOOLBOOK;
     const bool compact = circuit == FRW_CIRCUIT_NTT && encoding == FRW_ENC_COMPACT;    // `witness` = compact buffer, `instance` unused
     if (compact ? bad_common(ctx, logn, FRW_ENC_MONTGOMERY) : bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!sig || !pk || !hm || !witness || (!instance && !compact) || !status) return FRW_E_INVALID_ARG;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)1 << logn;
-    const size_t nb = logn == 9 ? 50 : 52;
-    const size_t wbytes = compact ? frw::compact_layout(logn).bytes
-                                  : (schoolbook ? n * n + 99 * n + nb : dual ? 186 * n + 4 + nb : 153 * n + nb) * 32;
-    const size_t ibytes = compact ? 0 : (2 * n + 1) * 32;
+    const frw::CircuitShape shape = frw::circuit_shape(circuit, logn);
+    const size_t n = shape.n;
+    const size_t wbytes = compact ? frw::compact_layout(logn).bytes : shape.num_witness * 32;
+    const size_t ibytes = compact ? 0 : shape.num_instance * 32;
     // 2 x (<= 1.6 GB) of device witness; a schoolbook witness is 10.0 | 36.8 MB, so a slot holds 128 | 32 of them (1.3 | 1.2 GB)
-    const size_t chunk = std::min<size_t>(batch, compact ? 2048 : schoolbook ? (logn == 9 ? 128 : 32) : 256);
-    const int nbuf = batch > chunk ? 2 : 1;
+    const size_t chunk = std::min<size_t>(batch, compact ? 2048 : circuit == FRW_CIRCUIT_SCHOOLBOOK ? (logn == 9 ? 128 : 32) : 256);
     const size_t in_bytes = 3 * chunk * n * 2;                              // sig | pk | hm of one chunk, contiguous
-    struct Slot { uint16_t *in; char *wit, *inst; int32_t *st; } slot[2];
-    for (int b = 0; b < nbuf; b++) {
-        frw::Carve size(nullptr);
-        size.take(in_bytes); size.take(chunk * wbytes); size.take(chunk * ibytes + 16); size.take(chunk * sizeof(int32_t));
-        FRW_HIP(A.reserve_device(b, size.off));
-        frw::Carve c(A.d_slot[b]);
-        slot[b].in = c.take<uint16_t>(in_bytes);
-        slot[b].wit = c.take<char>(chunk * wbytes);
-        slot[b].inst = c.take<char>(chunk * ibytes + 16);
-        slot[b].st = c.take<int32_t>(chunk * sizeof(int32_t));
-    }
-    FRW_HIP(A.reserve_pinned((size_t)nbuf * in_bytes));
-    const uint16_t *src[3] = {sig, pk, hm};
-    size_t k = 0;
-    for (size_t lo = 0; lo < batch; lo += chunk, k++) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        const int b = (int)(k & 1);
-        // slot b was last used by chunk k - 2: its copies out have finished before its memory is written again (the
-        // host waits too: it is about to overwrite the page-locked inputs that chunk's H2D copy read)
-        if (k >= 2) FRW_HIP(hipEventSynchronize(A.drained[b]));
-        uint16_t *stage = (uint16_t *)((char *)A.h_pin + (size_t)b * in_bytes);
-        for (int j = 0; j < 3; j++) memcpy(stage + (size_t)j * cnt * n, src[j] + lo * n, cnt * n * 2);
-        FRW_HIP(hipMemcpyAsync(slot[b].in, stage, 3 * cnt * n * 2, hipMemcpyHostToDevice, A.compute));
-        const uint16_t *d_sig = slot[b].in, *d_pk = d_sig + cnt * n, *d_hm = d_pk + cnt * n;
-        if (schoolbook)
-            FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, d_sig, d_pk, d_hm,
-                                                          (uint64_t *)slot[b].wit, (uint64_t *)slot[b].inst, slot[b].st, A.compute));
-        else if (dual)
-            FRW_HIP(frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, d_sig, d_pk, d_hm,
-                                                        (uint64_t *)slot[b].wit, (uint64_t *)slot[b].inst, slot[b].st, A.compute));
-        else if (compact)
-            FRW_HIP(frw::launch_witness_ntt_verify_compact(ctx->d_tables, ctx->num_cu, logn, cnt, d_sig, d_pk, d_hm, slot[b].wit,
-                                                           slot[b].st, A.compute));
-        else
-            FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, d_sig, d_pk, d_hm,
-                                                   (uint64_t *)slot[b].wit, (uint64_t *)slot[b].inst, slot[b].st, A.compute));
-        hipStream_t out = A.compute;
-        if (nbuf == 2) {
-            FRW_HIP(hipEventRecord(A.done[b], A.compute));
-            FRW_HIP(hipStreamWaitEvent(A.copy, A.done[b], 0));
-            out = A.copy;
-        }
-        FRW_HIP(hipMemcpyAsync((char *)witness + lo * wbytes, slot[b].wit, cnt * wbytes, hipMemcpyDeviceToHost, out));
-        if (!compact)
-            FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, slot[b].inst, cnt * ibytes, hipMemcpyDeviceToHost, out));
-        FRW_HIP(hipMemcpyAsync(status + lo, slot[b].st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, out));
-        if (nbuf == 2) FRW_HIP(hipEventRecord(A.drained[b], A.copy));
-    }
-    FRW_HIP(hipStreamSynchronize(A.compute));
-    if (nbuf == 2) FRW_HIP(hipStreamSynchronize(A.copy));
-    drain.settled = true;
-    bool any_bad = false;
-    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
-    return strict && any_bad ? FRW_E_RANGE : FRW_OK;
+    frw::Carve c(nullptr);
+    const size_t o_in = c.off;   c.take(in_bytes);
+    const size_t o_wit = c.off;  c.take(chunk * wbytes);
+    const size_t o_inst = c.off; c.take(chunk * ibytes + 16);
+    const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, batch > chunk ? 2 : 1, c.off, in_bytes,
+        {{witness, o_wit, wbytes}, {compact ? nullptr : instance, o_inst, ibytes}, {status, o_st, sizeof(int32_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            const uint16_t *d_in = (const uint16_t *)(d + o_in);
+            FRW_HIP(stage_rows({sig, pk, hm}, n, lo, cnt, stage, d + o_in, st));
+            FRW_HIP(launch_witness(ctx, circuit, logn, encoding, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, d + o_wit,
+                                   (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), st));
+            return FRW_OK;
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 }  // namespace
 
@@ -432,7 +435,8 @@ int frw_expand_host(int logn, size_t batch, const void *compact, uint64_t *witne
 {
     if ((logn != 9 && logn != 10) || (batch && (!compact || !witness || !instance))) return FRW_E_INVALID_ARG;
     const frw::CompactLayout c = frw::compact_layout(logn);
-    const size_t n = (size_t)1 << logn, nb = logn == 9 ? 50 : 52, W = 153 * n + nb, I = 2 * n + 1;
+    const frw::CircuitShape shape = frw::circuit_shape(FRW_CIRCUIT_NTT, logn);
+    const size_t n = shape.n, nb = shape.nb, W = shape.num_witness, I = shape.num_instance;
     for (size_t s = 0; s < batch; s++) {
         const unsigned char *base = (const unsigned char *)compact + s * c.bytes;
         const uint32_t *small = (const uint32_t *)base;                   // next small value
@@ -497,18 +501,7 @@ int frw_layout_dual(int logn, frw_layout_dual_t *out)
     if (!out || (logn != 9 && logn != 10)) return FRW_E_INVALID_ARG;
     const int n = 1 << logn, nb = logn == 9 ? 50 : 52;
     const int len[FRW_NUM_SEGMENTS_DUAL] = {n, n, n, 2, n, n, n, 2, 29 * n, 29 * n, 29 * n, 29 * n, 60 * n, 4 * n, nb};
-    int off = 0;
-    out->logn = logn;
-    out->n = n;
-    for (int i = 0; i < FRW_NUM_SEGMENTS_DUAL; i++) {
-        out->seg_off[i] = off;
-        out->seg_len[i] = len[i];
-        off += len[i];
-    }
-    out->num_witness = off;
-    out->num_instance = 2 * n + 1;
-    out->num_constraints = 189 * n + 10 + nb;
-    return FRW_OK;
+    return fill_layout(FRW_CIRCUIT_DUAL_NTT, logn, len, out);
 }
 
 int frw_layout_schoolbook(int logn, frw_layout_schoolbook_t *out)
@@ -516,19 +509,8 @@ int frw_layout_schoolbook(int logn, frw_layout_schoolbook_t *out)
     if (!out || (logn != 9 && logn != 10)) return FRW_E_INVALID_ARG;
     const int n = 1 << logn, nb = logn == 9 ? 50 : 52;
     const int len[FRW_NUM_SEGMENTS_SCHOOLBOOK] = {n, 28 * n, n * (n + 34), 36 * n, nb};
-    int off = 0;
-    out->logn = logn;
-    out->n = n;
-    for (int i = 0; i < FRW_NUM_SEGMENTS_SCHOOLBOOK; i++) {
-        out->seg_off[i] = off;
-        out->seg_len[i] = len[i];
-        off += len[i];
-    }
-    out->num_witness = off;
-    out->num_instance = 2 * n + 1;
-    out->num_constraints = n * n + 105 * n + nb + 2;
     out->column_len = n + 34;
-    return FRW_OK;
+    return fill_layout(FRW_CIRCUIT_SCHOOLBOOK, logn, len, out);
 }
 
 int frw_witness_schoolbook_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
@@ -557,52 +539,23 @@ int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int
     if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!poly || !witness || !ntt_out || !status) return FRW_E_INVALID_ARG;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    // same pipeline as witness_host: arena memory, one stream for a batch that fits a chunk, else the D2H of chunk k
-    // overlaps the kernel of chunk k+1
+    // as witness_host: one slot and one stream for a batch that fits a chunk, else two
     const size_t n = (size_t)1 << logn, wbytes = 29 * n * 32;
     const size_t chunk = std::min<size_t>(batch, 2048);
-    const int nbuf = batch > chunk ? 2 : 1;
-    struct Slot { uint16_t *in, *out; char *wit; int32_t *st; } slot[2];
-    for (int b = 0; b < nbuf; b++) {
-        frw::Carve size(nullptr);
-        size.take(chunk * n * 2); size.take(chunk * n * 2); size.take(chunk * wbytes); size.take(chunk * sizeof(int32_t));
-        FRW_HIP(A.reserve_device(b, size.off));
-        frw::Carve c(A.d_slot[b]);
-        slot[b].in = c.take<uint16_t>(chunk * n * 2);
-        slot[b].out = c.take<uint16_t>(chunk * n * 2);
-        slot[b].wit = c.take<char>(chunk * wbytes);
-        slot[b].st = c.take<int32_t>(chunk * sizeof(int32_t));
-    }
-    FRW_HIP(A.reserve_pinned((size_t)nbuf * chunk * n * 2));
-    size_t k = 0;
-    for (size_t lo = 0; lo < batch; lo += chunk, k++) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        const int b = (int)(k & 1);
-        if (k >= 2) FRW_HIP(hipEventSynchronize(A.drained[b]));
-        uint16_t *stage = (uint16_t *)((char *)A.h_pin + (size_t)b * chunk * n * 2);
-        memcpy(stage, poly + lo * n, cnt * n * 2);
-        FRW_HIP(hipMemcpyAsync(slot[b].in, stage, cnt * n * 2, hipMemcpyHostToDevice, A.compute));
-        FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, slot[b].in, (uint64_t *)slot[b].wit,
-                                     slot[b].out, slot[b].st, A.compute));
-        hipStream_t out = A.compute;
-        if (nbuf == 2) {
-            FRW_HIP(hipEventRecord(A.done[b], A.compute));
-            FRW_HIP(hipStreamWaitEvent(A.copy, A.done[b], 0));
-            out = A.copy;
-        }
-        FRW_HIP(hipMemcpyAsync((char *)witness + lo * wbytes, slot[b].wit, cnt * wbytes, hipMemcpyDeviceToHost, out));
-        FRW_HIP(hipMemcpyAsync(ntt_out + lo * n, slot[b].out, cnt * n * 2, hipMemcpyDeviceToHost, out));
-        FRW_HIP(hipMemcpyAsync(status + lo, slot[b].st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, out));
-        if (nbuf == 2) FRW_HIP(hipEventRecord(A.drained[b], A.copy));
-    }
-    FRW_HIP(hipStreamSynchronize(A.compute));
-    if (nbuf == 2) FRW_HIP(hipStreamSynchronize(A.copy));
-    drain.settled = true;
-    return FRW_OK;
+    frw::Carve c(nullptr);
+    const size_t o_in = c.off;  c.take(chunk * n * 2);
+    const size_t o_out = c.off; c.take(chunk * n * 2);
+    const size_t o_wit = c.off; c.take(chunk * wbytes);
+    const size_t o_st = c.off;  c.take(chunk * sizeof(int32_t));
+    return frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, batch > chunk ? 2 : 1, c.off, chunk * n * 2,
+        {{witness, o_wit, wbytes}, {ntt_out, o_out, n * 2}, {status, o_st, sizeof(int32_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            FRW_HIP(stage_rows({poly}, n, lo, cnt, stage, d + o_in, st));
+            FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, (const uint16_t *)(d + o_in), (uint64_t *)(d + o_wit),
+                                         (uint16_t *)(d + o_out), (int32_t *)(d + o_st), st));
+            return FRW_OK;
+        });
 }
 
 int frw_hash_to_point_dev(frw_ctx *ctx, int logn, size_t batch, const uint8_t *d_nonces, const uint8_t *d_msgs,
@@ -645,23 +598,15 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
     if (bad_common(ctx, logn, FRW_ENC_CANONICAL)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!pk_bytes || !sig_bytes || !msg_off || !sig || !pk || !hm || !status || sig_len <= 1 + FRW_NONCE_LEN) return FRW_E_INVALID_ARG;
-    if (!msgs && msg_off[batch] != msg_off[0]) return FRW_E_INVALID_ARG;
-    for (size_t i = 0; i < batch; i++)
-        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     frw::HostArena &A = ctx->arena;
     std::lock_guard<std::mutex> lock(A.mu);
     frw::DrainOnExit drain(A);
     FRW_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)1 << logn, pk_len = FRW_PK_LEN(logn);
-    const size_t msg_bytes = (size_t)(msg_off[batch] - msg_off[0]);
-    // one device slot, carved; the encoded inputs travel in ONE copy through the page-locked buffer, the results and both
-    // status vectors come back in ONE copy
-    frw::Carve hs(nullptr);                                             // layout of the staged inputs == their device layout
-    const size_t o_pkb = hs.off; hs.take(batch * pk_len);
-    const size_t o_sigb = hs.off; hs.take(batch * sig_len);
-    const size_t o_msgs = hs.off; hs.take(msg_bytes ? msg_bytes : 1);
-    const size_t o_off = hs.off; hs.take((batch + 1) * sizeof(uint64_t));
-    const size_t in_total = hs.off;
+    const size_t n = (size_t)1 << logn;
+    // one device slot, carved; the encoded inputs travel in ONE copy through the page-locked buffer (one pass of the whole batch), the
+    // results and both status vectors come back in ONE copy
+    const frw::StagedInputs in(logn, batch, batch, pk_bytes, sig_bytes, sig_len, msgs, msg_off);
     frw::Carve os(nullptr);                                             // layout of the results
     const size_t o_sig = os.off; os.take(batch * n * 2);
     const size_t o_pk = os.off; os.take(batch * n * 2);
@@ -670,26 +615,21 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
     const size_t o_st2 = os.off; os.take(batch * sizeof(int32_t));
     const size_t out_total = os.off;
     const size_t nonce_bytes = (batch * FRW_NONCE_LEN + 255) & ~(size_t)255;
-    FRW_HIP(A.reserve_device(0, in_total + out_total + nonce_bytes));
-    FRW_HIP(A.reserve_pinned(std::max(in_total, out_total)));
-    char *d_in = (char *)A.d_slot[0], *d_out = d_in + in_total, *d_nonce = d_out + out_total, *h = (char *)A.h_pin;
-    memcpy(h + o_pkb, pk_bytes, batch * pk_len);
-    memcpy(h + o_sigb, sig_bytes, batch * sig_len);
-    if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[0], msg_bytes);
-    uint64_t *off = (uint64_t *)(h + o_off);
-    for (size_t i = 0; i <= batch; i++) off[i] = msg_off[i] - msg_off[0];
+    FRW_HIP(A.reserve_device(0, in.bytes + out_total + nonce_bytes));
+    FRW_HIP(A.reserve_pinned(std::max(in.bytes, out_total)));
+    char *d_in = (char *)A.d_slot[0], *d_out = d_in + in.bytes, *d_nonce = d_out + out_total, *h = (char *)A.h_pin;
+    in.fill(h, 0, batch);
     hipStream_t st = A.compute;
-    FRW_HIP(hipMemcpyAsync(d_in, h, in_total, hipMemcpyHostToDevice, st));
+    FRW_HIP(hipMemcpyAsync(d_in, h, in.bytes, hipMemcpyHostToDevice, st));
     FRW_HIP(hipMemsetAsync(d_nonce, 0, batch * FRW_NONCE_LEN, st));
-    FRW_HIP(frw::launch_decode_public_keys(logn, batch, (const uint8_t *)(d_in + o_pkb), (uint16_t *)(d_out + o_pk),
-                                           (int32_t *)(d_out + o_st1), st));
-    FRW_HIP(frw::launch_decode_signatures(logn, batch, (const uint8_t *)(d_in + o_sigb), sig_len, (uint16_t *)(d_out + o_sig),
-                                          (uint8_t *)d_nonce, (int32_t *)(d_out + o_st2), st));
-    FRW_HIP(frw::launch_hash_to_point(logn, batch, (const uint8_t *)d_nonce, (const uint8_t *)(d_in + o_msgs),
-                                      (const uint64_t *)(d_in + o_off), (uint16_t *)(d_out + o_hm), st));
+    FRW_HIP(frw::launch_decode_public_keys(logn, batch, in.d_pk(d_in), (uint16_t *)(d_out + o_pk), (int32_t *)(d_out + o_st1), st));
+    FRW_HIP(frw::launch_decode_signatures(logn, batch, in.d_second(d_in), sig_len, (uint16_t *)(d_out + o_sig), (uint8_t *)d_nonce,
+                                          (int32_t *)(d_out + o_st2), st));
+    FRW_HIP(frw::launch_hash_to_point(logn, batch, (const uint8_t *)d_nonce, in.d_msgs(d_in), in.d_off(d_in), (uint16_t *)(d_out + o_hm), st));
     FRW_HIP(hipStreamSynchronize(st));                                   // the staged inputs have been read
     FRW_HIP(hipMemcpyAsync(h, d_out, out_total, hipMemcpyDeviceToHost, st));
     FRW_HIP(hipStreamSynchronize(st));
+    drain.settled = true;
     memcpy(sig, h + o_sig, batch * n * 2);
     memcpy(pk, h + o_pk, batch * n * 2);
     memcpy(hm, h + o_hm, batch * n * 2);
@@ -702,8 +642,7 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
 namespace {
 bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding)
 {
-    return bad_common(ctx, logn, encoding) ||
-           (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT && circuit != FRW_CIRCUIT_SCHOOLBOOK);
+    return bad_common(ctx, logn, encoding) || !frw::known_circuit(circuit);
 }
 // the schoolbook circuit's public inputs are the coefficients themselves (falcon_schoolbook.rs:66-83), the NTT circuits' their transforms
 int statement_form(int circuit) { return circuit == FRW_CIRCUIT_SCHOOLBOOK ? 1 : 0; }
@@ -752,35 +691,21 @@ int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint1
     if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
     if (!pk || !hm || !instance || !status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)1 << logn, ibytes = (2 * n + 1) * 32, chunk = std::min(batch, STATEMENT_CHUNK);
+    const size_t n = (size_t)1 << logn, ibytes = frw::circuit_shape(circuit, logn).num_instance * 32, chunk = std::min(batch, STATEMENT_CHUNK);
     frw::Carve c(nullptr);
     const size_t o_in = c.off;   c.take(2 * chunk * n * 2);
     const size_t o_inst = c.off; c.take(chunk * ibytes);
     const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
-    FRW_HIP(A.reserve_device(0, c.off));
-    FRW_HIP(A.reserve_pinned(2 * chunk * n * 2));
-    char *d = (char *)A.d_slot[0];
-    uint16_t *stage = (uint16_t *)A.h_pin, *d_in = (uint16_t *)(d + o_in);
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        memcpy(stage, pk + lo * n, cnt * n * 2);
-        memcpy(stage + cnt * n, hm + lo * n, cnt * n * 2);
-        FRW_HIP(hipMemcpyAsync(d_in, stage, 2 * cnt * n * 2, hipMemcpyHostToDevice, st));
-        FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, d_in, d_in + cnt * n,
-                                      (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st));
-        FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
-    }
-    drain.settled = true;
-    bool any_bad = false;
-    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
-    return strict && any_bad ? FRW_E_RANGE : FRW_OK;
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, 1, c.off, 2 * chunk * n * 2, {{instance, o_inst, ibytes}, {status, o_st, sizeof(int32_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            const uint16_t *d_in = (const uint16_t *)(d + o_in);
+            FRW_HIP(stage_rows({pk, hm}, n, lo, cnt, stage, d + o_in, st));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, d_in, d_in + cnt * n,
+                                          (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st));
+            return FRW_OK;
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 
 int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *nonces,
@@ -788,57 +713,28 @@ int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, 
 {
     if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
     if (!pk_bytes || !nonces || !msg_off || !instance || !status) return FRW_E_INVALID_ARG;
-    for (size_t i = 0; i < batch; i++)
-        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
-    if (batch && !msgs && msg_off[batch] != msg_off[0]) return FRW_E_INVALID_ARG;
+    if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)1 << logn, ibytes = (2 * n + 1) * 32, pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, STATEMENT_CHUNK);
-    size_t max_msg = 1;                                                   // the longest pass's message bytes
-    for (size_t lo = 0; lo < batch; lo += chunk)
-        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
-    // the staged inputs' layout == their device layout: ONE copy in per pass
-    frw::Carve hs(nullptr);
-    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
-    const size_t o_non = hs.off; hs.take(chunk * FRW_NONCE_LEN);
-    const size_t o_msgs = hs.off; hs.take(max_msg);
-    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
-    const size_t in_total = hs.off;
+    const size_t ibytes = frw::circuit_shape(circuit, logn).num_instance * 32, chunk = std::min(batch, STATEMENT_CHUNK);
+    const frw::StagedInputs in(logn, batch, chunk, pk_bytes, nonces, FRW_NONCE_LEN, msgs, msg_off);
     frw::Carve c(nullptr);
-    c.take(in_total);
+    c.take(in.bytes);
     const size_t o_ws = c.off;   c.take(frw_statement_workspace_bytes(logn, chunk));
     const size_t o_inst = c.off; c.take(chunk * ibytes);
     const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
-    FRW_HIP(A.reserve_device(0, c.off));
-    FRW_HIP(A.reserve_pinned(in_total));
-    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
-        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
-        memcpy(h + o_non, nonces + lo * FRW_NONCE_LEN, cnt * FRW_NONCE_LEN);
-        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
-        uint64_t *off = (uint64_t *)(h + o_off);
-        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
-        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
-        const frw::StatementBufs ws = frw::statement_layout(d + o_ws, logn, cnt);
-        FRW_HIP(frw::launch_decode_public_keys(logn, cnt, (const uint8_t *)(d + o_pkb), ws.pk, ws.decode_status, st));
-        FRW_HIP(frw::launch_hash_to_point(logn, cnt, (const uint8_t *)(d + o_non), (const uint8_t *)(d + o_msgs),
-                                          (const uint64_t *)(d + o_off), ws.hm, st));
-        FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, ws.pk, ws.hm,
-                                      (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st));
-        FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipStreamSynchronize(st));
-    }
-    drain.settled = true;
-    bool any_bad = false;
-    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
-    return strict && any_bad ? FRW_E_RANGE : FRW_OK;
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, 1, c.off, in.bytes, {{instance, o_inst, ibytes}, {status, o_st, sizeof(int32_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            in.fill(stage, lo, cnt);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            const frw::StatementBufs ws = frw::statement_layout(d + o_ws, logn, cnt);
+            FRW_HIP(frw::launch_decode_public_keys(logn, cnt, in.d_pk(d), ws.pk, ws.decode_status, st));
+            FRW_HIP(frw::launch_hash_to_point(logn, cnt, in.d_second(d), in.d_msgs(d), in.d_off(d), ws.hm, st));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, ws.pk, ws.hm,
+                                          (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st));
+            return FRW_OK;
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 
 int frw_aggregate_statement_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint16_t *d_pk_512, const uint16_t *d_hm_512,
@@ -870,12 +766,6 @@ bool bad_falcon_verify(const frw_ctx *ctx, int logn, int rule)
     return !ctx || (logn != 9 && logn != 10) || (rule != FRW_RULE_CIRCUIT && rule != FRW_RULE_SPEC);
 }
 constexpr size_t FALCON_VERIFY_CHUNK = 16384;     // signatures of one pass of the host-buffer forms: 100 MB of Falcon-1024 coefficients
-bool any_refused(const int32_t *status, size_t batch)
-{
-    bool any_bad = false;
-    for (size_t i = 0; i < batch; i++) any_bad |= status[i] != FRW_ST_OK;
-    return any_bad;
-}
 }  // namespace
 
 int frw_falcon_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk, const uint16_t *d_hm,
@@ -936,34 +826,21 @@ int frw_falcon_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig,
     if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
     if (!sig || !pk || !hm || !status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)1 << logn, chunk = std::min(batch, FALCON_VERIFY_CHUNK);
     frw::Carve c(nullptr);
     const size_t o_in = c.off;   c.take(3 * chunk * n * 2);
     const size_t o_norm = c.off; c.take(chunk * sizeof(uint64_t));
     const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
-    FRW_HIP(A.reserve_device(0, c.off));
-    FRW_HIP(A.reserve_pinned(3 * chunk * n * 2));
-    char *d = (char *)A.d_slot[0];
-    uint16_t *stage = (uint16_t *)A.h_pin, *d_in = (uint16_t *)(d + o_in);
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        memcpy(stage, sig + lo * n, cnt * n * 2);
-        memcpy(stage + cnt * n, pk + lo * n, cnt * n * 2);
-        memcpy(stage + 2 * cnt * n, hm + lo * n, cnt * n * 2);
-        FRW_HIP(hipMemcpyAsync(d_in, stage, 3 * cnt * n * 2, hipMemcpyHostToDevice, st));
-        FRW_HIP(frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, logn, rule, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, nullptr,
-                                          nullptr, (int32_t *)(d + o_st), (uint64_t *)(d + o_norm), st));
-        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (norm) FRW_HIP(hipMemcpyAsync(norm + lo, d + o_norm, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
-    }
-    drain.settled = true;
-    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, 1, c.off, 3 * chunk * n * 2, {{status, o_st, sizeof(int32_t)}, {norm, o_norm, sizeof(uint64_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            const uint16_t *d_in = (const uint16_t *)(d + o_in);
+            FRW_HIP(stage_rows({sig, pk, hm}, n, lo, cnt, stage, d + o_in, st));
+            FRW_HIP(frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, logn, rule, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, nullptr,
+                                              nullptr, (int32_t *)(d + o_st), (uint64_t *)(d + o_norm), st));
+            return FRW_OK;
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 
 int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *sig_bytes, size_t sig_len,
@@ -971,51 +848,25 @@ int frw_falcon_verify_from_bytes(frw_ctx *ctx, int logn, size_t batch, const uin
 {
     if (bad_falcon_verify(ctx, logn, rule)) return FRW_E_INVALID_ARG;
     if (!pk_bytes || !sig_bytes || !msgs || !msg_off || !status || sig_len <= 1 + FRW_NONCE_LEN) return FRW_E_INVALID_ARG;
-    for (size_t i = 0; i < batch; i++)
-        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    const size_t pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, FALCON_VERIFY_CHUNK);
-    size_t max_msg = 1;                                                   // the longest pass's message bytes
-    for (size_t lo = 0; lo < batch; lo += chunk)
-        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
-    // the staged inputs' layout == their device layout: ONE copy in per pass
-    frw::Carve hs(nullptr);
-    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
-    const size_t o_sigb = hs.off; hs.take(chunk * sig_len);
-    const size_t o_msgs = hs.off; hs.take(max_msg);
-    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
-    const size_t in_total = hs.off;
+    const size_t chunk = std::min(batch, FALCON_VERIFY_CHUNK);
+    const frw::StagedInputs in(logn, batch, chunk, pk_bytes, sig_bytes, sig_len, msgs, msg_off);
     frw::Carve c(nullptr);
-    c.take(in_total);
+    c.take(in.bytes);
     const size_t o_ws = c.off;   c.take(frw_falcon_verify_workspace_bytes(logn, chunk));
     const size_t o_norm = c.off; c.take(chunk * sizeof(uint64_t));
     const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
-    FRW_HIP(A.reserve_device(0, c.off));
-    FRW_HIP(A.reserve_pinned(in_total));
-    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
-        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
-        memcpy(h + o_sigb, sig_bytes + lo * sig_len, cnt * sig_len);
-        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
-        uint64_t *off = (uint64_t *)(h + o_off);
-        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
-        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
-        FRW_HIP(falcon_verify_chain(ctx, logn, cnt, (const uint8_t *)(d + o_pkb), (const uint8_t *)(d + o_sigb), sig_len,
-                                    (const uint8_t *)(d + o_msgs), (const uint64_t *)(d + o_off), rule, (int32_t *)(d + o_st),
-                                    (uint64_t *)(d + o_norm), d + o_ws, st));
-        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (norm) FRW_HIP(hipMemcpyAsync(norm + lo, d + o_norm, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipStreamSynchronize(st));
-    }
-    drain.settled = true;
-    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, 1, c.off, in.bytes, {{status, o_st, sizeof(int32_t)}, {norm, o_norm, sizeof(uint64_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            in.fill(stage, lo, cnt);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            FRW_HIP(falcon_verify_chain(ctx, logn, cnt, in.d_pk(d), in.d_second(d), sig_len, in.d_msgs(d), in.d_off(d), rule,
+                                        (int32_t *)(d + o_st), (uint64_t *)(d + o_norm), d + o_ws, st));
+            return FRW_OK;
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 
 // ---- the prover from bytes: (pk bytes, msg, sig bytes) -> Groth16 proofs on the wire, one call ----------------------------------------
@@ -1023,32 +874,26 @@ namespace {
 // what the arguments say about the circuit, before any handle is looked at
 bool bad_pok_prove(const frw_ctx *ctx, int circuit, int logn, int wire_mode, size_t sig_len)
 {
-    return !ctx || (logn != 9 && logn != 10) ||
-           (circuit != FRW_CIRCUIT_NTT && circuit != FRW_CIRCUIT_DUAL_NTT && circuit != FRW_CIRCUIT_SCHOOLBOOK) ||
-           frw_groth16_proof_wire_bytes(wire_mode) == 0 || sig_len <= 1 + FRW_NONCE_LEN;
+    return !ctx || (logn != 9 && logn != 10) || !frw::known_circuit(circuit) || frw_groth16_proof_wire_bytes(wire_mode) == 0 ||
+           sig_len <= 1 + FRW_NONCE_LEN;
 }
 // ... and whether the handles are that circuit's: a per-signature system with its I, W, C, and a whole key over it.  W in *num_witness.
 bool pok_prove_shape(const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, int logn, size_t *num_witness)
 {
-    if (!pk || !r || (logn != 9 && logn != 10)) return false;
-    const uint64_t n = (uint64_t)1 << logn, nb = logn == 9 ? 50 : 52;
-    uint64_t W, C;
-    switch (circuit) {
-    case FRW_CIRCUIT_NTT: W = 153 * n + nb; C = 159 * n + nb + 2; break;
-    case FRW_CIRCUIT_DUAL_NTT: W = 186 * n + 4 + nb; C = 189 * n + 10 + nb; break;
-    case FRW_CIRCUIT_SCHOOLBOOK: W = n * n + 99 * n + nb; C = n * n + 105 * n + nb + 2; break;
-    default: return false;
-    }
+    if (!pk || !r || (logn != 9 && logn != 10) || !frw::known_circuit(circuit)) return false;
+    const frw::CircuitShape s = frw::circuit_shape(circuit, logn);
     frw_r1cs_info_t info;
     frw_groth16_pk_info_t ki;
     if (frw_r1cs_info(r, &info) != FRW_OK || frw_groth16_pk_info(pk, &ki) != FRW_OK) return false;
-    if (info.num_statements != 1 || info.num_instance != 2 * n + 1 || info.num_witness != W || info.num_constraints != C) return false;
+    if (info.num_statements != 1 || info.num_instance != s.num_instance || info.num_witness != s.num_witness ||
+        info.num_constraints != s.num_constraints)
+        return false;
     if (ki.world > 1) return false;                                       // a slice of a key proves nothing by itself
     int device = -1;
     uint64_t ni = 0, nw = 0, dom = 0;
     frw::groth16_pk_counts(pk, &device, &ni, &nw, &dom);
-    if (ni != info.num_instance || nw != W || device != frw::r1cs_device(r)) return false;
-    *num_witness = (size_t)W;
+    if (ni != info.num_instance || nw != s.num_witness || device != frw::r1cs_device(r)) return false;
+    *num_witness = s.num_witness;
     return true;
 }
 constexpr size_t POK_PROVE_MAX_IN_FLIGHT = 4096;  // (the prover's own bound on a chunk)
@@ -1100,15 +945,7 @@ int frw_pok_prove_from_bytes_dev(frw_ctx *ctx, const frw_groth16_pk *pk, const f
         const size_t cnt = std::min<size_t>(k, count - lo);
         const uint32_t *index = ws.index + lo;
         FRW_HIP(frw::launch_pok_gather_inputs(logn, cnt, index, ws.screen.sig, ws.screen.pk, ws.screen.hm, ws.sig, ws.pk, ws.hm, st));
-        if (circuit == FRW_CIRCUIT_SCHOOLBOOK)
-            FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
-                                                          ws.witness, ws.instance, ws.witness_status, st));
-        else if (circuit == FRW_CIRCUIT_DUAL_NTT)
-            FRW_HIP(frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
-                                                        ws.witness, ws.instance, ws.witness_status, st));
-        else
-            FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm,
-                                                   ws.witness, ws.instance, ws.witness_status, st));
+        FRW_HIP(launch_witness(ctx, circuit, logn, FRW_ENC_MONTGOMERY, cnt, ws.sig, ws.pk, ws.hm, ws.witness, ws.instance, ws.witness_status, st));
         int rc = frw_groth16_prove_rs_dev(pk, r, cnt, ws.witness, ws.instance, ws.rs + lo * 8, ws.proofs, ws.unsatisfied, ws.groth16_ws,
                                           ws.groth16_bytes, st);
         if (rc == FRW_OK) rc = frw_groth16_proofs_to_wire_dev(ctx->device, cnt, ws.proofs, wire_mode, ws.wire, ws.wire_status, st);
@@ -1126,68 +963,36 @@ int frw_pok_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r
 {
     if (bad_pok_prove(ctx, circuit, logn, wire_mode, sig_len)) return FRW_E_INVALID_ARG;
     if (!pk || !r || !pk_bytes || !sig_bytes || !msgs || !msg_off || !rs || !wire || !status) return FRW_E_INVALID_ARG;
-    for (size_t i = 0; i < batch; i++)
-        if (msg_off[i + 1] < msg_off[i]) return FRW_E_INVALID_ARG;        // offsets must be non-decreasing
+    if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     size_t W = 0;
     if (!pok_prove_shape(pk, r, circuit, logn, &W) || frw::r1cs_device(r) != ctx->device) return FRW_E_INVALID_ARG;
-    frw::HostArena &A = ctx->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    FRW_HIP(hipSetDevice(ctx->device));
-    const size_t pk_len = FRW_PK_LEN(logn), chunk = std::min(batch, POK_PROVE_CHUNK), ibytes = (((size_t)2 << logn) + 1) * 32;
+    const size_t chunk = std::min(batch, POK_PROVE_CHUNK), ibytes = frw::circuit_shape(circuit, logn).num_instance * 32;
     const size_t wire_len = frw_groth16_proof_wire_bytes(wire_mode);
-    size_t max_msg = 1;                                                   // the longest pass's message bytes
-    for (size_t lo = 0; lo < batch; lo += chunk)
-        max_msg = std::max<size_t>(max_msg, (size_t)(msg_off[std::min(batch, lo + chunk)] - msg_off[lo]));
-    // the staged inputs' layout == their device layout: ONE copy in per pass
-    frw::Carve hs(nullptr);
-    const size_t o_pkb = hs.off; hs.take(chunk * pk_len);
-    const size_t o_sigb = hs.off; hs.take(chunk * sig_len);
-    const size_t o_msgs = hs.off; hs.take(max_msg);
-    const size_t o_off = hs.off; hs.take((chunk + 1) * sizeof(uint64_t));
-    const size_t o_rs = hs.off; hs.take(chunk * 64);
-    const size_t in_total = hs.off;
+    const frw::StagedInputs in(logn, batch, chunk, pk_bytes, sig_bytes, sig_len, msgs, msg_off, rs);
     const size_t ws_bytes = frw_pok_prove_workspace_bytes(pk, r, circuit, logn, chunk, std::min(chunk, POK_PROVE_HOST_IN_FLIGHT));
     if (ws_bytes == 0) return FRW_E_INVALID_ARG;
     frw::Carve c(nullptr);
-    c.take(in_total);
+    c.take(in.bytes);
     const size_t o_ws = c.off;   c.take(ws_bytes);
     const size_t o_wire = c.off; c.take(chunk * wire_len);
     const size_t o_prf = c.off;  c.take(chunk * 384);
     const size_t o_inst = c.off; c.take(instance ? chunk * ibytes : 0);
     const size_t o_st = c.off;   c.take(chunk * sizeof(int32_t));
     const size_t o_uns = c.off;  c.take(chunk * sizeof(uint32_t));
-    FRW_HIP(A.reserve_device(0, c.off));
-    FRW_HIP(A.reserve_pinned(in_total));
-    char *d = (char *)A.d_slot[0], *h = (char *)A.h_pin;
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        const size_t msg_bytes = (size_t)(msg_off[lo + cnt] - msg_off[lo]);
-        memcpy(h + o_pkb, pk_bytes + lo * pk_len, cnt * pk_len);
-        memcpy(h + o_sigb, sig_bytes + lo * sig_len, cnt * sig_len);
-        if (msg_bytes) memcpy(h + o_msgs, msgs + msg_off[lo], msg_bytes);
-        uint64_t *off = (uint64_t *)(h + o_off);
-        for (size_t i = 0; i <= cnt; i++) off[i] = msg_off[lo + i] - msg_off[lo];
-        memcpy(h + o_rs, rs + lo * 8, cnt * 64);
-        FRW_HIP(hipMemcpyAsync(d, h, in_total, hipMemcpyHostToDevice, st));
-        const int rc = frw_pok_prove_from_bytes_dev(ctx, pk, r, circuit, logn, cnt, (const uint8_t *)(d + o_pkb), (const uint8_t *)(d + o_sigb),
-                                                    sig_len, (const uint8_t *)(d + o_msgs), (const uint64_t *)(d + o_off),
-                                                    (const uint64_t *)(d + o_rs), wire_mode, (uint8_t *)(d + o_wire),
-                                                    proofs ? (uint64_t *)(d + o_prf) : nullptr, instance ? (uint64_t *)(d + o_inst) : nullptr,
-                                                    (int32_t *)(d + o_st), num_unsatisfied ? (uint32_t *)(d + o_uns) : nullptr, d + o_ws,
-                                                    ws_bytes, st);
-        if (rc != FRW_OK) return rc;
-        FRW_HIP(hipMemcpyAsync(wire + lo * wire_len, d + o_wire, cnt * wire_len, hipMemcpyDeviceToHost, st));
-        if (proofs) FRW_HIP(hipMemcpyAsync(proofs + lo * 48, d + o_prf, cnt * 384, hipMemcpyDeviceToHost, st));
-        if (instance) FRW_HIP(hipMemcpyAsync((char *)instance + lo * ibytes, d + o_inst, cnt * ibytes, hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipMemcpyAsync(status + lo, d + o_st, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (num_unsatisfied) FRW_HIP(hipMemcpyAsync(num_unsatisfied + lo, d + o_uns, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        FRW_HIP(hipStreamSynchronize(st));           // the staged inputs and the slot are reused by the next pass
-    }
-    drain.settled = true;
-    return strict && any_refused(status, batch) ? FRW_E_RANGE : FRW_OK;
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, batch, chunk, 1, c.off, in.bytes,
+        {{wire, o_wire, wire_len}, {proofs, o_prf, 384}, {instance, o_inst, ibytes}, {status, o_st, sizeof(int32_t)},
+         {num_unsatisfied, o_uns, sizeof(uint32_t)}},
+        [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
+            in.fill(stage, lo, cnt);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            return frw_pok_prove_from_bytes_dev(ctx, pk, r, circuit, logn, cnt, in.d_pk(d), in.d_second(d), sig_len, in.d_msgs(d), in.d_off(d),
+                                                in.d_rs(d), wire_mode, (uint8_t *)(d + o_wire), proofs ? (uint64_t *)(d + o_prf) : nullptr,
+                                                instance ? (uint64_t *)(d + o_inst) : nullptr, (int32_t *)(d + o_st),
+                                                num_unsatisfied ? (uint32_t *)(d + o_uns) : nullptr, d + o_ws, ws_bytes, st);
+        });
+    return strict_verdict(rc, strict, status, batch);
 }
 
 int frw_gadget_block_len(int kind)
@@ -1234,6 +1039,7 @@ int frw_gadget(frw_ctx *ctx, int kind, size_t count, const void *a, const uint64
     FRW_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     if (status) FRW_HIP(hipMemcpyAsync(status, d_st, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FRW_HIP(hipStreamSynchronize(st));
+    drain.settled = true;
     return FRW_OK;
 }
 

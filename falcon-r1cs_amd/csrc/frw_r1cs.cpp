@@ -22,10 +22,10 @@
 #include "../../include/frw.h"
 #include "frw_arena.h"
 #include "frw_device.h"
+#include "frw_stage.h"
 #include "host/frw_host.hpp"
 
 namespace {
-bool known_circuit(int circuit) { return circuit == FRW_CIRCUIT_NTT || circuit == FRW_CIRCUIT_DUAL_NTT || circuit == FRW_CIRCUIT_SCHOOLBOOK; }
 frw::host::ConstraintMatrices build_matrices(int circuit, int logn)
 {
     using namespace frw::host;
@@ -247,7 +247,7 @@ void upload_qap_tables(frw_r1cs *r, uint64_t num_constraints, uint64_t num_insta
 
 extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
 {
-    if (!out || (logn != 9 && logn != 10) || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
+    if (!out || (logn != 9 && logn != 10) || !frw::known_circuit(circuit)) return FRW_E_INVALID_ARG;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FRW_E_NO_DEVICE;
@@ -631,37 +631,25 @@ extern "C" int frw_qap_witness_map(const frw_r1cs *r, size_t batch, const uint64
     if (!r || (batch && (!witness || !instance || !h))) return FRW_E_INVALID_ARG;
     if (r->qap.num_passes < 2) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
-    frw::HostArena &A = r->arena;
-    std::lock_guard<std::mutex> lock(A.mu);
-    frw::DrainOnExit drain(A);
-    hipError_t e = hipSetDevice(r->device);
-    if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
     const size_t n = (size_t)1 << r->qap.log_n, W = r->dev.num_witness, I = r->dev.num_instance;
     const size_t chunk = std::min<size_t>(batch, 64), per = frw::qap_workspace_bytes_per_signature(r->dev, r->qap);
-    // one arena slot, carved (grow-only: a second call of the same size allocates nothing)
-    frw::Carve size(nullptr);
-    size.take(chunk * W * 32); size.take(chunk * I * 32); size.take(chunk * n * 32); size.take(chunk * per);
-    size.take(chunk * sizeof(uint32_t));
-    if ((e = A.reserve_device(0, size.off)) != hipSuccess) return frw::record_hip_error(e, "frw_qap_witness_map: device memory");
-    frw::Carve c(A.d_slot[0]);
-    uint64_t *d_wit = c.take<uint64_t>(chunk * W * 32), *d_inst = c.take<uint64_t>(chunk * I * 32);
-    uint64_t *d_h = c.take<uint64_t>(chunk * n * 32);
-    void *d_ws = c.take(chunk * per);
-    uint32_t *d_bad = c.take<uint32_t>(chunk * sizeof(uint32_t));
-    hipStream_t st = A.compute;
-    for (size_t lo = 0; lo < batch; lo += chunk) {
-        const size_t cnt = std::min(chunk, batch - lo);
-        if ((e = hipMemcpyAsync(d_wit, witness + lo * W * 4, cnt * W * 32, hipMemcpyHostToDevice, st)) == hipSuccess)
-            e = hipMemcpyAsync(d_inst, instance + lo * I * 4, cnt * I * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = frw::launch_qap_witness_map(r->dev, r->qap, cnt, d_wit, d_inst, d_h, d_bad, d_ws, chunk * per, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h + lo * n * 4, d_h, cnt * n * 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && num_unsatisfied)
-            e = hipMemcpyAsync(num_unsatisfied + lo, d_bad, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return frw::record_hip_error(e, "frw_qap_witness_map");
-    }
-    return FRW_OK;
+    frw::Carve c(nullptr);
+    const size_t o_wit = c.off;  c.take(chunk * W * 32);
+    const size_t o_inst = c.off; c.take(chunk * I * 32);
+    const size_t o_h = c.off;    c.take(chunk * n * 32);
+    const size_t o_ws = c.off;   c.take(chunk * per);
+    const size_t o_bad = c.off;  c.take(chunk * sizeof(uint32_t));
+    // one slot, nothing page-locked: the vectors are copied in straight from the caller's memory
+    return frw::host_passes(
+        r->arena, r->device, batch, chunk, 1, c.off, 0, {{h, o_h, n * 32}, {num_unsatisfied, o_bad, sizeof(uint32_t)}},
+        [&](char *d, char *, size_t lo, size_t cnt, hipStream_t st) -> int {
+            hipError_t e = hipMemcpyAsync(d + o_wit, witness + lo * W * 4, cnt * W * 32, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(d + o_inst, instance + lo * I * 4, cnt * I * 32, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess)
+                e = frw::launch_qap_witness_map(r->dev, r->qap, cnt, (const uint64_t *)(d + o_wit), (const uint64_t *)(d + o_inst),
+                                                (uint64_t *)(d + o_h), (uint32_t *)(d + o_bad), d + o_ws, chunk * per, st);
+            return e == hipSuccess ? FRW_OK : frw::record_hip_error(e, "frw_qap_witness_map");
+        });
 }
 
 extern "C" int frw_r1cs_diag_host_allocations(const frw_r1cs *r, uint64_t *count)
@@ -681,7 +669,7 @@ extern "C" int frw_r1cs_check_dev(const frw_r1cs *r, size_t batch, const uint64_
 extern "C" int frw_r1cs_export(int circuit, int logn, const char *path, uint64_t *counts /* 6 x u64, may be NULL */)
 {
     using namespace frw::host;
-    if ((logn != 9 && logn != 10) || !path || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
+    if ((logn != 9 && logn != 10) || !path || !frw::known_circuit(circuit)) return FRW_E_INVALID_ARG;
     try {
         ConstraintMatrices m = build_matrices(circuit, logn);
         if (counts) {
@@ -1038,7 +1026,7 @@ extern "C" int frw_groth16_setup(int device, int circuit, int logn, const uint64
                                  frw_groth16_pk **pk_out, uint64_t *vk_out)
 {
     using namespace frw::host;
-    if (!toxic || !pk_out || (logn != 9 && logn != 10) || !known_circuit(circuit)) return FRW_E_INVALID_ARG;
+    if (!toxic || !pk_out || (logn != 9 && logn != 10) || !frw::known_circuit(circuit)) return FRW_E_INVALID_ARG;
     *pk_out = nullptr;
     try {
         const ConstraintMatrices m = build_matrices(circuit, logn);

@@ -265,20 +265,32 @@ def test_tampered_bytes_are_refused_and_their_neighbours_are_not(engine, logn):
     assert FC.comp_decode(sg_a[:100], logn) is None
 
 
+_AROUND_THE_RATE = []
+
+
+def _signed_around_the_rate():
+    """Falcon-512 signatures of messages of 0, 95, 96, 97 and 200 bytes under the first fixture key -> (pk_bytes, msgs, sigs); signed once"""
+    if not _AROUND_THE_RATE:
+        logn = 9
+        case = _cases(logn)[0]
+        seed = bytes.fromhex(case["key_seed"])
+        sk = S.keygen(logn, seed)
+        pk_bytes = sk.public_key_bytes()
+        assert pk_bytes.hex() == case["pk_bytes"]
+        lengths = [0, 95, 96, 97, 200]
+        msgs = [bytes((7 * i + k) & 255 for i in range(k)) for k in lengths]
+        sigs = [S.sign(sk, m, seed + bytes([k & 255])) for m, k in zip(msgs, lengths)]
+        assert all(S.verify(pk_bytes, m, s, logn) for m, s in zip(msgs, sigs))
+        _AROUND_THE_RATE.append((pk_bytes, msgs, sigs))
+    return _AROUND_THE_RATE[0]
+
+
 # ---- 8. message lengths around the SHAKE rate ------------------------------------------------------------------------------------------
 def test_message_lengths_around_the_shake_rate(engine):
     """nonce || msg is 136 bytes, SHAKE256's rate, at a 96-byte message: 95, 96 and 97 straddle the block boundary; 0 is the empty
     message, 200 a third block.  Signed here with oracle/falcon_sign.py from the first fixture key's seed."""
     logn = 9
-    case = _cases(logn)[0]
-    seed = bytes.fromhex(case["key_seed"])
-    sk = S.keygen(logn, seed)
-    pk_bytes = sk.public_key_bytes()
-    assert pk_bytes.hex() == case["pk_bytes"]
-    lengths = [0, 95, 96, 97, 200]
-    msgs = [bytes((7 * i + k) & 255 for i in range(k)) for k in lengths]
-    sigs = [S.sign(sk, m, seed + bytes([k & 255])) for m, k in zip(msgs, lengths)]
-    assert all(S.verify(pk_bytes, m, s, logn) for m, s in zip(msgs, sigs))
+    pk_bytes, msgs, sigs = _signed_around_the_rate()
     want = [_spec_sum(pk_bytes, m, s, logn) for m, s in zip(msgs, sigs)]
     for rule in RULES:
         st, nrm = _from_bytes(engine, logn, [pk_bytes] * 5, sigs, msgs, rule)
@@ -315,6 +327,70 @@ def test_host_buffer_forms_and_strict(engine):
     good = np.nonzero(st == OK)[0]
     st3, _ = engine.falcon_verify(logn, sig[good], pk[good], hm[good], FV.RULE_SPEC)                        # strict, nothing refused
     assert not st3.any()
+
+
+# ---- 9b. the host-buffer forms past their first pass -----------------------------------------------------------------------------------
+PASS = 16384                                         # signatures of one pass of the host-buffer forms (FALCON_VERIFY_CHUNK in frw_capi.cpp)
+
+
+def _strict_is_e_range(rc, got, want):
+    assert rc == -5
+    for g, w in zip(got, want):
+        assert np.array_equal(g, w)
+
+
+def test_host_form_in_two_passes_equals_the_device_form(engine):
+    """16,387 Falcon-512 triples = one full pass and three more, tiled from 131 valid ones (131 does not divide 16,384).  The device form
+    does not chunk: its statuses and norms over the whole batch are the reference.  Slot 16,385 (second pass) has another hm."""
+    import falcon_r1cs_amd as frw
+    logn, batch, bad = 9, PASS + 3, PASS + 1
+    tile = np.arange(batch) % 131
+    sig, pk, hm = (a[tile] for a in frw.synth_triples(logn, 131, seed=16387))
+    hm[bad] = np.random.default_rng(16387).integers(0, Q, 512, dtype=np.uint16)
+    want_st, want_nrm = _verify(engine, logn, sig, pk, hm, FV.RULE_CIRCUIT)
+    assert np.nonzero(want_st)[0].tolist() == [bad] and want_st[bad] == NORM_BOUND
+    st, nrm = engine.falcon_verify(logn, sig, pk, hm, FV.RULE_CIRCUIT, strict=False)
+    assert np.array_equal(st, want_st) and np.array_equal(nrm.view(np.int64), want_nrm)
+    assert nrm[PASS] != nrm[0] and nrm[PASS] == nrm[PASS % 131]             # (the second pass is not the first one again)
+    st2, none = engine.falcon_verify(logn, sig, pk, hm, FV.RULE_CIRCUIT, strict=False, want_norm=False)     # norm = NULL
+    assert none is None and np.array_equal(st2, want_st)
+    # strict through the C entry point itself: FRW_E_RANGE, and the buffers are complete all the same
+    h_st, h_nrm = np.full(batch, -7, dtype=np.int32), np.full(batch, 5, dtype=np.uint64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    s_, p_, h_ = (np.ascontiguousarray(a) for a in (sig, pk, hm))
+    rc = engine._lib.frw_falcon_verify(engine._ctx, logn, batch, p(s_), p(p_), p(h_), FV.RULE_CIRCUIT, p(h_st), p(h_nrm), 1)
+    _strict_is_e_range(rc, (h_st, h_nrm.view(np.int64)), (want_st, want_nrm))
+
+
+def test_host_form_from_bytes_in_two_passes_equals_the_device_form(engine):
+    """16,387 encoded Falcon-512 signatures tiled from the two genuine cases and five signed here over messages of 0, 95, 96, 97 and 200
+    bytes: a period of 7, which does not divide 16,384, so the second pass's messages differ from those at the same positions of the
+    first and their offsets have to be rebased.  Slot 16,385 has one message byte flipped."""
+    import falcon_r1cs_amd as frw
+    logn, batch, bad = 9, PASS + 3, PASS + 1
+    pk_a, msgs_a, sigs_a = _signed_around_the_rate()
+    seven = [(pk_a, m, s) for m, s in zip(msgs_a, sigs_a)] + [tuple(bytes.fromhex(c[k]) for k in ("pk_bytes", "msg", "sig_bytes")) for c in _cases(logn)]
+    assert len(seven) == 7 and PASS % 7 and {len(t[1]) for t in seven} >= {0, 95, 96, 97, 200}
+    entries = [seven[i % 7] for i in range(batch)]
+    assert [e[1] for e in entries[PASS:PASS + 3]] != [e[1] for e in entries[:3]]
+    k, m, s = entries[bad]
+    assert len(m) > 3
+    entries[bad] = (k, m[:3] + bytes([m[3] ^ 1]) + m[4:], s)
+    pkb, msgs, sgb = ([e[j] for e in entries] for j in range(3))
+    want_st, want_nrm = _from_bytes(engine, logn, pkb, sgb, msgs, FV.RULE_SPEC)
+    assert np.nonzero(want_st)[0].tolist() == [bad] and want_st[bad] == NORM_BOUND
+    assert want_nrm[:7].tolist() == [_spec_sum(*t, logn) for t in ((e[0], e[1], e[2]) for e in seven)]
+    st, nrm = engine.falcon_verify_from_bytes(logn, pkb, sgb, msgs, FV.RULE_SPEC, strict=False)
+    assert np.array_equal(st, want_st) and np.array_equal(nrm.view(np.int64), want_nrm)
+    st2, none = engine.falcon_verify_from_bytes(logn, pkb, sgb, msgs, FV.RULE_SPEC, strict=False, want_norm=False)      # norm = NULL
+    assert none is None and np.array_equal(st2, want_st)
+    # strict through the C entry point itself: FRW_E_RANGE, and the buffers are complete all the same
+    _, sig_len, a_pk, a_sg, blob, off = engine._falcon_verify_bytes(logn, pkb, sgb, msgs)
+    h_st, h_nrm = np.full(batch, -7, dtype=np.int32), np.full(batch, 5, dtype=np.uint64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = engine._lib.frw_falcon_verify_from_bytes(engine._ctx, logn, batch, p(a_pk), p(a_sg), sig_len, p(blob), p(off), FV.RULE_SPEC, p(h_st),
+                                                  p(h_nrm), 1)
+    _strict_is_e_range(rc, (h_st, h_nrm.view(np.int64)), (want_st, want_nrm))
 
 
 # ---- 10. screening an aggregate --------------------------------------------------------------------------------------------------------

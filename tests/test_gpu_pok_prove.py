@@ -355,3 +355,32 @@ def test_host_form_equals_the_device_form(keys, mixed):
         assert np.array_equal(got, outs[2][name]), name
     with pytest.raises(frw.FrwError):
         engine.pok_prove_from_bytes(key, r1cs, NTT, 9, pkb, sgb, msgs, rs)
+
+
+def test_host_form_in_two_passes_equals_the_device_form(keys):
+    """259 slots = one full pass of the host-buffer form (POK_PROVE_CHUNK = 256 in frw_capi.cpp) and three more.  Slots 0, 1 and 257
+    genuine, every other one with a bad signature header: three proofs are made, one of them in the second pass.  The device form over the
+    whole batch is the reference.  The genuine messages have different lengths, so the second pass's offsets have to be rebased."""
+    engine = keys.engine
+    key, r1cs, _ = keys.get(NTT, 9)
+    g = PC.genuine(9, 3)
+    assert len({len(t[1]) for t in g}) > 1
+    batch, where = 259, (0, 1, 257)
+    items = [(PC.bad_header(g[i % 3]), PC.blinding("refused")) for i in range(batch)]
+    status = [PC.DECODE] * batch
+    for slot, k in zip(where, range(3)):
+        items[slot] = (g[k], PC.blinding("g%d" % k))
+        status[slot] = PC.OK
+    want = run(keys, NTT, 9, items, 3)
+    assert want["status"].tolist() == status
+    held_to_the_chain(keys, NTT, 9, [items[s] for s in where], {k: v[list(where)] for k, v in want.items()}, [PC.OK] * 3)
+    pkb, msgs, sgb = ([t[k] for t, _ in items] for k in range(3))
+    rs = np.stack([r for _, r in items])
+    host = engine.pok_prove_from_bytes(key, r1cs, NTT, 9, pkb, sgb, msgs, rs, strict=False)
+    for name in ("wire", "proofs", "instance", "status", "num_unsatisfied"):
+        assert np.array_equal(host[name], want[name]), name
+    rest = np.ones(batch, dtype=bool)
+    rest[list(where)] = False
+    for name in ("wire", "proofs", "instance", "num_unsatisfied"):
+        assert not host[name][rest].any(), name
+    assert all(host["wire"][s].any() for s in where)

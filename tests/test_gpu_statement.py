@@ -212,6 +212,62 @@ def test_host_buffer_form_and_strict(engine):
     assert hst.tolist() == [0, 0, frw.ST_COEFF_RANGE, 0, 0] and not inst[2].any() and inst[3].any()
 
 
+# ---- 4b. the host-buffer forms past their first pass ------------------------------------------------------------------------------------
+PASS = 4096                                          # statements of one pass of the host-buffer forms (STATEMENT_CHUNK in frw_capi.cpp)
+
+
+def test_host_form_in_two_passes_equals_the_device_form(engine):
+    """4,099 Falcon-512 statements = one full pass and three more.  The device form does not chunk: its instance vectors and statuses
+    over the whole batch are the reference, byte for byte.  Statement 4,097 (second pass) has a key coefficient of q."""
+    import falcon_r1cs_amd as frw
+    logn, batch, bad = 9, PASS + 3, PASS + 1
+    _, pk, hm = frw.synth_triples(logn, batch, seed=4099)
+    pk = pk.copy()
+    pk[bad, 11] = Q
+    want, want_st, intact = _statement(engine, 0, logn, pk, hm, 1)
+    want, want_st = want.cpu().numpy(), want_st.cpu().numpy()
+    assert intact and np.nonzero(want_st)[0].tolist() == [bad] and want_st[bad] == frw.ST_COEFF_RANGE
+    inst, st = engine.statement(0, logn, pk, hm, strict=False)
+    assert np.array_equal(st, want_st)
+    assert np.array_equal(inst.view(np.int64), want)
+    assert not inst[bad].any() and inst[bad - 1].any() and inst[bad + 1].any()
+    assert not np.array_equal(inst[PASS], inst[0])               # (the second pass is not the first one again)
+    with pytest.raises(frw.FrwError) as ei:
+        engine.statement(0, logn, pk, hm)
+    assert ei.value.code == -5
+
+
+def test_host_form_from_bytes_in_two_passes_equals_the_device_form(engine):
+    """4,099 statements tiled from the two Falcon-512 keys and nonces of the genuine cases with messages of 0, 95, 96, 97, 33, 200 and 13
+    bytes (nonce || msg is SHAKE256's rate at 96): a period of 7, which does not divide 4,096, so the second pass's messages differ from
+    those at the same positions of the first and their offsets have to be rebased.  Statement 4,097's key has a wrong header byte."""
+    import torch
+    import falcon_r1cs_amd as frw
+    logn, batch, bad = 9, PASS + 3, PASS + 1
+    sel = [c for c in _cases() if c["logn"] == logn]
+    keys = [bytes.fromhex(c["pk_bytes"]) for c in sel]
+    nonces = [bytes.fromhex(c["sig_bytes"])[1:41] for c in sel]
+    lengths = [0, 95, 96, 97, 33, 200, 13]
+    period = [bytes((5 * i + k) & 255 for i in range(k)) for k in lengths]
+    pkb = [keys[(i // 7) % 2] for i in range(batch)]
+    non = [nonces[(i // 3) % 2] for i in range(batch)]
+    msgs = [period[i % 7] for i in range(batch)]
+    assert PASS % 7 and msgs[PASS:PASS + 3] != msgs[:3]
+    pkb[bad] = bytes([pkb[bad][0] ^ 0x10]) + pkb[bad][1:]
+    d_inst, d_st = engine.statement_from_bytes_dev(0, logn, pkb, non, msgs, frw.ENC_MONTGOMERY)
+    torch.cuda.synchronize()
+    want, want_st = d_inst.cpu().numpy(), d_st.cpu().numpy()
+    assert np.nonzero(want_st)[0].tolist() == [bad] and want_st[bad] == frw.ST_DECODE
+    inst, st = engine.statement_from_bytes(0, logn, pkb, non, msgs, frw.ENC_MONTGOMERY, strict=False)
+    assert np.array_equal(st, want_st)
+    assert np.array_equal(inst.view(np.int64), want)
+    assert not inst[bad].any() and inst[bad - 1].any() and inst[bad + 1].any()
+    assert not np.array_equal(inst[PASS], inst[0])
+    with pytest.raises(frw.FrwError) as ei:
+        engine.statement_from_bytes(0, logn, pkb, non, msgs)
+    assert ei.value.code == -5
+
+
 # ---- 5. aggregate ----------------------------------------------------------------------------------------------------------------------
 def test_aggregate_statement_equals_aggregate_assign(engine):
     import torch

@@ -51,3 +51,7 @@ ASAN_OPTIONS=detect_leaks=0 /tmp/frw_pok_prove_layout_asan | tail -1
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wno-unknown-pragmas -fno-strict-aliasing \
     -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" -o /tmp/frw_rerand_host_asan "$ROOT/tests/cpp/test_rerand_host.cpp"
 ASAN_OPTIONS=detect_leaks=0 /tmp/frw_rerand_host_asan | tail -1
+# the host side of the bytes paths (frw_stage.h: the staged inputs pass by pass, the circuits' sizes against frw_layout*): a program of its own
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" \
+    -o /tmp/frw_stage_host_asan "$ROOT/tests/cpp/test_stage_host.cpp" -L"$ROOT/falcon-r1cs_amd" -lfrw -Wl,-rpath,"$ROOT/falcon-r1cs_amd"
+ASAN_OPTIONS=detect_leaks=0 /tmp/frw_stage_host_asan | tail -1

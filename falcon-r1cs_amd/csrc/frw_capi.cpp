@@ -995,6 +995,273 @@ int frw_pok_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r
     return strict_verdict(rc, strict, status, batch);
 }
 
+// ---- an aggregate from bytes: the encoded (pk, msg, sig) of its statements, in statement order -> verdicts, the verifier's statement,
+// ONE proof on the wire ---------------------------------------------------------------------------------------------------------------
+namespace {
+// an aggregate handle on the context's device, and how many statements of each parameter set it has; null: not one
+const frw::R1csAgg *aggregate_on(const frw_r1cs *aggregate, const frw_ctx *ctx, size_t count[2])
+{
+    int device = -1;
+    const frw::R1csAgg *agg = frw::r1cs_aggregate(aggregate, &device);
+    if (!agg || (ctx && device != ctx->device)) return nullptr;
+    count[0] = agg->set[0].count;
+    count[1] = agg->set[1].count;
+    return agg;
+}
+// the routed decoders and SHAKE256 into the per-set arrays of `ws`, one launch per parameter set and stage, then each set's verification
+// kernel; the verdicts (and norms) go back into statement order, and the number of refused statements into ws.refused
+hipError_t aggregate_screen_chain(const frw_ctx *ctx, const frw::R1csAgg *agg, const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes,
+                                  const uint8_t *d_msgs, const uint64_t *d_msg_off, int rule, int32_t *d_status, uint64_t *d_norm,
+                                  const frw::AggregateScreenBufs &ws, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    for (int g = 0; g < 2 && e == hipSuccess; g++) {
+        const frw::R1csAggSet &set = agg->set[g];
+        if (!set.count) continue;
+        e = frw::launch_agg_decode_public_keys(9 + g, set.count, set.stmt, d_pk_bytes, ws.pk[g], ws.pk_status[g], st);
+        if (e == hipSuccess) e = frw::launch_agg_decode_signatures(9 + g, set.count, set.stmt, d_sig_bytes, ws.sig[g], ws.nonce, ws.sig_status[g], st);
+        if (e == hipSuccess) e = frw::launch_agg_hash_to_point(9 + g, set.count, set.stmt, ws.nonce, d_msgs, d_msg_off, ws.hm[g], st);
+        if (e == hipSuccess)
+            e = frw::launch_falcon_verify(ctx->d_tables, ctx->num_cu, 9 + g, rule, set.count, ws.sig[g], ws.pk[g], ws.hm[g], ws.sig_status[g],
+                                          ws.pk_status[g], ws.status[g], ws.norm[g], st);
+    }
+    if (e != hipSuccess) return e;
+    const uint32_t *stmt[2] = {agg->set[0].stmt, agg->set[1].stmt};
+    const size_t count[2] = {agg->set[0].count, agg->set[1].count};
+    return frw::launch_agg_verdicts(stmt, ws.status, ws.norm, count, d_status, d_norm, ws.refused, st);
+}
+// frw_aggregate_statement_dev's launches on decoded keys and hashed messages that are in `ws` already, the key decoder's verdicts first
+hipError_t aggregate_statement_launches(const frw_ctx *ctx, const frw::R1csAgg *agg, int encoding, uint64_t *d_instance, int32_t *d_status,
+                                        const frw::AggregateScreenBufs &ws, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    bool first = true;
+    for (int g = 0; g < 2 && e == hipSuccess; g++) {
+        const frw::R1csAggSet &set = agg->set[g];
+        if (!set.count) continue;
+        e = frw::launch_statement(ctx->d_tables, ctx->num_cu, 9 + g, 0, encoding, set.count, ws.pk[g], ws.hm[g], d_instance, set.offs,
+                                  first ? 2 : 0, ws.pk_status[g], d_status, set.stmt, st);
+        first = false;
+    }
+    return e;
+}
+// whether `pk` is a whole key with the aggregate's instance and witness counts, on its device
+bool aggregate_key_fits(const frw_groth16_pk *pk, const frw_r1cs *aggregate)
+{
+    frw_r1cs_info_t info;
+    frw_groth16_pk_info_t ki;
+    if (!pk || frw_r1cs_info(aggregate, &info) != FRW_OK || frw_groth16_pk_info(pk, &ki) != FRW_OK || ki.world > 1) return false;
+    int device = -1;
+    uint64_t ni = 0, nw = 0, dom = 0;
+    frw::groth16_pk_counts(pk, &device, &ni, &nw, &dom);
+    return ni == info.num_instance && nw == info.num_witness && device == frw::r1cs_device(aggregate);
+}
+}  // namespace
+
+size_t frw_aggregate_screen_workspace_bytes(const frw_r1cs *aggregate)
+{
+    size_t count[2];
+    return aggregate_on(aggregate, nullptr, count) ? frw::aggregate_screen_layout(nullptr, count[0], count[1]).bytes : 0;
+}
+
+int frw_aggregate_falcon_verify_from_bytes_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *d_pk_bytes, const uint8_t *d_sig_bytes,
+                                               const uint8_t *d_msgs, const uint64_t *d_msg_off, int rule, int32_t *d_status, uint64_t *d_norm,
+                                               void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (!ctx || (rule != FRW_RULE_CIRCUIT && rule != FRW_RULE_SPEC)) return FRW_E_INVALID_ARG;
+    if (!aggregate || !d_pk_bytes || !d_sig_bytes || !d_msgs || !d_msg_off || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
+    if ((uintptr_t)d_workspace & 15) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    const frw::R1csAgg *agg = aggregate_on(aggregate, ctx, count);
+    if (!agg || workspace_bytes < frw::aggregate_screen_layout(nullptr, count[0], count[1]).bytes) return FRW_E_INVALID_ARG;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(aggregate_screen_chain(ctx, agg, d_pk_bytes, d_sig_bytes, d_msgs, d_msg_off, rule, d_status, d_norm,
+                                   frw::aggregate_screen_layout(d_workspace, count[0], count[1]), (hipStream_t)stream));
+    return FRW_OK;
+}
+
+int frw_aggregate_statement_from_bytes_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *d_pk_bytes, const uint8_t *d_nonces,
+                                           const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding, uint64_t *d_instance,
+                                           int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (bad_common(ctx, 10, encoding)) return FRW_E_INVALID_ARG;
+    if (!aggregate || !d_pk_bytes || !d_nonces || !d_msgs || !d_msg_off || !d_instance || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
+    if ((uintptr_t)d_workspace & 15) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    const frw::R1csAgg *agg = aggregate_on(aggregate, ctx, count);
+    if (!agg || workspace_bytes < frw::aggregate_screen_layout(nullptr, count[0], count[1]).bytes) return FRW_E_INVALID_ARG;
+    const frw::AggregateScreenBufs ws = frw::aggregate_screen_layout(d_workspace, count[0], count[1]);
+    hipStream_t st = (hipStream_t)stream;
+    FRW_HIP(hipSetDevice(ctx->device));
+    for (int g = 0; g < 2; g++) {
+        const frw::R1csAggSet &set = agg->set[g];
+        FRW_HIP(frw::launch_agg_decode_public_keys(9 + g, set.count, set.stmt, d_pk_bytes, ws.pk[g], ws.pk_status[g], st));
+        FRW_HIP(frw::launch_agg_hash_to_point(9 + g, set.count, set.stmt, d_nonces, d_msgs, d_msg_off, ws.hm[g], st));
+    }
+    FRW_HIP(aggregate_statement_launches(ctx, agg, encoding, d_instance, d_status, ws, st));
+    return FRW_OK;
+}
+
+size_t frw_aggregate_prove_workspace_bytes(const frw_groth16_pk *pk, const frw_r1cs *aggregate)
+{
+    size_t count[2];
+    if (!pk || !aggregate_on(aggregate, nullptr, count) || !aggregate_key_fits(pk, aggregate)) return 0;
+    const size_t g = frw_groth16_workspace_bytes(pk, aggregate, 1);
+    return g ? frw::aggregate_prove_layout(nullptr, count[0], count[1], g).bytes : 0;
+}
+
+int frw_aggregate_prove_from_bytes_dev(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *aggregate, const uint8_t *d_pk_bytes,
+                                       const uint8_t *d_sig_bytes, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint64_t *d_rs,
+                                       int wire_mode, uint8_t *d_wire, uint64_t *d_proof, uint64_t *d_instance, uint8_t *d_nonces_out,
+                                       int32_t *d_status, uint32_t *d_num_unsatisfied, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const size_t wire_len = frw_groth16_proof_wire_bytes(wire_mode);
+    if (!ctx || wire_len == 0) return FRW_E_INVALID_ARG;
+    if (!pk || !aggregate || !d_pk_bytes || !d_sig_bytes || !d_msgs || !d_msg_off || !d_rs || !d_wire || !d_status || !d_workspace)
+        return FRW_E_INVALID_ARG;
+    if ((uintptr_t)d_workspace & 255) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    const frw::R1csAgg *agg = aggregate_on(aggregate, ctx, count);
+    if (!agg || !aggregate_key_fits(pk, aggregate)) return FRW_E_INVALID_ARG;
+    const size_t g16 = frw_groth16_workspace_bytes(pk, aggregate, 1);
+    if (g16 == 0 || workspace_bytes < frw::aggregate_prove_layout(nullptr, count[0], count[1], g16).bytes) return FRW_E_INVALID_ARG;
+    const frw::AggregateProveBufs ws = frw::aggregate_prove_layout(d_workspace, count[0], count[1], g16);
+    const size_t total = count[0] + count[1];
+    hipStream_t st = (hipStream_t)stream;
+    FRW_HIP(hipSetDevice(ctx->device));
+    // 1. decode, hash and screen: d_status is frw_aggregate_falcon_verify_from_bytes_dev's under FRW_RULE_CIRCUIT
+    FRW_HIP(aggregate_screen_chain(ctx, agg, d_pk_bytes, d_sig_bytes, d_msgs, d_msg_off, FRW_RULE_CIRCUIT, d_status, nullptr, ws.screen, st));
+    // 2. the verifier's statement, from the keys, nonces and messages alone (its own status words stay in the workspace)
+    if (d_instance) FRW_HIP(aggregate_statement_launches(ctx, agg, FRW_ENC_MONTGOMERY, d_instance, ws.statement_status, ws.screen, st));
+    if (d_nonces_out) FRW_HIP(hipMemcpyAsync(d_nonces_out, ws.screen.nonce, total * FRW_NONCE_LEN, hipMemcpyDeviceToDevice, st));
+    // 3. the one host wait
+    uint32_t refused = 0;
+    FRW_HIP(hipMemcpyAsync(&refused, ws.screen.refused, sizeof refused, hipMemcpyDeviceToHost, st));
+    FRW_HIP(hipStreamSynchronize(st));
+    if (refused) {      // 4. an aggregate with a statement that cannot be proven has no proof
+        FRW_HIP(hipMemsetAsync(d_wire, 0, wire_len, st));
+        if (d_proof) FRW_HIP(hipMemsetAsync(d_proof, 0, 384, st));
+        if (d_num_unsatisfied) FRW_HIP(hipMemsetAsync(d_num_unsatisfied, 0xff, sizeof(uint32_t), st));
+        frw::record_error("frw_aggregate_prove_from_bytes_dev: %u of %zu statements refused (see the status words)", refused, total);
+        return FRW_E_RANGE;
+    }
+    // 5. every statement was accepted: the witness batches are complete, in one encoding, none zero-filled
+    for (int g = 0; g < 2; g++)
+        if (count[g])
+            FRW_HIP(launch_witness(ctx, FRW_CIRCUIT_NTT, 9 + g, FRW_ENC_MONTGOMERY, count[g], ws.screen.sig[g], ws.screen.pk[g], ws.screen.hm[g],
+                                   ws.set_witness[g], ws.set_instance[g], ws.witness_status[g], st));
+    int rc = frw_aggregate_assign_dev(aggregate, ws.set_witness[0], ws.set_instance[0], ws.set_witness[1], ws.set_instance[1], ws.witness,
+                                      ws.instance, st);
+    if (rc == FRW_OK) rc = frw_groth16_prove_rs_dev(pk, aggregate, 1, ws.witness, ws.instance, d_rs, ws.proof, ws.unsatisfied, ws.groth16_ws, ws.groth16_bytes, st);
+    if (rc == FRW_OK) rc = frw_groth16_proofs_to_wire_dev(ctx->device, 1, ws.proof, wire_mode, ws.wire, ws.wire_status, st);
+    if (rc != FRW_OK) return rc;
+    FRW_HIP(hipMemcpyAsync(d_wire, ws.wire, wire_len, hipMemcpyDeviceToDevice, st));
+    if (d_proof) FRW_HIP(hipMemcpyAsync(d_proof, ws.proof, 384, hipMemcpyDeviceToDevice, st));
+    if (d_num_unsatisfied) FRW_HIP(hipMemcpyAsync(d_num_unsatisfied, ws.unsatisfied, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return FRW_OK;
+}
+
+// The host-buffer forms: an aggregate is not divisible, so each is ONE pass of frw::host_passes over the whole statement (to the pass
+// driver: a batch of one item, the aggregate), staged by StagedAggregate (frw_stage.h).
+int frw_aggregate_falcon_verify_from_bytes(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *pk_bytes, const uint8_t *sig_bytes,
+                                           const uint8_t *msgs, const uint64_t *msg_off, int rule, int32_t *status, uint64_t *norm)
+{
+    if (!ctx || (rule != FRW_RULE_CIRCUIT && rule != FRW_RULE_SPEC)) return FRW_E_INVALID_ARG;
+    if (!aggregate || !pk_bytes || !sig_bytes || !msgs || !msg_off || !status) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    if (!aggregate_on(aggregate, ctx, count)) return FRW_E_INVALID_ARG;
+    const size_t total = count[0] + count[1];
+    if (!frw::message_offsets_ok(msgs, msg_off, total)) return FRW_E_INVALID_ARG;
+    const frw::StagedAggregate in(count[0], count[1], false, pk_bytes, sig_bytes, msgs, msg_off);
+    const size_t ws_bytes = frw_aggregate_screen_workspace_bytes(aggregate);
+    frw::Carve c(nullptr);
+    c.take(in.bytes);
+    const size_t o_ws = c.off;   c.take(ws_bytes);
+    const size_t o_norm = c.off; c.take(total * sizeof(uint64_t));
+    const size_t o_st = c.off;   c.take(total * sizeof(int32_t));
+    return frw::host_passes(
+        ctx->arena, ctx->device, 1, 1, 1, c.off, in.bytes, {{status, o_st, total * sizeof(int32_t)}, {norm, o_norm, total * sizeof(uint64_t)}},
+        [&](char *d, char *stage, size_t, size_t, hipStream_t st) -> int {
+            in.fill(stage);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            return frw_aggregate_falcon_verify_from_bytes_dev(aggregate, ctx, in.d_pk(d), in.d_second(d), in.d_msgs(d), in.d_off(d), rule,
+                                                              (int32_t *)(d + o_st), (uint64_t *)(d + o_norm), d + o_ws, ws_bytes, st);
+        });
+}
+
+int frw_aggregate_statement_from_bytes(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *pk_bytes, const uint8_t *nonces,
+                                       const uint8_t *msgs, const uint64_t *msg_off, int encoding, uint64_t *instance, int32_t *status)
+{
+    if (bad_common(ctx, 10, encoding)) return FRW_E_INVALID_ARG;
+    if (!aggregate || !pk_bytes || !nonces || !msgs || !msg_off || !instance || !status) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    if (!aggregate_on(aggregate, ctx, count)) return FRW_E_INVALID_ARG;
+    const size_t total = count[0] + count[1];
+    if (!frw::message_offsets_ok(msgs, msg_off, total)) return FRW_E_INVALID_ARG;
+    frw_r1cs_info_t info;
+    if (frw_r1cs_info(aggregate, &info) != FRW_OK) return FRW_E_INVALID_ARG;
+    const frw::StagedAggregate in(count[0], count[1], true, pk_bytes, nonces, msgs, msg_off);
+    const size_t ws_bytes = frw_aggregate_screen_workspace_bytes(aggregate), ibytes = (size_t)info.num_instance * 32;
+    frw::Carve c(nullptr);
+    c.take(in.bytes);
+    const size_t o_ws = c.off;   c.take(ws_bytes);
+    const size_t o_inst = c.off; c.take(ibytes);
+    const size_t o_st = c.off;   c.take(total * sizeof(int32_t));
+    return frw::host_passes(
+        ctx->arena, ctx->device, 1, 1, 1, c.off, in.bytes, {{instance, o_inst, ibytes}, {status, o_st, total * sizeof(int32_t)}},
+        [&](char *d, char *stage, size_t, size_t, hipStream_t st) -> int {
+            in.fill(stage);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            return frw_aggregate_statement_from_bytes_dev(aggregate, ctx, in.d_pk(d), in.d_second(d), in.d_msgs(d), in.d_off(d), encoding,
+                                                          (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), d + o_ws, ws_bytes, st);
+        });
+}
+
+int frw_aggregate_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *aggregate, const uint8_t *pk_bytes,
+                                   const uint8_t *sig_bytes, const uint8_t *msgs, const uint64_t *msg_off, const uint64_t *rs, int wire_mode,
+                                   uint8_t *wire, uint64_t *proof, uint64_t *instance, uint8_t *nonces_out, int32_t *status,
+                                   uint32_t *num_unsatisfied)
+{
+    const size_t wire_len = frw_groth16_proof_wire_bytes(wire_mode);
+    if (!ctx || wire_len == 0) return FRW_E_INVALID_ARG;
+    if (!pk || !aggregate || !pk_bytes || !sig_bytes || !msgs || !msg_off || !rs || !wire || !status) return FRW_E_INVALID_ARG;
+    size_t count[2];
+    if (!aggregate_on(aggregate, ctx, count)) return FRW_E_INVALID_ARG;
+    const size_t total = count[0] + count[1];
+    if (!frw::message_offsets_ok(msgs, msg_off, total)) return FRW_E_INVALID_ARG;
+    const size_t ws_bytes = frw_aggregate_prove_workspace_bytes(pk, aggregate);
+    frw_r1cs_info_t info;
+    if (ws_bytes == 0 || frw_r1cs_info(aggregate, &info) != FRW_OK) return FRW_E_INVALID_ARG;
+    const frw::StagedAggregate in(count[0], count[1], false, pk_bytes, sig_bytes, msgs, msg_off, rs);
+    const size_t ibytes = (size_t)info.num_instance * 32;
+    frw::Carve c(nullptr);
+    c.take(in.bytes);
+    const size_t o_ws = c.off;   c.take(ws_bytes);
+    const size_t o_wire = c.off; c.take(wire_len);
+    const size_t o_prf = c.off;  c.take(384);
+    const size_t o_inst = c.off; c.take(instance ? ibytes : 0);
+    const size_t o_non = c.off;  c.take(total * FRW_NONCE_LEN);
+    const size_t o_st = c.off;   c.take(total * sizeof(int32_t));
+    const size_t o_uns = c.off;  c.take(sizeof(uint32_t));
+    bool refused = false;           // the outputs of a refused aggregate are complete and go out like any others; the verdict comes after
+    const int rc = frw::host_passes(
+        ctx->arena, ctx->device, 1, 1, 1, c.off, in.bytes,
+        {{wire, o_wire, wire_len}, {proof, o_prf, 384}, {instance, o_inst, ibytes}, {nonces_out, o_non, total * FRW_NONCE_LEN},
+         {status, o_st, total * sizeof(int32_t)}, {num_unsatisfied, o_uns, sizeof(uint32_t)}},
+        [&](char *d, char *stage, size_t, size_t, hipStream_t st) -> int {
+            in.fill(stage);
+            FRW_HIP(hipMemcpyAsync(d, stage, in.bytes, hipMemcpyHostToDevice, st));
+            const int r = frw_aggregate_prove_from_bytes_dev(ctx, pk, aggregate, in.d_pk(d), in.d_second(d), in.d_msgs(d), in.d_off(d), in.d_rs(d),
+                                                             wire_mode, (uint8_t *)(d + o_wire), proof ? (uint64_t *)(d + o_prf) : nullptr,
+                                                             instance ? (uint64_t *)(d + o_inst) : nullptr,
+                                                             nonces_out ? (uint8_t *)(d + o_non) : nullptr, (int32_t *)(d + o_st),
+                                                             num_unsatisfied ? (uint32_t *)(d + o_uns) : nullptr, d + o_ws, ws_bytes, st);
+            refused = r == FRW_E_RANGE;
+            return refused ? FRW_OK : r;
+        });
+    return rc == FRW_OK && refused ? FRW_E_RANGE : rc;
+}
+
 int frw_gadget_block_len(int kind)
 {
     static const int len[6] = {27, 29, 29, 18, 50, 52};

@@ -104,6 +104,19 @@ hipError_t launch_hash_to_point(int logn, size_t batch, const uint8_t *nonces, c
 hipError_t launch_decode_public_keys(int logn, size_t batch, const uint8_t *pk_bytes, uint16_t *pk, int32_t *status, hipStream_t st);
 hipError_t launch_decode_signatures(int logn, size_t batch, const uint8_t *sig_bytes, size_t sig_len, uint16_t *sig,
                                     uint8_t *nonce_out, int32_t *status, hipStream_t st);
+// the same three for ONE parameter set of an aggregate whose encoded inputs lie in statement order, both sets mixed (frw_prepare.hip):
+// item k of the launch is statement stmt[k] (R1csAggSet::stmt), its bytes are where aggregate_route (frw_layout.h) says, its decoded
+// row is row k of the set's dense array.  nonces: count-of-all-statements x 40 bytes in statement order -- read by the hash, written by
+// the signature decoder (always: the 40 bytes behind the header, whatever the header is).
+hipError_t launch_agg_hash_to_point(int logn, size_t count, const uint32_t *stmt, const uint8_t *nonces, const uint8_t *msgs,
+                                    const uint64_t *msg_off, uint16_t *hm, hipStream_t st);
+hipError_t launch_agg_decode_public_keys(int logn, size_t count, const uint32_t *stmt, const uint8_t *pk_bytes, uint16_t *pk, int32_t *status,
+                                         hipStream_t st);
+hipError_t launch_agg_decode_signatures(int logn, size_t count, const uint32_t *stmt, const uint8_t *sig_bytes, uint16_t *sig, uint8_t *nonces,
+                                        int32_t *status, hipStream_t st);
+// both sets' verdicts (set_norm -> norm only where norm is non-null) into statement order, then refused[0] = the statuses that are not FRW_ST_OK
+hipError_t launch_agg_verdicts(const uint32_t *const stmt[2], const int32_t *const set_status[2], const uint64_t *const set_norm[2],
+                               const size_t count[2], int32_t *status, uint64_t *norm, uint32_t *refused, hipStream_t st);
 // compaction for the prover from bytes (frw_prepare.hip).  launch_pok_scan: index[0 .. count) = the slots whose status is FRW_ST_OK, in
 // slot order, count[0] = their number (block_sums: one word per BLOCK slots of scratch; any batch).  The gathers make the blinding
 // factors of all accepted slots and the (sig, pk, hm) rows of one chunk of them dense; launch_pok_zero_refused writes zeros to every output

@@ -397,6 +397,109 @@ inline PokProveBufs pok_prove_layout(void *ws, int logn, size_t batch, size_t k,
     b.bytes = c.off;
     return b;
 }
+// ---- an aggregate's inputs from bytes (frw_aggregate_*_from_bytes_dev).  The encoded keys, and the encoded signatures, of the statements
+// lie end to end in STATEMENT order, Falcon-512 and Falcon-1024 mixed (set g = logn - 9): 897 | 1,793 bytes a key, 666 | 1,280 a signature,
+// so nothing is aligned.  Item k of set g is the k-th statement of that set, statement s of the aggregate (R1csAggSet::stmt): k statements
+// of its own set and s - k of the other one lie before it.  The nonces are 40 bytes a statement, in statement order.  This one function is
+// where the kernels (frw_prepare.hip), the size functions and the host-side staging (frw_stage.h) get it from.
+__host__ __device__ constexpr size_t aggregate_pk_len(int g) { return g ? 1793 : 897; }        // FRW_PK_LEN(9 + g)
+__host__ __device__ constexpr size_t aggregate_sig_len(int g) { return g ? 1280 : 666; }       // FRW_SIG_LEN(9 + g)
+struct AggRoute { size_t pk_off, sig_off, nonce_off; };
+__host__ __device__ inline AggRoute aggregate_route(int g, size_t k, size_t s)
+{
+    const size_t other = s - k;
+    AggRoute r;
+    r.pk_off = k * aggregate_pk_len(g) + other * aggregate_pk_len(g ^ 1);
+    r.sig_off = k * aggregate_sig_len(g) + other * aggregate_sig_len(g ^ 1);
+    r.nonce_off = s * 40;
+    return r;
+}
+// all the keys' | signatures' bytes of an aggregate of count9 Falcon-512 and count10 Falcon-1024 statements: where statement `count` would start
+__host__ __device__ inline size_t aggregate_pk_bytes(size_t count9, size_t count10) { return aggregate_route(0, count9, count9 + count10).pk_off; }
+__host__ __device__ inline size_t aggregate_sig_bytes(size_t count9, size_t count10) { return aggregate_route(0, count9, count9 + count10).sig_off; }
+
+// ---- the screen of an aggregate from bytes (frw_aggregate_falcon_verify_from_bytes_dev; frw_aggregate_statement_from_bytes_dev uses the
+// pk, hm and pk_status pieces of the same layout).  Per parameter set g, dense in the set's own order: the decoded signatures, keys and
+// hashed messages as uint16_t[count_g][N_g], both decoders' statuses, the verification kernel's status words and norms.  Then what is in
+// statement order: the nonces, count x 40 bytes, and one piece of 16 bytes for the number of refused statements (the one value the
+// prover's host side reads).  Every piece is rounded up to 16 bytes.
+struct AggregateScreenBufs {
+    uint16_t *sig[2], *pk[2], *hm[2];
+    int32_t *sig_status[2], *pk_status[2], *status[2];
+    uint64_t *norm[2];
+    uint8_t *nonce;
+    uint32_t *refused;
+    size_t bytes;
+};
+inline AggregateScreenBufs aggregate_screen_layout(void *ws, size_t count9, size_t count10)
+{
+    AggregateScreenBufs b{};
+    Carve c(ws);
+    const size_t count[2] = {count9, count10};
+    for (int g = 0; g < 2; g++) {
+        const size_t row = count[g] * ((size_t)512 << g) * 2;
+        b.sig[g] = c.take<uint16_t>(row, 16);
+        b.pk[g] = c.take<uint16_t>(row, 16);
+        b.hm[g] = c.take<uint16_t>(row, 16);
+        b.sig_status[g] = c.take<int32_t>(count[g] * 4, 16);
+        b.pk_status[g] = c.take<int32_t>(count[g] * 4, 16);
+        b.status[g] = c.take<int32_t>(count[g] * 4, 16);
+        b.norm[g] = c.take<uint64_t>(count[g] * 8, 16);
+    }
+    b.nonce = c.take<uint8_t>((count9 + count10) * 40, 16);
+    b.refused = c.take<uint32_t>(16, 16);
+    b.bytes = c.off;
+    return b;
+}
+// ---- the aggregate prover from bytes (frw_aggregate_prove_from_bytes_dev): the screen's layout above; then from a 256-byte boundary,
+// per parameter set, the witness kernel's batch (count_g x W_g elements; W = 153 N + 50 | 52), its instance batch (count_g x (2 N + 1))
+// and its status words; the aggregate's own witness and instance vectors (sum of W_g count_g; 1 + sum of 2 N_g count_g elements), the
+// proof's 48 limbs, 384 wire bytes (the longer mode's), the encoder's status word, the prover's count of violated rows, the status words
+// of the statement kernels (statement order; the caller's array holds the screen's); and, 256-byte
+// aligned, the Groth16 prover's workspace for the one proof (groth16_bytes = frw_groth16_workspace_bytes(pk, aggregate, 1)).
+struct AggregateProveBufs {
+    AggregateScreenBufs screen;
+    uint64_t *set_witness[2], *set_instance[2];
+    int32_t *witness_status[2];
+    uint64_t *witness, *instance, *proof;
+    uint8_t *wire;
+    int32_t *wire_status, *statement_status;
+    uint32_t *unsatisfied;
+    void *groth16_ws;
+    size_t num_witness, num_instance;      // of the aggregate
+    size_t groth16_bytes, bytes;
+};
+inline AggregateProveBufs aggregate_prove_layout(void *ws, size_t count9, size_t count10, size_t groth16_bytes)
+{
+    AggregateProveBufs b{};
+    Carve c(ws);
+    const size_t count[2] = {count9, count10};
+    b.screen = aggregate_screen_layout(c.at(), count9, count10);
+    c.take(b.screen.bytes, 256);
+    b.num_instance = 1;
+    for (int g = 0; g < 2; g++) {
+        const size_t n = (size_t)512 << g, W = 153 * n + (g ? 52 : 50), I = 2 * n + 1;
+        c.align_to(256);
+        b.set_witness[g] = c.take<uint64_t>(count[g] * W * 32, 256);
+        b.set_instance[g] = c.take<uint64_t>(count[g] * I * 32, 16);
+        b.witness_status[g] = c.take<int32_t>(count[g] * 4, 16);
+        b.num_witness += count[g] * W;
+        b.num_instance += count[g] * (I - 1);
+    }
+    c.align_to(256);
+    b.witness = c.take<uint64_t>(b.num_witness * 32, 256);
+    b.instance = c.take<uint64_t>(b.num_instance * 32, 16);
+    b.proof = c.take<uint64_t>(384, 16);
+    b.wire = c.take<uint8_t>(POK_WIRE_STAGE, 16);
+    b.wire_status = c.take<int32_t>(4, 16);
+    b.unsatisfied = c.take<uint32_t>(4, 16);
+    b.statement_status = c.take<int32_t>((count9 + count10) * 4, 16);
+    c.align_to(256);
+    b.groth16_ws = c.take(groth16_bytes, 256);
+    b.groth16_bytes = groth16_bytes;
+    b.bytes = c.off;
+    return b;
+}
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
 {

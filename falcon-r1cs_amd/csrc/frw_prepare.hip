@@ -13,25 +13,21 @@
 #include <algorithm>
 #include "frw_device.h"
 #include "frw_keccak.h"
+#include "frw_layout.h"
 
 namespace frw {
 
 constexpr int SHAKE256_RATE = 136;
 constexpr int NONCE_LEN = 40;
 
-// hm = HashToPoint(nonce || msg): SHAKE256, big-endian 16-bit words, accept w < 5q as w mod q (Falcon spec Alg. 3)
-__global__ __launch_bounds__(BLOCK) void hash_to_point_kernel(int logn, size_t batch, const uint8_t *__restrict__ nonces,
-                                                              const uint8_t *__restrict__ msgs,
-                                                              const uint64_t *__restrict__ msg_off, uint16_t *__restrict__ hm)
+// hm = HashToPoint(nonce || msg): SHAKE256, big-endian 16-bit words, accept w < 5q as w mod q (Falcon spec Alg. 3).  One signature: its
+// 40-byte nonce, its message msgs[o0 .. o1) and its row of N coefficients, wherever the caller keeps them.
+__device__ __forceinline__ void hash_to_point_one(int logn, const uint8_t *__restrict__ nonce, const uint8_t *__restrict__ msg, uint64_t o0,
+                                         uint64_t o1, uint16_t *__restrict__ out)
 {
-    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= batch) return;
     const int n = 1 << logn;
-    const uint8_t *nonce = nonces + s * NONCE_LEN;
-    const uint8_t *msg = msgs + msg_off[s];
     // the host entry point rejects decreasing offsets; a device-side caller that breaks the precondition of
     // include/frw.h gets an empty message here rather than a 2^64-byte absorb loop
-    const uint64_t o0 = msg_off[s], o1 = msg_off[s + 1];
     const size_t total = NONCE_LEN + (size_t)(o1 >= o0 ? o1 - o0 : 0);
     uint64_t st[25];
 #pragma unroll
@@ -58,7 +54,6 @@ __global__ __launch_bounds__(BLOCK) void hash_to_point_kernel(int logn, size_t b
         if (last) break;
     }
     // squeeze
-    uint16_t *out = hm + s * (size_t)n;
     int cnt = 0;
     while (cnt < n) {
 #pragma unroll
@@ -72,7 +67,26 @@ __global__ __launch_bounds__(BLOCK) void hash_to_point_kernel(int logn, size_t b
     }
 }
 
-// pk: header 0x00 + logn, then N x 14 bits, big-endian bit order
+__global__ __launch_bounds__(BLOCK) void hash_to_point_kernel(int logn, size_t batch, const uint8_t *__restrict__ nonces,
+                                                              const uint8_t *__restrict__ msgs,
+                                                              const uint64_t *__restrict__ msg_off, uint16_t *__restrict__ hm)
+{
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= batch) return;
+    const uint64_t o0 = msg_off[s], o1 = msg_off[s + 1];
+    hash_to_point_one(logn, nonces + s * NONCE_LEN, msgs + o0, o0, o1, hm + (s << logn));
+}
+
+// pk: header 0x00 + logn, then N x 14 bits, big-endian bit order.  Coefficient k of the key at p (any alignment)
+__device__ __forceinline__ uint32_t public_key_coeff(const uint8_t *__restrict__ p, int k)
+{
+    const int bit = 14 * k, off = bit & 7;
+    const uint8_t *q = p + 1 + (bit >> 3);
+    uint32_t acc = (uint32_t)q[0] << 16 | (uint32_t)q[1] << 8;
+    if (off + 14 > 16) acc |= q[2];
+    return (acc >> (24 - 14 - off)) & 0x3fffu;
+}
+
 __global__ __launch_bounds__(BLOCK) void decode_public_keys_kernel(int logn, size_t batch, const uint8_t *__restrict__ pk_bytes,
                                                                    uint16_t *__restrict__ pk, int32_t *__restrict__ status)
 {
@@ -83,28 +97,20 @@ __global__ __launch_bounds__(BLOCK) void decode_public_keys_kernel(int logn, siz
     const size_t s = idx >> logn;
     const int k = (int)(idx & (size_t)(n - 1));
     const uint8_t *p = pk_bytes + s * pk_len;
-    const int bit = 14 * k, off = bit & 7;
-    const uint8_t *q = p + 1 + (bit >> 3);
-    uint32_t acc = (uint32_t)q[0] << 16 | (uint32_t)q[1] << 8;
-    if (off + 14 > 16) acc |= q[2];
-    const uint32_t c = (acc >> (24 - 14 - off)) & 0x3fffu;
+    const uint32_t c = public_key_coeff(p, k);
     pk[idx] = (uint16_t)c;
     if (c >= Q || (k == 0 && p[0] != (uint8_t)logn)) atomicMax(&status[s], ST_DECODE);
 }
 
-// sig: header 0x30 + logn, 40-byte nonce, compressed coefficients, zero padding up to sig_len
-__global__ __launch_bounds__(BLOCK) void decode_signatures_kernel(int logn, size_t batch, const uint8_t *__restrict__ sig_bytes,
-                                                                  size_t sig_len, uint16_t *__restrict__ sig,
-                                                                  uint8_t *__restrict__ nonce_out, int32_t *__restrict__ status)
+// sig: header 0x30 + logn, 40-byte nonce, compressed coefficients, zero padding up to sig_len.  One signature at p (any alignment):
+// its N coefficients -> out, its nonce -> nonce_out (may be null; only where the header is the expected one); true: well formed
+__device__ __forceinline__ bool decode_signature_one(int logn, const uint8_t *__restrict__ p, size_t sig_len, uint16_t *__restrict__ out,
+                                            uint8_t *__restrict__ nonce_out)
 {
-    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= batch) return;
     const int n = 1 << logn;
-    const uint8_t *p = sig_bytes + s * sig_len;
-    uint16_t *out = sig + s * (size_t)n;
     bool ok = sig_len > 1 + NONCE_LEN && p[0] == (uint8_t)(0x30 + logn);
     if (ok && nonce_out)
-        for (int i = 0; i < NONCE_LEN; i++) nonce_out[s * NONCE_LEN + i] = p[1 + i];
+        for (int i = 0; i < NONCE_LEN; i++) nonce_out[i] = p[1 + i];
     const uint8_t *body = p + 1 + NONCE_LEN;
     const size_t body_len = ok ? sig_len - 1 - NONCE_LEN : 0;
     size_t v = 0;
@@ -133,7 +139,92 @@ __global__ __launch_bounds__(BLOCK) void decode_signatures_kernel(int logn, size
     if (ok && (acc & ((1u << acc_len) - 1u))) ok = false;          // unused bits of the last byte
     for (; ok && v < body_len; v++)
         if (body[v]) ok = false;                                    // padding
+    return ok;
+}
+
+__global__ __launch_bounds__(BLOCK) void decode_signatures_kernel(int logn, size_t batch, const uint8_t *__restrict__ sig_bytes,
+                                                                  size_t sig_len, uint16_t *__restrict__ sig,
+                                                                  uint8_t *__restrict__ nonce_out, int32_t *__restrict__ status)
+{
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= batch) return;
+    const bool ok = decode_signature_one(logn, sig_bytes + s * sig_len, sig_len, sig + (s << logn),
+                                         nonce_out ? nonce_out + s * NONCE_LEN : nullptr);
     status[s] = ok ? ST_OK : ST_DECODE;
+}
+
+// ---- the inputs of an aggregate (frw_aggregate_*_from_bytes_dev): the encoded keys and signatures of statements of BOTH parameter sets
+// laid end to end in statement order, read where they lie.  One launch per parameter set and stage: item k of set g is statement
+// stmt[k] (R1csAggSet::stmt), its bytes are where aggregate_route (frw_layout.h) says, its decoded row is row k of the set's dense
+// array, which is what the per-set kernels downstream take.  Nonces stay in statement order.  The bodies are the kernels' above.
+__global__ __launch_bounds__(BLOCK) void agg_hash_to_point_kernel(int logn, size_t count, const uint32_t *__restrict__ stmt,
+                                                                  const uint8_t *__restrict__ nonces, const uint8_t *__restrict__ msgs,
+                                                                  const uint64_t *__restrict__ msg_off, uint16_t *__restrict__ hm)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const size_t s = stmt[k];
+    const uint64_t o0 = msg_off[s], o1 = msg_off[s + 1];
+    hash_to_point_one(logn, nonces + aggregate_route(logn - 9, k, s).nonce_off, msgs + o0, o0, o1, hm + (k << logn));
+}
+
+__global__ __launch_bounds__(BLOCK) void agg_decode_public_keys_kernel(int logn, size_t count, const uint32_t *__restrict__ stmt,
+                                                                       const uint8_t *__restrict__ pk_bytes, uint16_t *__restrict__ pk,
+                                                                       int32_t *__restrict__ status)
+{
+    const int n = 1 << logn;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= count * (size_t)n) return;
+    const size_t k = idx >> logn;
+    const int j = (int)(idx & (size_t)(n - 1));
+    const uint8_t *p = pk_bytes + aggregate_route(logn - 9, k, stmt[k]).pk_off;
+    const uint32_t c = public_key_coeff(p, j);
+    pk[idx] = (uint16_t)c;                                   // row k of the set's dense array: idx = k N + j
+    if (c >= Q || (j == 0 && p[0] != (uint8_t)logn)) atomicMax(&status[k], ST_DECODE);
+}
+
+// the nonce is copied out whatever the header says: the verifier's statement is made from the 40 bytes after it, not from a verdict
+__global__ __launch_bounds__(BLOCK) void agg_decode_signatures_kernel(int logn, size_t count, const uint32_t *__restrict__ stmt,
+                                                                      const uint8_t *__restrict__ sig_bytes, uint16_t *__restrict__ sig,
+                                                                      uint8_t *__restrict__ nonces, int32_t *__restrict__ status)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const AggRoute r = aggregate_route(logn - 9, k, stmt[k]);
+    const uint8_t *p = sig_bytes + r.sig_off;
+    for (int i = 0; i < NONCE_LEN; i++) nonces[r.nonce_off + i] = p[1 + i];
+    status[k] = decode_signature_one(logn, p, aggregate_sig_len(logn - 9), sig + (k << logn), nullptr) ? ST_OK : ST_DECODE;
+}
+
+// the per-set screen's verdicts (and norms, where asked for) back into statement order: a lane per item of either set
+struct AggVerdicts { const uint32_t *stmt[2]; const int32_t *status[2]; const uint64_t *norm[2]; uint32_t count[2]; };
+__global__ __launch_bounds__(BLOCK) void agg_scatter_verdicts_kernel(AggVerdicts v, int32_t *__restrict__ status, uint64_t *__restrict__ norm)
+{
+    size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int g = 0;
+    if (k >= v.count[0]) { k -= v.count[0]; g = 1; }
+    if (k >= v.count[g]) return;
+    const size_t s = v.stmt[g][k];
+    status[s] = v.status[g][k];
+    if (norm) norm[s] = v.norm[g][k];
+}
+
+// ONE workgroup: refused[0] = the statements whose status is not FRW_ST_OK -- the one value the aggregate prover's host side reads
+__global__ __launch_bounds__(BLOCK) void agg_count_refused_kernel(size_t count, const int32_t *__restrict__ status, uint32_t *__restrict__ refused)
+{
+    __shared__ uint32_t wave_count[WAVES];
+    uint32_t mine = 0;
+    for (size_t s = threadIdx.x; s < count; s += BLOCK) mine += status[s] != ST_OK;
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) wave_count[threadIdx.x / WAVE] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) total += wave_count[w];
+        refused[0] = total;
+    }
 }
 
 // ---- compaction for the prover from bytes (frw_pok_prove_from_bytes_dev): the witness and prover calls take dense batches, the caller's
@@ -336,6 +427,47 @@ hipError_t launch_decode_signatures(int logn, size_t batch, const uint8_t *sig_b
     if (batch == 0) return hipSuccess;
     hipLaunchKernelGGL(decode_signatures_kernel, dim3((unsigned)((batch + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, logn, batch,
                        sig_bytes, sig_len, sig, nonce_out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_agg_hash_to_point(int logn, size_t count, const uint32_t *stmt, const uint8_t *nonces, const uint8_t *msgs,
+                                    const uint64_t *msg_off, uint16_t *hm, hipStream_t st)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(agg_hash_to_point_kernel, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, logn, count, stmt, nonces,
+                       msgs, msg_off, hm);
+    return hipGetLastError();
+}
+
+hipError_t launch_agg_decode_public_keys(int logn, size_t count, const uint32_t *stmt, const uint8_t *pk_bytes, uint16_t *pk, int32_t *status,
+                                         hipStream_t st)
+{
+    if (count == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(status, 0, count * sizeof(int32_t), st);
+    if (e != hipSuccess) return e;
+    const size_t total = count << logn;
+    hipLaunchKernelGGL(agg_decode_public_keys_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, logn, count, stmt,
+                       pk_bytes, pk, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_agg_decode_signatures(int logn, size_t count, const uint32_t *stmt, const uint8_t *sig_bytes, uint16_t *sig, uint8_t *nonces,
+                                        int32_t *status, hipStream_t st)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(agg_decode_signatures_kernel, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, logn, count, stmt,
+                       sig_bytes, sig, nonces, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_agg_verdicts(const uint32_t *const stmt[2], const int32_t *const set_status[2], const uint64_t *const set_norm[2],
+                               const size_t count[2], int32_t *status, uint64_t *norm, uint32_t *refused, hipStream_t st)
+{
+    const size_t total = count[0] + count[1];
+    if (total == 0) return hipSuccess;
+    const AggVerdicts v = {{stmt[0], stmt[1]}, {set_status[0], set_status[1]}, {set_norm[0], set_norm[1]}, {(uint32_t)count[0], (uint32_t)count[1]}};
+    hipLaunchKernelGGL(agg_scatter_verdicts_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, v, status, norm);
+    hipLaunchKernelGGL(agg_count_refused_kernel, dim3(1), dim3(BLOCK), 0, st, total, (const int32_t *)status, refused);
     return hipGetLastError();
 }
 

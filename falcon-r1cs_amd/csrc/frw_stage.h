@@ -1,7 +1,7 @@
 // frw_stage.h -- what the host-buffer entry points know before they touch the device: the three circuits' sizes, and how the encoded
-// inputs of the bytes paths (frw_prepare_inputs, frw_statement_from_bytes, frw_falcon_verify_from_bytes, frw_pok_prove_from_bytes) are
-// staged.  Host code only, nothing of the HIP runtime is called: tests/cpp/test_stage_host.cpp fills real memory by it under the
-// sanitizers.
+// inputs of the bytes paths (frw_prepare_inputs, frw_statement_from_bytes, frw_falcon_verify_from_bytes, frw_pok_prove_from_bytes; the
+// mixed-length ones of frw_aggregate_*_from_bytes) are staged.  Host code only, nothing of the HIP runtime is called:
+// tests/cpp/test_stage_host.cpp and tests/cpp/test_aggregate_bytes.cpp fill real memory by it under the sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -72,6 +72,48 @@ struct StagedInputs {
         if (rs) memcpy(h + o_rs, rs + lo * 8, cnt * 64);
     }
     // the pieces of a pass copied to `base`
+    const uint8_t *d_pk(const void *base) const { return (const uint8_t *)base + o_pk; }
+    const uint8_t *d_second(const void *base) const { return (const uint8_t *)base + o_second; }
+    const uint8_t *d_msgs(const void *base) const { return (const uint8_t *)base + o_msgs; }
+    const uint64_t *d_off(const void *base) const { return (const uint64_t *)((const char *)base + o_off); }
+    const uint64_t *d_rs(const void *base) const { return (const uint64_t *)((const char *)base + o_rs); }
+};
+
+// The encoded inputs of ONE aggregate (frw_aggregate_*_from_bytes): the same pieces, but the statements' keys and signatures are of two
+// lengths, mixed, in statement order -- the layout the device entry points read in place, so the pieces are the caller's arrays whole
+// (aggregate_pk_bytes / aggregate_sig_bytes of frw_layout.h say how long), and an aggregate is one pass: it is not divisible.  `nonces`:
+// the second piece is the statements' nonces (40 bytes each), not their signatures.  rs: the proof's r and s, 64 bytes, or NULL.
+struct StagedAggregate {
+    const uint8_t *pk_bytes, *second, *msgs;
+    const uint64_t *msg_off, *rs;
+    size_t count, pk_total, second_total, msg_total;
+    size_t o_pk, o_second, o_msgs, o_off, o_rs, bytes;
+
+    StagedAggregate(size_t count9, size_t count10, bool nonces, const uint8_t *pk_bytes_, const uint8_t *second_, const uint8_t *msgs_,
+                    const uint64_t *msg_off_, const uint64_t *rs_ = nullptr)
+        : pk_bytes(pk_bytes_), second(second_), msgs(msgs_), msg_off(msg_off_), rs(rs_), count(count9 + count10),
+          pk_total(aggregate_pk_bytes(count9, count10)),
+          second_total(nonces ? (count9 + count10) * FRW_NONCE_LEN : aggregate_sig_bytes(count9, count10)),
+          msg_total((size_t)(msg_off_[count9 + count10] - msg_off_[0]))
+    {
+        Carve c(nullptr);
+        o_pk = c.off;     c.take(pk_total);
+        o_second = c.off; c.take(second_total);
+        o_msgs = c.off;   c.take(msg_total ? msg_total : 1);
+        o_off = c.off;    c.take((count + 1) * sizeof(uint64_t));
+        o_rs = c.off;     if (rs) c.take(64);
+        bytes = c.off;
+    }
+    void fill(void *stage) const
+    {
+        char *h = (char *)stage;
+        memcpy(h + o_pk, pk_bytes, pk_total);
+        memcpy(h + o_second, second, second_total);
+        if (msg_total) memcpy(h + o_msgs, msgs + msg_off[0], msg_total);
+        uint64_t *off = (uint64_t *)(h + o_off);
+        for (size_t i = 0; i <= count; i++) off[i] = msg_off[i] - msg_off[0];
+        if (rs) memcpy(h + o_rs, rs, 64);
+    }
     const uint8_t *d_pk(const void *base) const { return (const uint8_t *)base + o_pk; }
     const uint8_t *d_second(const void *base) const { return (const uint8_t *)base + o_second; }
     const uint8_t *d_msgs(const void *base) const { return (const uint8_t *)base + o_msgs; }

@@ -288,6 +288,23 @@ class Groth16Verifier:
         verdicts = self.verify_wire_dev(d_inst, d_wire, compressed, ENC_MONTGOMERY, flags, batched, seed, stream)
         return d_status, verdicts
 
+    def verify_aggregate_wire_dev(self, engine, handle, pk_bytes, nonces, msgs, wire, compressed=True, flags=0, stream=0):
+        """verify_statements_wire_dev for ONE aggregate proof: the statements' Falcon public keys, nonces and messages in statement
+        order and the proof's wire bytes, nothing else.  The aggregate's instance vector is made on the device by `engine`
+        (aggregate_statement_from_bytes_dev on `handle`, the constraint system this key was set up for) and goes to verify_wire_dev as
+        it is.  Returns (statuses int32[count], verdict int32[1]) device tensors: a refused statement leaves zeros in its slots, an
+        instance vector that is well formed and verifies against no proof."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(wire, torch.Tensor):
+            d_wire = wire.to(dev).contiguous().view(torch.uint8).reshape(-1)
+        else:
+            raw = wire if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire, dtype=np.uint8).tobytes()
+            d_wire = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+        d_inst, d_status = engine.aggregate_statement_from_bytes_dev(handle, pk_bytes, nonces, msgs, ENC_MONTGOMERY, stream)
+        verdict = self.verify_wire_dev(d_inst.reshape(1, -1, 4), d_wire, compressed, ENC_MONTGOMERY, flags, False, None, stream)
+        return d_status, verdict
+
     def rerandomize(self, proofs, factors, flags=0):
         """ark-groth16's rerandomize_proof on the host (frw_groth16_rerandomize): A' = A / r1, B' = r1 B + r1 r2 delta_g2,
         C' = C + r2 A.  proofs: uint64[batch, 48]; factors: uint64[batch, 2, 4], r1 and r2 of every proof, any 256-bit values (taken
@@ -1008,6 +1025,161 @@ class WitnessEngine:
                                                      P(out["instance"]), P(out["status"]), P(out["num_unsatisfied"]), self._ptr(workspace),
                                                      workspace.numel(), C.c_void_p(stream)), "frw_pok_prove_from_bytes_dev")
         return {k: (v[:batch] if v is not None else None) for k, v in out.items()}
+
+    # ---- an aggregate from bytes: triples of mixed parameter sets in statement order -> verdicts, the statement, ONE proof ------------
+    @staticmethod
+    def _aggregate_bytes(triples, nonces=None):
+        """[(pk_bytes, msg, sig_bytes)] in statement order (with `nonces`: [(pk_bytes, msg)] and the 40-byte nonces) -> the keys end to
+        end, the signatures (or nonces) end to end, the message blob and its offsets.  The lengths say which parameter set a statement
+        is of; the handle says which it must be, and the library reads the bytes by the handle."""
+        keys = [bytes(t[0]) for t in triples]
+        msgs = [bytes(t[1]) for t in triples]
+        second = [bytes(x) for x in nonces] if nonces is not None else [bytes(t[2]) for t in triples]
+        if len(second) != len(keys):
+            raise ValueError("one nonce per statement")
+        for i, k in enumerate(keys):
+            logn = {PK_LEN[9]: 9, PK_LEN[10]: 10}.get(len(k))
+            if logn is None or len(second[i]) != (NONCE_LEN if nonces is not None else SIG_LEN[logn]):
+                raise ValueError("statement %d: a key of %d or %d bytes and a signature of %d or %d (a nonce of %d)"
+                                 % (i, PK_LEN[9], PK_LEN[10], SIG_LEN[9], SIG_LEN[10], NONCE_LEN))
+        pkb = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
+        sec = np.frombuffer(b"".join(second) or b"\0", dtype=np.uint8)
+        blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(keys) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        return len(keys), pkb, sec, blob, off
+
+    def _aggregate_count(self, handle, count, where):
+        info = self.r1cs_info(handle)
+        if int(info.num_statements) != count:
+            raise FrwError(-1, where, "%d statements given, the aggregate has %d" % (count, int(info.num_statements)))
+        return info
+
+    def _aggregate_upload(self, arrays):
+        import torch
+        dev = torch.device("cuda", self.device)
+        return [torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a).copy()).to(dev) for a in arrays]
+
+    def aggregate_screen_workspace_bytes(self, handle):
+        return int(self._lib.frw_aggregate_screen_workspace_bytes(handle))
+
+    def aggregate_falcon_verify_from_bytes(self, handle, triples, rule=RULE_CIRCUIT, want_norm=True):
+        """Host buffers (frw_aggregate_falcon_verify_from_bytes): [(pk_bytes, msg, sig_bytes)] in statement order -> (status i32[count],
+        norm u64[count] or None), statement by statement what falcon_verify_from_bytes gives."""
+        count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
+        self._aggregate_count(handle, count, "frw_aggregate_falcon_verify_from_bytes")
+        st = np.zeros(count, dtype=np.int32)
+        norm = np.zeros(count, dtype=np.uint64) if want_norm else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._lib.frw_aggregate_falcon_verify_from_bytes(handle, self._ctx, p(pkb), p(sgb), p(blob), p(off), int(rule), p(st),
+                                                               p(norm) if want_norm else None), "frw_aggregate_falcon_verify_from_bytes")
+        return st, norm
+
+    def aggregate_falcon_verify_from_bytes_dev(self, handle, triples, rule=RULE_CIRCUIT, stream=0, workspace=None):
+        """The same on the device (frw_aggregate_falcon_verify_from_bytes_dev) -> (status int32[count], norm int64[count]) device
+        tensors, not synchronised.  Capture-safe once the inputs are on the device."""
+        import torch
+        count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
+        self._aggregate_count(handle, count, "frw_aggregate_falcon_verify_from_bytes_dev")
+        d_pkb, d_sgb, d_blob, d_off = self._aggregate_upload((pkb, sgb, blob, off))
+        dev = d_pkb.device
+        d_status = torch.empty(count, dtype=torch.int32, device=dev)
+        d_norm = torch.empty(count, dtype=torch.int64, device=dev)
+        if workspace is None:
+            workspace = torch.empty(max(self.aggregate_screen_workspace_bytes(handle), 16), dtype=torch.uint8, device=dev)
+        check(self._lib.frw_aggregate_falcon_verify_from_bytes_dev(handle, self._ctx, self._ptr(d_pkb), self._ptr(d_sgb), self._ptr(d_blob),
+                                                                   self._ptr(d_off), int(rule), self._ptr(d_status), self._ptr(d_norm),
+                                                                   self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
+              "frw_aggregate_falcon_verify_from_bytes_dev")
+        return d_status, d_norm
+
+    def aggregate_statement_from_bytes(self, handle, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY):
+        """Host buffers (frw_aggregate_statement_from_bytes): the verifier's side -- keys, 40-byte nonces and messages in statement
+        order -> (instance u64[I, 4], status i32[count])."""
+        count, pkb, non, blob, off = self._aggregate_bytes(list(zip(pk_bytes, msgs)), nonces)
+        info = self._aggregate_count(handle, count, "frw_aggregate_statement_from_bytes")
+        inst = np.zeros((int(info.num_instance), 4), dtype=np.uint64)
+        st = np.zeros(count, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._lib.frw_aggregate_statement_from_bytes(handle, self._ctx, p(pkb), p(non), p(blob), p(off), int(encoding), p(inst), p(st)),
+              "frw_aggregate_statement_from_bytes")
+        return inst, st
+
+    def aggregate_statement_from_bytes_dev(self, handle, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
+        """The same on the device (frw_aggregate_statement_from_bytes_dev) -> (instance int64[I, 4], status int32[count]) device
+        tensors, not synchronised."""
+        import torch
+        count, pkb, non, blob, off = self._aggregate_bytes(list(zip(pk_bytes, msgs)), nonces)
+        info = self._aggregate_count(handle, count, "frw_aggregate_statement_from_bytes_dev")
+        d_pkb, d_non, d_blob, d_off = self._aggregate_upload((pkb, non, blob, off))
+        dev = d_pkb.device
+        d_inst = torch.empty((int(info.num_instance), 4), dtype=torch.int64, device=dev)
+        d_status = torch.empty(count, dtype=torch.int32, device=dev)
+        if workspace is None:
+            workspace = torch.empty(max(self.aggregate_screen_workspace_bytes(handle), 16), dtype=torch.uint8, device=dev)
+        check(self._lib.frw_aggregate_statement_from_bytes_dev(handle, self._ctx, self._ptr(d_pkb), self._ptr(d_non), self._ptr(d_blob),
+                                                               self._ptr(d_off), int(encoding), self._ptr(d_inst), self._ptr(d_status),
+                                                               self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
+              "frw_aggregate_statement_from_bytes_dev")
+        return d_inst, d_status
+
+    def aggregate_prove_workspace_bytes(self, pk, handle):
+        """Bytes of frw_aggregate_prove_from_bytes_dev's workspace (0: not an aggregate, or a key that is not this handle's)."""
+        return int(self._lib.frw_aggregate_prove_workspace_bytes(pk, handle))
+
+    def aggregate_prove_from_bytes(self, pk, handle, triples, rs, compressed=True, strict=True):
+        """Host buffers (frw_aggregate_prove_from_bytes): [(pk_bytes, msg, sig_bytes)] in statement order, rs uint64[2, 4] -> dict(rc,
+        wire uint8[192 | 384], proof uint64[48], instance uint64[I, 4], nonces uint8[count, 40], status int32[count],
+        num_unsatisfied).  A refused statement means NO proof: rc = E_RANGE, wire and proof all zero, num_unsatisfied all ones, status
+        says which statement; with strict that is raised as FrwError."""
+        count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
+        info = self._aggregate_count(handle, count, "frw_aggregate_prove_from_bytes")
+        rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(2, 4)
+        out = {"wire": np.zeros(proof_wire_bytes(compressed), dtype=np.uint8), "proof": np.zeros(48, dtype=np.uint64),
+               "instance": np.zeros((int(info.num_instance), 4), dtype=np.uint64), "nonces": np.zeros((count, NONCE_LEN), dtype=np.uint8),
+               "status": np.zeros(count, dtype=np.int32), "num_unsatisfied": np.zeros(1, dtype=np.uint32)}
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self._lib.frw_aggregate_prove_from_bytes(self._ctx, pk, handle, p(pkb), p(sgb), p(blob), p(off), p(rs),
+                                                      WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, p(out["wire"]), p(out["proof"]),
+                                                      p(out["instance"]), p(out["nonces"]), p(out["status"]), p(out["num_unsatisfied"]))
+        return self._aggregate_verdict(rc, out, out["status"], strict, "frw_aggregate_prove_from_bytes")
+
+    @staticmethod
+    def _aggregate_verdict(rc, out, status, strict, where):
+        if rc == E_RANGE and strict:
+            st = np.asarray(status.tolist())
+            bad = np.nonzero(st)[0]
+            raise FrwError(rc, where, "no proof: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+        if rc != E_RANGE:
+            check(rc, where)
+        out["rc"] = rc
+        return out
+
+    def aggregate_prove_from_bytes_dev(self, pk, handle, triples, rs, compressed=True, strict=True, workspace=None, stream=0):
+        """The same on the device (frw_aggregate_prove_from_bytes_dev) -> dict of device tensors (wire uint8, proof int64[48], instance
+        int64[I, 4], nonces uint8[count, 40], status int32[count], num_unsatisfied int32[1]) and rc.  rs: uint64[2, 4] on the host or an
+        int64 device tensor.  The call waits on `stream` once, for the number of refused statements."""
+        import torch
+        count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
+        info = self._aggregate_count(handle, count, "frw_aggregate_prove_from_bytes_dev")
+        d_pkb, d_sgb, d_blob, d_off = self._aggregate_upload((pkb, sgb, blob, off))
+        dev = d_pkb.device
+        d_rs = rs if isinstance(rs, torch.Tensor) else self._aggregate_upload((np.ascontiguousarray(rs, dtype=np.uint64).reshape(8),))[0]
+        out = {"wire": torch.empty(proof_wire_bytes(compressed), dtype=torch.uint8, device=dev),
+               "proof": torch.empty(48, dtype=torch.int64, device=dev),
+               "instance": torch.empty((int(info.num_instance), 4), dtype=torch.int64, device=dev),
+               "nonces": torch.empty((count, NONCE_LEN), dtype=torch.uint8, device=dev),
+               "status": torch.empty(count, dtype=torch.int32, device=dev),
+               "num_unsatisfied": torch.empty(1, dtype=torch.int32, device=dev)}
+        if workspace is None:
+            workspace = torch.empty(max(self.aggregate_prove_workspace_bytes(pk, handle), 256), dtype=torch.uint8, device=dev)
+        rc = self._lib.frw_aggregate_prove_from_bytes_dev(self._ctx, pk, handle, self._ptr(d_pkb), self._ptr(d_sgb), self._ptr(d_blob),
+                                                          self._ptr(d_off), self._ptr(d_rs),
+                                                          WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, self._ptr(out["wire"]),
+                                                          self._ptr(out["proof"]), self._ptr(out["instance"]), self._ptr(out["nonces"]),
+                                                          self._ptr(out["status"]), self._ptr(out["num_unsatisfied"]), self._ptr(workspace),
+                                                          workspace.numel(), C.c_void_p(stream))
+        return self._aggregate_verdict(rc, out, out["status"], strict, "frw_aggregate_prove_from_bytes_dev")
 
     def groth16_setup_r1cs(self, handle, alpha, beta, gamma, delta, t, mode=KEY_AUTO, rank=0, world=1, want_vk=True):
         """groth16_setup for the system behind an r1cs handle (a per-signature circuit or an aggregate statement).

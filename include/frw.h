@@ -362,6 +362,8 @@ int frw_r1cs_diag_host_allocations(const frw_r1cs *r, uint64_t *count);
  * Falcon-1024 batch count_logn10 (frw_r1cs_info), both written with the SAME encoding (the aggregate's constant one is copied from the
  * first statement's own instance vector) and none of them rejected (FRW_ST_COEFF_RANGE zero-fills a slot: its leading one too).
  * Device-to-device copies on `stream` only -- two per run of consecutive statements of one parameter set --, capture-safe.
+ * THE CHECKED WAY IN is frw_aggregate_prove_from_bytes_dev (below): it screens every statement first and calls this only when all
+ * were accepted, so the three preconditions hold by construction; a chain assembled by hand must keep them itself.
  * frw_groth16_setup_r1cs is frw_groth16_setup for the system behind any handle; the proving key of an aggregate has one query
  * point per variable of the whole statement.  As window tables that is 3.6 KB of G1 tables x 3 and 7.2 KB of G2 per variable and
  * 1.8 KB per domain point of h_query: 53 GB for sixteen Falcon-1024 statements -- the fastest proofs, up to there.  Beyond, the key
@@ -1016,6 +1018,77 @@ int frw_pok_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r
                              const uint8_t *pk_bytes, const uint8_t *sig_bytes, size_t sig_len, const uint8_t *msgs,
                              const uint64_t *msg_off, const uint64_t *rs, int wire_mode, uint8_t *wire, uint64_t *proofs,
                              uint64_t *instance, int32_t *status, uint32_t *num_unsatisfied, int strict);
+
+/* ---- an aggregate from bytes: encoded Falcon signatures of mixed parameter sets in, verdicts, the verifier's statement, ONE proof out ----
+ * Both halves of examples/pok_sig.rs:21-47 for an aggregate handle (frw_r1cs_load_aggregate; its statements are FRW_CIRCUIT_NTT's),
+ * from what a caller holds: a list of (pk, msg, sig) in STATEMENT order, Falcon-512 and Falcon-1024 mixed, not two sorted piles.
+ *     d_pk_bytes      the encoded keys laid end to end in statement order: statement i takes FRW_PK_LEN(logn[i]) bytes (897 | 1,793), so
+ *                     no key but the first is aligned to anything; nothing is assumed of the alignment of any input byte
+ *     d_sig_bytes     likewise, FRW_SIG_LEN(logn[i]) bytes each (666 | 1,280)
+ *     d_nonces        (the statement call, in place of the signatures) count x FRW_NONCE_LEN bytes, statement order
+ *     d_msgs, d_msg_off   one blob and count + 1 non-decreasing offsets in statement order, as for frw_hash_to_point_dev
+ * The device code reads every statement's bytes where they lie (csrc/frw_layout.h aggregate_route: k statements of its own set and s - k
+ * of the other lie before the k-th statement of a set, statement s) and writes the decoded rows into its parameter set's dense arrays,
+ * which the per-set kernels take: one launch per parameter set and stage.
+ * frw_aggregate_falcon_verify_from_bytes_dev -- the screen: d_status[i] (int32_t[count]) and d_norm[i] (uint64_t[count], may be NULL) are
+ *     word for word what frw_falcon_verify_from_bytes_dev writes for statement i alone under `rule`; FRW_ST_DECODE beats
+ *     FRW_ST_COEFF_RANGE beats FRW_ST_NORM_BOUND.  d_workspace: frw_aggregate_screen_workspace_bytes(aggregate) bytes, 16-byte aligned
+ *     (csrc/frw_layout.h aggregate_screen_layout).  Stream-ordered, allocates nothing, no host wait: capture-safe.
+ * frw_aggregate_statement_from_bytes_dev -- the verifier's half: d_instance (uint64_t[I][4]) holds the bytes frw_aggregate_statement_dev
+ *     writes for the decoded keys and the hashed messages of the same inputs, [1, NTT(pk_0), NTT(hm_0), ...].  The constant one is
+ *     always written; a refused statement's 2 N slots are zero; d_status (int32_t[count]) is in statement order: FRW_ST_OK, FRW_ST_DECODE
+ *     (a malformed key).  The same workspace size and alignment as the screen's.  Capture-safe.
+ * frw_aggregate_prove_from_bytes_dev -- the prover's half as ONE call, on `stream`:
+ *   1. the routed decoders and SHAKE256, then the screen under FRW_RULE_CIRCUIT: d_status is the screen's;
+ *   2. d_instance (may be NULL; FRW_ENC_MONTGOMERY) and d_nonces_out (may be NULL; count x 40: bytes 1 .. 40 of every signature) are
+ *      written: d_instance is exactly what frw_aggregate_statement_from_bytes_dev writes for these keys, nonces and messages -- the
+ *      verifier's statement, which does not depend on the signatures;
+ *   3. THE ONE HOST WAIT: the number of refused statements is copied to the host and `stream` is synchronised, so the call is NOT
+ *      stream-capture safe, like frw_pok_prove_from_bytes_dev;
+ *   4. if any statement is refused: d_wire (all bytes of the chosen mode) and d_proof are zero-filled, d_num_unsatisfied is all ones, no
+ *      witness or prover kernel is launched, and the call returns FRW_E_RANGE -- an aggregate with a statement that cannot be proven has
+ *      no proof; d_status says which one;
+ *   5. else each parameter set's witness kernel (FRW_ENC_MONTGOMERY), frw_aggregate_assign_dev's copies into the workspace,
+ *      frw_groth16_prove_rs_dev on the aggregate handle and the wire encoder; d_num_unsatisfied is the prover's count; FRW_OK.  Every
+ *      statement was accepted, so the preconditions of frw_aggregate_assign_dev hold by construction.
+ *     d_rs            uint64_t[2][4], as for frw_groth16_prove_rs_dev        d_wire   frw_groth16_proof_wire_bytes(wire_mode) bytes
+ *     d_proof         (may be NULL) uint64_t[48]                              d_num_unsatisfied  (may be NULL) uint32_t[1]
+ *     d_workspace     frw_aggregate_prove_workspace_bytes(pk, aggregate) bytes, 256-byte aligned (csrc/frw_layout.h aggregate_prove_layout:
+ *                     the screen's pieces, the per-set witness and instance batches, the aggregate's vectors, limbs, wire bytes, status
+ *                     words and frw_groth16_workspace_bytes(pk, aggregate, 1))
+ * The proof's bytes depend only on the statements' inputs and d_rs, and are byte for byte what the chain of frw_prepare_inputs,
+ * frw_witness_ntt_verify_dev, frw_aggregate_assign_dev, frw_groth16_prove_rs_dev and frw_groth16_proofs_to_wire_dev gives.  Nothing is
+ * written beyond the stated sizes; nothing is left as stale memory.  Allocates nothing.
+ * FRW_E_INVALID_ARG before any device work: a null pointer other than the ones marked, a handle that is not an aggregate, an unknown
+ * rule, encoding (FRW_ENC_COMPACT too) or wire mode, a misaligned or small workspace, ctx, key and handle on different devices; a key
+ * in slices (world > 1) or whose instance and witness counts are not the handle's.  The size functions return 0 for the same.
+ * What the call CANNOT check: a key made for the same multiset of statements in another order has the same counts.  Pairing the key
+ * with the handle it was set up from is the caller's responsibility (the proof of a mismatched pair verifies against nothing).
+ * The host-buffer forms (no _dev) take the same arguments as host pointers and no workspace; an aggregate is not divisible, so each is
+ * ONE pass through the context's arena (FRW_E_OUT_OF_MEMORY if the arena cannot hold the statement); decreasing message offsets ->
+ * FRW_E_INVALID_ARG.  frw_aggregate_prove_from_bytes returns FRW_E_RANGE as the device form does, with every output complete. */
+size_t frw_aggregate_screen_workspace_bytes(const frw_r1cs *aggregate);
+int frw_aggregate_falcon_verify_from_bytes_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *d_pk_bytes,
+                                               const uint8_t *d_sig_bytes, const uint8_t *d_msgs, const uint64_t *d_msg_off, int rule,
+                                               int32_t *d_status, uint64_t *d_norm, void *d_workspace, size_t workspace_bytes,
+                                               void *stream);
+int frw_aggregate_statement_from_bytes_dev(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *d_pk_bytes, const uint8_t *d_nonces,
+                                           const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding, uint64_t *d_instance,
+                                           int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+size_t frw_aggregate_prove_workspace_bytes(const frw_groth16_pk *pk, const frw_r1cs *aggregate);
+int frw_aggregate_prove_from_bytes_dev(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *aggregate, const uint8_t *d_pk_bytes,
+                                       const uint8_t *d_sig_bytes, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint64_t *d_rs,
+                                       int wire_mode, uint8_t *d_wire, uint64_t *d_proof, uint64_t *d_instance, uint8_t *d_nonces_out,
+                                       int32_t *d_status, uint32_t *d_num_unsatisfied, void *d_workspace, size_t workspace_bytes,
+                                       void *stream);
+int frw_aggregate_falcon_verify_from_bytes(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *pk_bytes, const uint8_t *sig_bytes,
+                                           const uint8_t *msgs, const uint64_t *msg_off, int rule, int32_t *status, uint64_t *norm);
+int frw_aggregate_statement_from_bytes(const frw_r1cs *aggregate, frw_ctx *ctx, const uint8_t *pk_bytes, const uint8_t *nonces,
+                                       const uint8_t *msgs, const uint64_t *msg_off, int encoding, uint64_t *instance, int32_t *status);
+int frw_aggregate_prove_from_bytes(frw_ctx *ctx, const frw_groth16_pk *pk, const frw_r1cs *aggregate, const uint8_t *pk_bytes,
+                                   const uint8_t *sig_bytes, const uint8_t *msgs, const uint64_t *msg_off, const uint64_t *rs,
+                                   int wire_mode, uint8_t *wire, uint64_t *proof, uint64_t *instance, uint8_t *nonces_out,
+                                   int32_t *status, uint32_t *num_unsatisfied);
 
 /* ---- stand-alone gadget blocks ---------------------------------------------------------------
  * The reference's gadget functions are also called outside the full circuit (its unit tests do; so can any

@@ -411,6 +411,32 @@ extern "C" {
                                     batch: usize, pk_bytes: *const u8, sig_bytes: *const u8, sig_len: usize, msgs: *const u8,
                                     msg_off: *const u64, rs: *const u64, wire_mode: c_int, wire: *mut u8, proofs: *mut u64,
                                     instance: *mut u64, status: *mut i32, num_unsatisfied: *mut u32, strict: c_int) -> c_int;
+    pub fn frw_aggregate_screen_workspace_bytes(aggregate: *const frw_r1cs) -> usize;
+    pub fn frw_aggregate_falcon_verify_from_bytes_dev(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, d_pk_bytes: *const u8,
+                                                      d_sig_bytes: *const u8, d_msgs: *const u8, d_msg_off: *const u64, rule: c_int,
+                                                      d_status: *mut i32, d_norm: *mut u64, d_workspace: *mut c_void,
+                                                      workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_aggregate_statement_from_bytes_dev(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, d_pk_bytes: *const u8,
+                                                  d_nonces: *const u8, d_msgs: *const u8, d_msg_off: *const u64, encoding: c_int,
+                                                  d_instance: *mut u64, d_status: *mut i32, d_workspace: *mut c_void,
+                                                  workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_aggregate_prove_workspace_bytes(pk: *const frw_groth16_pk, aggregate: *const frw_r1cs) -> usize;
+    pub fn frw_aggregate_prove_from_bytes_dev(ctx: *mut frw_ctx, pk: *const frw_groth16_pk, aggregate: *const frw_r1cs,
+                                              d_pk_bytes: *const u8, d_sig_bytes: *const u8, d_msgs: *const u8, d_msg_off: *const u64,
+                                              d_rs: *const u64, wire_mode: c_int, d_wire: *mut u8, d_proof: *mut u64,
+                                              d_instance: *mut u64, d_nonces_out: *mut u8, d_status: *mut i32,
+                                              d_num_unsatisfied: *mut u32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                              stream: *mut c_void) -> c_int;
+    pub fn frw_aggregate_falcon_verify_from_bytes(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, pk_bytes: *const u8,
+                                                  sig_bytes: *const u8, msgs: *const u8, msg_off: *const u64, rule: c_int,
+                                                  status: *mut i32, norm: *mut u64) -> c_int;
+    pub fn frw_aggregate_statement_from_bytes(aggregate: *const frw_r1cs, ctx: *mut frw_ctx, pk_bytes: *const u8, nonces: *const u8,
+                                              msgs: *const u8, msg_off: *const u64, encoding: c_int, instance: *mut u64,
+                                              status: *mut i32) -> c_int;
+    pub fn frw_aggregate_prove_from_bytes(ctx: *mut frw_ctx, pk: *const frw_groth16_pk, aggregate: *const frw_r1cs, pk_bytes: *const u8,
+                                          sig_bytes: *const u8, msgs: *const u8, msg_off: *const u64, rs: *const u64, wire_mode: c_int,
+                                          wire: *mut u8, proof: *mut u64, instance: *mut u64, nonces_out: *mut u8, status: *mut i32,
+                                          num_unsatisfied: *mut u32) -> c_int;
     pub fn frw_gadget_block_len(kind: c_int) -> c_int;
     pub fn frw_gadget_dev(ctx: *mut frw_ctx, kind: c_int, count: usize, d_a: *const c_void, d_b: *const u64,
                           encoding: c_int, d_out: *mut u64, d_status: *mut i32, stream: *mut c_void) -> c_int;

@@ -47,6 +47,10 @@ class CompactLayoutStruct(C.Structure):
                 ("num_instance_values", C.c_uint64), ("status_off", C.c_uint64)]
 
 
+class FieldInfoStruct(C.Structure):
+    _fields_ = [("modulus", C.c_uint64 * 4), ("one", C.c_uint64 * 4), ("r2", C.c_uint64 * 4), ("ninv32", C.c_uint32), ("bits", C.c_uint32)]
+
+
 class MsmInfoStruct(C.Structure):
     _fields_ = [("num_points", C.c_uint64), ("window_bits", C.c_int32), ("num_windows", C.c_int32), ("table_bytes", C.c_uint64),
                 ("workspace_bytes_per_signature", C.c_uint64)]
@@ -182,6 +186,10 @@ PROTOTYPES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_expand_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_expand_host": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_field_info": (C.c_int, [C.c_void_p, C.POINTER(FieldInfoStruct)]),
+    "frw_ctx_field_encoding": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "frw_expand_field_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_expand_field_host": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frw_diag_launch_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int32 * 4)]),
     "frw_layout_dual": (C.c_int, [C.c_int, C.POINTER(LayoutDualStruct)]),
     "frw_witness_dual_ntt_verify_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -22,6 +22,10 @@ struct frw_ctx {
     int num_cu;
     frw::Tables *d_tables;
     frw::HostArena arena;            // streams, events, device and page-locked memory of the host-buffer entry points
+    // the fields registered with frw_ctx_field_encoding: encoding FRW_ENC_FIELD_BASE + i is fields[i]; lives and dies with the context
+    int num_fields;
+    uint64_t field_modulus[FRW_MAX_FIELDS][4];
+    frw::FieldConsts fields[FRW_MAX_FIELDS];
 };
 
 namespace {
@@ -80,6 +84,20 @@ bool bad_common(const frw_ctx *ctx, int logn, int encoding)
 {
     return !ctx || (logn != 9 && logn != 10) || (encoding != FRW_ENC_CANONICAL && encoding != FRW_ENC_MONTGOMERY);
 }
+
+// The calls that also take a field registered on the context (FRW_ENC_FIELD_BASE + i): *fc = its constants, or null for the two
+// BLS12-381 encodings.  An id that this context did not hand out is refused like any other unknown encoding.
+bool bad_field_common(const frw_ctx *ctx, int logn, int encoding, const frw::FieldConsts **fc)
+{
+    *fc = nullptr;
+    if (ctx && encoding >= FRW_ENC_FIELD_BASE && encoding < FRW_ENC_FIELD_BASE + ctx->num_fields) {
+        *fc = &ctx->fields[encoding - FRW_ENC_FIELD_BASE];
+        return logn != 9 && logn != 10;
+    }
+    return bad_common(ctx, logn, encoding);
+}
+// what the launchers take as `enc` beside fc (they do not look at it when fc is set)
+int kernel_enc(int encoding, const frw::FieldConsts *fc) { return fc ? FRW_ENC_MONTGOMERY : encoding; }
 
 
 // frw_layout*: the segment table of a circuit's witness laid end to end.  The counts are frw::circuit_shape's; the table has to add up
@@ -165,6 +183,7 @@ int frw_ctx_create(int device, frw_ctx **out)
     ctx->device = device;
     ctx->num_cu = prop.multiProcessorCount;
     ctx->d_tables = nullptr;
+    ctx->num_fields = 0;
     frw::Tables host;
     build_tables(host);
     hipError_t e = hipMalloc((void **)&ctx->d_tables, sizeof(frw::Tables));
@@ -213,24 +232,26 @@ int frw_witness_ntt_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint1
 {
     if (encoding == FRW_ENC_COMPACT)       // d_witness = compact buffer, d_instance unused (may be NULL)
         return frw_witness_ntt_verify_compact_dev(ctx, logn, batch, d_sig, d_pk, d_hm, d_witness, d_status, stream);
-    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_sig || !d_pk || !d_hm || !d_witness || !d_instance || !d_status) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm,
-                                           d_witness, d_instance, d_status, (hipStream_t)stream));
+    FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_sig, d_pk, d_hm,
+                                           d_witness, d_instance, d_status, (hipStream_t)stream, fc));
     return FRW_OK;
 }
 
 int frw_ntt_modq_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_poly, int encoding, uint64_t *d_witness,
                      uint16_t *d_ntt_out, int32_t *d_status, void *stream)
 {
-    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_poly || !d_witness || !d_ntt_out || !d_status) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_poly, d_witness, d_ntt_out,
-                                 d_status, (hipStream_t)stream));
+    FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_poly, d_witness, d_ntt_out,
+                                 d_status, (hipStream_t)stream, fc));
     return FRW_OK;
 }
 
@@ -259,7 +280,8 @@ hipError_t stage_rows(std::initializer_list<const uint16_t *> src, size_t n, siz
 }
 // the witness kernel of a circuit (FRW_ENC_COMPACT: the NTT circuit's compact form; d_witness is the compact buffer, d_instance unused)
 hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, int encoding, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
-                          const uint16_t *d_hm, void *d_witness, uint64_t *d_instance, int32_t *d_status, hipStream_t st)
+                          const uint16_t *d_hm, void *d_witness, uint64_t *d_instance, int32_t *d_status, hipStream_t st,
+                          const frw::FieldConsts *fc = nullptr)
 {
     if (circuit == FRW_CIRCUIT_SCHOOLBOOK)
         return frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
@@ -269,8 +291,8 @@ hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, int encodin
                                                    d_instance, d_status, st);
     if (encoding == FRW_ENC_COMPACT)
         return frw::launch_witness_ntt_verify_compact(ctx->d_tables, ctx->num_cu, logn, batch, d_sig, d_pk, d_hm, d_witness, d_status, st);
-    return frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness, d_instance,
-                                          d_status, st);
+    return frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_sig, d_pk, d_hm,
+                                          (uint64_t *)d_witness, d_instance, d_status, st, fc);
 }
 
 // The host-buffer witness calls of the three circuits.  The pass loop is frw::host_passes (frw_arena.h); this says what a pass is: the
@@ -282,7 +304,11 @@ int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16
                  const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance, int32_t *status, int strict)
 {
     const bool compact = circuit == FRW_CIRCUIT_NTT && encoding == FRW_ENC_COMPACT;    // `witness` = compact buffer, `instance` unused
-    if (compact ? bad_common(ctx, logn, FRW_ENC_MONTGOMERY) : bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
+    // a field registered on the context: the NTT circuit only (the other two need field inverses made by BLS12-381 host code)
+    const frw::FieldConsts *fc = nullptr;
+    if (compact ? bad_common(ctx, logn, FRW_ENC_MONTGOMERY)
+                : circuit == FRW_CIRCUIT_NTT ? bad_field_common(ctx, logn, encoding, &fc) : bad_common(ctx, logn, encoding))
+        return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!sig || !pk || !hm || !witness || (!instance && !compact) || !status) return FRW_E_INVALID_ARG;
     const frw::CircuitShape shape = frw::circuit_shape(circuit, logn);
@@ -304,7 +330,7 @@ int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16
             const uint16_t *d_in = (const uint16_t *)(d + o_in);
             FRW_HIP(stage_rows({sig, pk, hm}, n, lo, cnt, stage, d + o_in, st));
             FRW_HIP(launch_witness(ctx, circuit, logn, encoding, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, d + o_wit,
-                                   (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), st));
+                                   (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), st, fc));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -429,11 +455,13 @@ inline void fr_to_montgomery(const uint64_t x[3], uint64_t out[4])
     const bool ge = t[4] != 0 || !borrow;
     for (int j = 0; j < 4; j++) out[j] = ge ? d[j] : t[j];
 }
-}  // namespace
 
-int frw_expand_host(int logn, size_t batch, const void *compact, uint64_t *witness, uint64_t *instance)
+// The relayout of frw_expand_host for any field.  What an element is comes from the caller: fr_to_montgomery(x as three 64-bit limbs, out)
+// and FR_ONE, the field's one -- under the names the body had when BLS12-381's were the only ones.
+extern "C++" template <class ToField>
+int expand_host_with(int logn, size_t batch, const void *compact, uint64_t *witness, uint64_t *instance, const uint64_t (&FR_ONE)[4],
+                     ToField fr_to_montgomery)
 {
-    if ((logn != 9 && logn != 10) || (batch && (!compact || !witness || !instance))) return FRW_E_INVALID_ARG;
     const frw::CompactLayout c = frw::compact_layout(logn);
     const frw::CircuitShape shape = frw::circuit_shape(FRW_CIRCUIT_NTT, logn);
     const size_t n = shape.n, nb = shape.nb, W = shape.num_witness, I = shape.num_instance;
@@ -486,12 +514,88 @@ int frw_expand_host(int logn, size_t batch, const void *compact, uint64_t *witne
     }
     return FRW_OK;
 }
+}  // namespace
+
+int frw_expand_host(int logn, size_t batch, const void *compact, uint64_t *witness, uint64_t *instance)
+{
+    if ((logn != 9 && logn != 10) || (batch && (!compact || !witness || !instance))) return FRW_E_INVALID_ARG;
+    return expand_host_with(logn, batch, compact, witness, instance, FR_ONE, fr_to_montgomery);
+}
+
+// ---- any four-limb scalar field (frw_field.h): constants of a modulus, the context's registry, the compact expansion ------------
+namespace {
+void limbs64(const uint32_t (&w)[8], uint64_t out[4])
+{
+    for (int j = 0; j < 4; j++) out[j] = (uint64_t)w[2 * j] | ((uint64_t)w[2 * j + 1] << 32);
+}
+}  // namespace
+
+int frw_field_info(const uint64_t modulus[4], frw_field_info_t *out)
+{
+    frw::FieldDerived d;
+    if (!modulus || !out || !frw::field_derive(modulus, &d)) return FRW_E_INVALID_ARG;
+    limbs64(d.fc.p, out->modulus);
+    limbs64(d.fc.one, out->one);
+    limbs64(d.r2, out->r2);
+    out->ninv32 = d.fc.ninv32;
+    out->bits = d.bits;
+    return FRW_OK;
+}
+
+int frw_ctx_field_encoding(frw_ctx *ctx, const uint64_t modulus[4], int *encoding)
+{
+    frw::FieldDerived d;
+    if (!ctx || !modulus || !encoding || !frw::field_derive(modulus, &d)) return FRW_E_INVALID_ARG;
+    for (int i = 0; i < ctx->num_fields; i++)
+        if (!memcmp(ctx->field_modulus[i], modulus, 32)) {
+            *encoding = FRW_ENC_FIELD_BASE + i;
+            return FRW_OK;
+        }
+    if (ctx->num_fields == FRW_MAX_FIELDS) {
+        snprintf(g_last_error, sizeof g_last_error, "frw_ctx_field_encoding: the context already holds %d fields", FRW_MAX_FIELDS);
+        return FRW_E_INVALID_ARG;
+    }
+    memcpy(ctx->field_modulus[ctx->num_fields], modulus, 32);
+    ctx->fields[ctx->num_fields] = d.fc;
+    *encoding = FRW_ENC_FIELD_BASE + ctx->num_fields++;
+    return FRW_OK;
+}
+
+int frw_expand_field_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact, int encoding, uint64_t *d_witness,
+                         uint64_t *d_instance, void *stream)
+{
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, logn, encoding, &fc) || !fc) return FRW_E_INVALID_ARG;          // a registered field, nothing else
+    if (batch == 0) return FRW_OK;
+    if (!d_compact || !d_witness || !d_instance || ((uintptr_t)d_compact & 15)) return FRW_E_INVALID_ARG;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(frw::launch_expand(ctx->num_cu, logn, batch, d_compact, d_witness, d_instance, (hipStream_t)stream, fc));
+    return FRW_OK;
+}
+
+int frw_expand_field_host(const uint64_t modulus[4], int logn, size_t batch, const void *compact, uint64_t *witness, uint64_t *instance)
+{
+    frw::FieldDerived d;
+    if (!modulus || !frw::field_derive(modulus, &d)) return FRW_E_INVALID_ARG;
+    if ((logn != 9 && logn != 10) || (batch && (!compact || !witness || !instance))) return FRW_E_INVALID_ARG;
+    uint64_t one[4];
+    limbs64(d.fc.one, one);
+    const frw::FieldConsts &fc = d.fc;
+    return expand_host_with(logn, batch, compact, witness, instance, one, [&fc](const uint64_t x[3], uint64_t out[4]) {
+        const uint32_t x5[5] = {(uint32_t)x[0], (uint32_t)(x[0] >> 32), (uint32_t)x[1], (uint32_t)(x[1] >> 32), (uint32_t)x[2]};
+        uint32_t e[8];
+        if (!(x5[1] | x5[2] | x5[3] | x5[4])) frw::field_encode_u32(fc, x5[0], e);
+        else frw::field_encode_u160(fc, x5, e);
+        limbs64(e, out);
+    });
+}
 
 int frw_diag_launch_shape(frw_ctx *ctx, int logn, int encoding, size_t batch, int32_t out[4])
 {
-    if (!ctx || !out || (logn != 9 && logn != 10) || encoding < 0 || encoding > 2) return FRW_E_INVALID_ARG;
+    const bool field = ctx && encoding >= FRW_ENC_FIELD_BASE && encoding < FRW_ENC_FIELD_BASE + ctx->num_fields;
+    if (!ctx || !out || (logn != 9 && logn != 10) || ((encoding < 0 || encoding > 2) && !field)) return FRW_E_INVALID_ARG;
     int o[4];
-    frw::launch_shape_witness_ntt_verify(ctx->num_cu, logn, encoding, batch, o);
+    frw::launch_shape_witness_ntt_verify(ctx->num_cu, logn, field ? 3 : encoding, batch, o);
     for (int i = 0; i < 4; i++) out[i] = o[i];
     return FRW_OK;
 }
@@ -536,7 +640,8 @@ int frw_witness_schoolbook_verify(frw_ctx *ctx, int logn, size_t batch, const ui
 int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int encoding, uint64_t *witness,
                  uint16_t *ntt_out, int32_t *status)
 {
-    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!poly || !witness || !ntt_out || !status) return FRW_E_INVALID_ARG;
     // as witness_host: one slot and one stream for a batch that fits a chunk, else two
@@ -552,8 +657,8 @@ int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int
         {{witness, o_wit, wbytes}, {ntt_out, o_out, n * 2}, {status, o_st, sizeof(int32_t)}},
         [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
             FRW_HIP(stage_rows({poly}, n, lo, cnt, stage, d + o_in, st));
-            FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, encoding, cnt, (const uint16_t *)(d + o_in), (uint64_t *)(d + o_wit),
-                                         (uint16_t *)(d + o_out), (int32_t *)(d + o_st), st));
+            FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), cnt, (const uint16_t *)(d + o_in),
+                                         (uint64_t *)(d + o_wit), (uint16_t *)(d + o_out), (int32_t *)(d + o_st), st, fc));
             return FRW_OK;
         });
 }
@@ -640,9 +745,10 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
 
 // ---- the verifier's statement: instance_assignment from (pk, hm), or from the key's and the message's bytes; no signature -------------
 namespace {
-bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding)
+// (a registered field is accepted for every circuit: the instance values are below q in all three)
+bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding, const frw::FieldConsts **fc)
 {
-    return bad_common(ctx, logn, encoding) || !frw::known_circuit(circuit);
+    return bad_field_common(ctx, logn, encoding, fc) || !frw::known_circuit(circuit);
 }
 // the schoolbook circuit's public inputs are the coefficients themselves (falcon_schoolbook.rs:66-83), the NTT circuits' their transforms
 int statement_form(int circuit) { return circuit == FRW_CIRCUIT_SCHOOLBOOK ? 1 : 0; }
@@ -652,12 +758,13 @@ constexpr size_t STATEMENT_CHUNK = 4096;          // statements of one pass of t
 int frw_statement_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *d_pk, const uint16_t *d_hm, int encoding,
                       uint64_t *d_instance, int32_t *d_status, void *stream)
 {
-    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (!d_pk || !d_hm || !d_instance || !d_status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, batch, d_pk, d_hm, d_instance,
-                                  nullptr, 1, nullptr, d_status, nullptr, (hipStream_t)stream));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), batch, d_pk, d_hm,
+                                  d_instance, nullptr, 1, nullptr, d_status, nullptr, (hipStream_t)stream, fc));
     return FRW_OK;
 }
 
@@ -671,7 +778,8 @@ int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t bat
                                  const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding, uint64_t *d_instance, int32_t *d_status,
                                  void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (!d_pk_bytes || !d_nonces || !d_msgs || !d_msg_off || !d_instance || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
     if (((uintptr_t)d_workspace & 15) || workspace_bytes < frw_statement_workspace_bytes(logn, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
@@ -680,15 +788,16 @@ int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t bat
     FRW_HIP(hipSetDevice(ctx->device));
     FRW_HIP(frw::launch_decode_public_keys(logn, batch, d_pk_bytes, ws.pk, ws.decode_status, st));
     FRW_HIP(frw::launch_hash_to_point(logn, batch, d_nonces, d_msgs, d_msg_off, ws.hm, st));
-    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, batch, ws.pk, ws.hm, d_instance,
-                                  nullptr, 1, ws.decode_status, d_status, nullptr, st));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), batch, ws.pk, ws.hm,
+                                  d_instance, nullptr, 1, ws.decode_status, d_status, nullptr, st, fc));
     return FRW_OK;
 }
 
 int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *pk, const uint16_t *hm, int encoding,
                   uint64_t *instance, int32_t *status, int strict)
 {
-    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (!pk || !hm || !instance || !status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     const size_t n = (size_t)1 << logn, ibytes = frw::circuit_shape(circuit, logn).num_instance * 32, chunk = std::min(batch, STATEMENT_CHUNK);
@@ -701,8 +810,8 @@ int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint1
         [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
             const uint16_t *d_in = (const uint16_t *)(d + o_in);
             FRW_HIP(stage_rows({pk, hm}, n, lo, cnt, stage, d + o_in, st));
-            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, d_in, d_in + cnt * n,
-                                          (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), cnt, d_in,
+                                          d_in + cnt * n, (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st, fc));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -711,7 +820,8 @@ int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint1
 int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *nonces,
                              const uint8_t *msgs, const uint64_t *msg_off, int encoding, uint64_t *instance, int32_t *status, int strict)
 {
-    if (bad_statement(ctx, circuit, logn, encoding)) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
     if (!pk_bytes || !nonces || !msg_off || !instance || !status) return FRW_E_INVALID_ARG;
     if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
@@ -730,8 +840,8 @@ int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, 
             const frw::StatementBufs ws = frw::statement_layout(d + o_ws, logn, cnt);
             FRW_HIP(frw::launch_decode_public_keys(logn, cnt, in.d_pk(d), ws.pk, ws.decode_status, st));
             FRW_HIP(frw::launch_hash_to_point(logn, cnt, in.d_second(d), in.d_msgs(d), in.d_off(d), ws.hm, st));
-            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), encoding, cnt, ws.pk, ws.hm,
-                                          (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), cnt, ws.pk, ws.hm,
+                                          (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st, fc));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -1271,18 +1381,20 @@ int frw_gadget_block_len(int kind)
 int frw_gadget_dev(frw_ctx *ctx, int kind, size_t count, const void *d_a, const uint64_t *d_b, int encoding,
                    uint64_t *d_out, int32_t *d_status, void *stream)
 {
-    if (bad_common(ctx, 10, encoding) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, 10, encoding, &fc) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
     if (count == 0) return FRW_OK;
     if (!d_a || !d_out || (kind == FRW_G_ADD_MOD && !d_b)) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_gadget(kind, encoding, count, d_a, d_b, d_out, d_status, (hipStream_t)stream));
+    FRW_HIP(frw::launch_gadget(kind, kernel_enc(encoding, fc), count, d_a, d_b, d_out, d_status, (hipStream_t)stream, fc));
     return FRW_OK;
 }
 
 int frw_gadget(frw_ctx *ctx, int kind, size_t count, const void *a, const uint64_t *b, int encoding, uint64_t *out,
                int32_t *status)
 {
-    if (bad_common(ctx, 10, encoding) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
+    const frw::FieldConsts *fc;
+    if (bad_field_common(ctx, 10, encoding, &fc) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
     if (count == 0) return FRW_OK;
     if (!a || !out || (kind == FRW_G_ADD_MOD && !b)) return FRW_E_INVALID_ARG;
     frw::HostArena &A = ctx->arena;
@@ -1302,7 +1414,7 @@ int frw_gadget(frw_ctx *ctx, int kind, size_t count, const void *a, const uint64
     hipStream_t st = A.compute;
     FRW_HIP(hipMemcpyAsync(d_a, a, in_bytes, hipMemcpyHostToDevice, st));
     if (b_bytes) FRW_HIP(hipMemcpyAsync(d_b, b, b_bytes, hipMemcpyHostToDevice, st));
-    FRW_HIP(frw::launch_gadget(kind, encoding, count, d_a, b_bytes ? d_b : nullptr, d_out, d_st, st));
+    FRW_HIP(frw::launch_gadget(kind, kernel_enc(encoding, fc), count, d_a, b_bytes ? d_b : nullptr, d_out, d_st, st, fc));
     FRW_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     if (status) FRW_HIP(hipMemcpyAsync(status, d_st, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FRW_HIP(hipStreamSynchronize(st));

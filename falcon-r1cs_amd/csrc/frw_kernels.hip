@@ -14,7 +14,8 @@
 // divisions, Montgomery conversions, the tile writer's 3 vector instructions per store) lives in LDS/registers
 // and overlaps with the stores of the other resident wavefronts.  No MFMA: nothing here is GEMM-shaped.
 //
-// Kernels in this file: witness_ntt_verify_kernel (the hot path; ENC = 2 writes the compact encoding),
+// Kernels in this file: witness_ntt_verify_kernel (the hot path; ENC = 2 writes the compact encoding, ENC = 3 Montgomery form over
+// a field whose constants arrive as a kernel argument: frw_field.h),
 // witness_dual_ntt_verify_kernel (the signed-split variant, falcon_dual_ntt.rs), ntt_modq_kernel (ntt_circuit alone),
 // expand_kernel (compact -> arkworks layout), gadget_kernel (the gadgets called on their own), digest_kernel and
 // write_stream_kernel (verification / calibration utilities).
@@ -34,6 +35,7 @@
 #include <algorithm>
 #include <mutex>
 #include "frw_device.h"
+#include "frw_field.h"
 
 namespace frw {
 
@@ -98,10 +100,34 @@ __device__ __forceinline__ void cond_sub_p(uint32_t (&T)[9], uint32_t (&out)[8])
     for (int j = 0; j < 8; j++) out[j] = bw ? T[j] : d[j];
 }
 
-// integer < 2^32  ->  field element in the requested encoding
-template <int ENC>
-__device__ __forceinline__ void encode_u32(uint32_t x, uint32_t (&out)[8])
+// What an instantiation gets of the field.  ENC 0, 1, 2 know BLS12-381's Fr from the literals above and carry an empty argument;
+// ENC 3 = "Montgomery form, constants from an argument": FieldConsts (frw_field.h) by value, a kernel argument of 33 words that
+// is the same for every lane of a launch and therefore lives in scalar registers.
+struct NoField {};
+template <int ENC> struct FieldArg { using type = NoField; };
+template <> struct FieldArg<3> { using type = FieldConsts; };
+template <int ENC> using field_arg_t = typename FieldArg<ENC>::type;
+
+// this half (0: limbs 0..3, 1: limbs 4..7) of the field element one in the requested encoding
+template <int ENC, typename FA = NoField>
+__device__ __forceinline__ v4u one_half(int h, const FA &fa = FA())
 {
+    if constexpr (ENC == 3) {
+        return h ? mk4(fa.one[4], fa.one[5], fa.one[6], fa.one[7]) : mk4(fa.one[0], fa.one[1], fa.one[2], fa.one[3]);
+    } else {
+        constexpr uint32_t R[8] = FRW_R32;
+        return ENC == 0 ? (h ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0)) : (h ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+    }
+}
+
+// integer < 2^32  ->  field element in the requested encoding
+template <int ENC, typename FA = NoField>
+__device__ __forceinline__ void encode_u32(uint32_t x, uint32_t (&out)[8], const FA &fa = FA())
+{
+    if constexpr (ENC == 3) {
+        field_encode_u32(fa, x, out);
+        return;
+    }
 #if defined(FRW_FAKE_ENCODE)      // timing experiments only (tools/ab_variants.py): what would cheaper encodes buy?
     if (true) {
 #else
@@ -119,9 +145,13 @@ __device__ __forceinline__ void encode_u32(uint32_t x, uint32_t (&out)[8])
 }
 
 // integer < 2^160 (five limbs)  ->  field element
-template <int ENC>
-__device__ __forceinline__ void encode_u160(const uint32_t (&x)[5], uint32_t (&out)[8])
+template <int ENC, typename FA = NoField>
+__device__ __forceinline__ void encode_u160(const uint32_t (&x)[5], uint32_t (&out)[8], const FA &fa = FA())
 {
+    if constexpr (ENC == 3) {
+        field_encode_u160(fa, x, out);
+        return;
+    }
 #if defined(FRW_FAKE_ENCODE)
     if (true) {
 #else
@@ -442,15 +472,16 @@ __device__ __forceinline__ void init_vtab_rows(uint16_t *vtab, int row0, int row
 __device__ __forceinline__ void init_vtab(uint16_t *vtab, int rows, int tid) { init_vtab_rows(vtab, 0, rows, tid); }
 
 // the wave's constants: 16 lanes write the four group constants of (slot 0 | 1, half 0 | 1): zero | this half of one
-template <int ENC>
-__device__ __forceinline__ void init_slab_const(uint32_t slab_w, int lane)
+template <int ENC, typename FA = NoField>
+__device__ __forceinline__ void init_slab_const(uint32_t slab_w, int lane, const FA &fa = FA())
 {
     constexpr uint32_t R[8] = FRW_R32;
     if (lane < 16) {
         const int slot = lane >> 3, h = (lane >> 2) & 1, g = lane & 3;
         v4u c = mk4(0, 0, 0, 0);
         if (slot == 1) {
-            if (ENC == 0) c = h ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0);
+            if constexpr (ENC == 3) c = one_half<3>(h, fa);
+            else if (ENC == 0) c = h ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0);
             else c = h ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]);
         }
         *(FRW_LDS v4u *)(uintptr_t)(slab_w + slot * SLAB_SLOT + h * SLAB_HALF + g * SLAB_GRP + 256) = c;
@@ -605,13 +636,14 @@ __device__ __forceinline__ M lane_read(M v, int k)
     else return (M)__shfl((unsigned long long)v, k, WAVE);
 }
 
-template <int ENC, int BLK, int NVAL, int VFIRST, typename MASK>
-__device__ __forceinline__ void emit_tile_generic(v4u *__restrict__ out, const v4u *slab, MASK mask, int lane, int nchunks)
+template <int ENC, int BLK, int NVAL, int VFIRST, typename MASK, typename FA = NoField>
+__device__ __forceinline__ void emit_tile_generic(v4u *__restrict__ out, const v4u *slab, MASK mask, int lane, int nchunks, const FA &fa = FA())
 {
     constexpr uint32_t R[8] = FRW_R32;
     const int half = lane & 1;
     v4u one;
-    if (ENC == 0) one = half ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0);
+    if constexpr (ENC == 3) one = one_half<3>(half, fa);
+    else if (ENC == 0) one = half ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0);
     else one = half ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]);
     lds_fence();
     for (int it = 0; it < 2 * BLK; it++) {
@@ -686,7 +718,7 @@ template <int LOGN, int ENC>
 __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
     const Tables *__restrict__ tab, size_t batch, size_t full,
     const uint16_t *__restrict__ g_sig, const uint16_t *__restrict__ g_pk, const uint16_t *__restrict__ g_hm,
-    v4u *__restrict__ g_wit, v4u *__restrict__ g_inst, int32_t *__restrict__ g_status)
+    v4u *__restrict__ g_wit, v4u *__restrict__ g_inst, int32_t *__restrict__ g_status, const field_arg_t<ENC> fa)
 {
     constexpr int N = 1 << LOGN;
     constexpr int NB = LOGN == 9 ? 50 : 52;
@@ -711,7 +743,7 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
     for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
     if constexpr (!COMPACT) {
         init_vtab(sm.vtab, VTAB_ROWS, tid);
-        init_slab_const<ENC>(wc.slab, lane);
+        init_slab_const<ENC>(wc.slab, lane, fa);
     }
 
     const size_t items = full + (batch - full) * PARTS;
@@ -775,9 +807,7 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
         uint32_t e8[8];
         // instance_assignment[0] = 1; then pk_ntt, hm_ntt                                   :63,:67
         if (!COMPACT && tid < 2 && does(0)) {
-            constexpr uint32_t R[8] = FRW_R32;
-            v4u one = ENC == 0 ? (tid ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0))
-                                 : (tid ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+            const v4u one = one_half<ENC>(tid, fa);
             inst[tid] = one;
         }
         if (does(0) || does(1))
@@ -793,14 +823,14 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
                 const uint32_t wd = pack_bits<27>(ltq_mask(vk), lane);
                 if (lane < 54) cb[t * 54 + lane] = wd;
             } else {
-            encode_u32<VENC>(s_npk[k], e8); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<VENC>(s_npk[k], e8, fa); slab_put(wc.slab, 0, lane, e8);
             emit_values(ri, 32 + t * TILE1, wc);
-            encode_u32<VENC>(s_nhm[k], e8); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<VENC>(s_nhm[k], e8, fa); slab_put(wc.slab, 0, lane, e8);
             emit_values(ri, 32 + (N / WAVE + t) * TILE1, wc);
             // S0 sig, S1 v                                                                  :58-59,:71
-            encode_u32<VENC>(sm.sig[k], e8); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<VENC>(sm.sig[k], e8, fa); slab_put(wc.slab, 0, lane, e8);
             emit_values(rw, t * TILE1, wc);
-            encode_u32<VENC>(vk, e8); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<VENC>(vk, e8, fa); slab_put(wc.slab, 0, lane, e8);
             emit_values(rw, (N / WAVE + t) * TILE1, wc);
             // S2 enforce_less_than_q(v[k])                                                  :73-77
             emit_tile<27>(rw, (2 * N + t * WAVE * 27) * 32, ltq_mask(vk), wc);
@@ -818,9 +848,9 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
                     const uint32_t wd = pack_bits<27>(ltq_mask(c), lane);
                     if (lane < 54) cb[3 * CL.seg_words + t * 54 + lane] = wd;
                 } else {
-                encode_u32<VENC>(prod, e8); slab_put(wc.slab, 0, lane, e8);
-                encode_u32<VENC>(tq, e8);   slab_put(wc.slab, 1, lane, e8);
-                encode_u32<VENC>(c, e8);    slab_put(wc.slab, 2, lane, e8);
+                encode_u32<VENC>(prod, e8, fa); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<VENC>(tq, e8, fa);   slab_put(wc.slab, 1, lane, e8);
+                encode_u32<VENC>(c, e8, fa);    slab_put(wc.slab, 2, lane, e8);
                 emit_tile<30>(rw, (87 * N + t * WAVE * 30) * 32, ltq_mask(c) << 3, wc);
                 }
             }
@@ -841,8 +871,8 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
                 const uint32_t wd = pack_bits<16>(m, lane);
                 if (lane < 32) cb[4 * CL.seg_words + t * 32 + lane] = wd;
             } else {
-            encode_u32<VENC>(r, e8);  slab_put(wc.slab, 0, lane, e8);
-            encode_u32<VENC>(sq, e8); slab_put(wc.slab, 1, lane, e8);
+            encode_u32<VENC>(r, e8, fa);  slab_put(wc.slab, 0, lane, e8);
+            encode_u32<VENC>(sq, e8, fa); slab_put(wc.slab, 1, lane, e8);
             emit_tile<18>(rw, (117 * N + t * WAVE * 18) * 32, m, wc);
             }
         }
@@ -864,10 +894,7 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
                 if (lane < 2 + GAP) cb[4 * CL.seg_words + N + lane] = lane < 2 ? (uint32_t)(nm >> (32 * lane)) : 0u;
                 if (lane < TAIL) ((uint32_t *)(cbase + CL.status_off))[lane] = lane == 0 ? (uint32_t)verdict : 0u;
             } else {
-            constexpr uint32_t R[8] = FRW_R32;
-            const int half = lane & 1;
-            v4u one = ENC == 0 ? (half ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0))
-                                 : (half ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+            const v4u one = one_half<ENC>(lane & 1, fa);
             v4u *o = wit + (size_t)153 * N * 2;
             for (int c = lane; c < NB * 2; c += WAVE) {
                 const int pos = c >> 1;
@@ -896,8 +923,8 @@ __global__ __launch_bounds__(BLOCK) void witness_ntt_verify_kernel(
                     const uint32_t wd = pack_bits<27>(ltq_mask(b), lane);
                     if (lane < 54) cb[(which ? 2 : 1) * CL.seg_words + t * 54 + lane] = wd;
                 } else {
-                encode_u160<VENC>(q5, e8); slab_put(wc.slab, 0, lane, e8);    // t_var :137
-                encode_u32<VENC>(b, e8);   slab_put(wc.slab, 1, lane, e8);    // b_var :138
+                encode_u160<VENC>(q5, e8, fa); slab_put(wc.slab, 0, lane, e8);    // t_var :137
+                encode_u32<VENC>(b, e8, fa);   slab_put(wc.slab, 1, lane, e8);    // b_var :138
                 emit_tile<29>(rw, seg + t * WAVE * 29 * 32, ltq_mask(b) << 2, wc);
                 }
             }
@@ -1316,7 +1343,7 @@ template <int LOGN, int FORM, int ENC>
 __global__ __launch_bounds__(BLOCK) void statement_kernel(
     const Tables *__restrict__ tab, size_t batch, const uint16_t *__restrict__ g_pk, const uint16_t *__restrict__ g_hm,
     v4u *__restrict__ g_out, const uint64_t *__restrict__ offs, int lead, const int32_t *__restrict__ pre,
-    int32_t *__restrict__ g_status, const uint32_t *__restrict__ sidx)
+    int32_t *__restrict__ g_status, const uint32_t *__restrict__ sidx, const field_arg_t<ENC> fa)
 {
     constexpr int N = 1 << LOGN;
     constexpr size_t I = 2 * (size_t)N + 1;
@@ -1331,9 +1358,7 @@ __global__ __launch_bounds__(BLOCK) void statement_kernel(
     wc.lane = lane;
     if constexpr (FORM == 0)
         for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
-    constexpr uint32_t R[8] = FRW_R32;
-    const v4u one = ENC == 0 ? (tid & 1 ? mk4(0, 0, 0, 0) : mk4(1, 0, 0, 0))
-                             : (tid & 1 ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]));
+    const v4u one = one_half<ENC>(tid & 1, fa);
 
     const size_t items = batch * 2;
     for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -1372,7 +1397,7 @@ __global__ __launch_bounds__(BLOCK) void statement_kernel(
         const __amdgpu_buffer_rsrc_t ro = make_rsrc(dst, (uint32_t)(N * 32));
         uint32_t e8[8];
         for (int t = wave; t < TILES; t += WAVES) {
-            encode_u32<ENC>(sm.poly[t * WAVE + lane], e8); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<ENC>(sm.poly[t * WAVE + lane], e8, fa); slab_put(wc.slab, 0, lane, e8);
             emit_values(ro, t * TILE1, wc);
         }
         lds_barrier();                      // sm.poly and sm.bad are rewritten by the next item
@@ -1513,7 +1538,7 @@ template <int LOGN, int ENC>
 __global__ __launch_bounds__(BLOCK) void ntt_modq_kernel(
     const Tables *__restrict__ tab, size_t batch,
     const uint16_t *__restrict__ g_poly,
-    v4u *__restrict__ g_wit, uint16_t *__restrict__ g_ntt, int32_t *__restrict__ g_status)
+    v4u *__restrict__ g_wit, uint16_t *__restrict__ g_ntt, int32_t *__restrict__ g_status, const field_arg_t<ENC> fa)
 {
     constexpr int N = 1 << LOGN;
     constexpr int TILES = N / WAVE;
@@ -1527,7 +1552,7 @@ __global__ __launch_bounds__(BLOCK) void ntt_modq_kernel(
     wc.lane = lane;
     for (int j = tid; j < N; j += BLOCK) sm.tw[j] = tab->tw[j];
     init_vtab(sm.vtab, TileShape<30>::ROW0, tid);
-    init_slab_const<ENC>(wc.slab, lane);
+    init_slab_const<ENC>(wc.slab, lane, fa);
 
     for (size_t s = blockIdx.x; s < batch; s += gridDim.x) {
         if (tid == 0) sm.bad = 0;
@@ -1556,8 +1581,8 @@ __global__ __launch_bounds__(BLOCK) void ntt_modq_kernel(
             for (int i = 0; i < 5; i++) a[i] = sm.lad[i * N + k];
             const uint32_t b = divmod_q_u160(a, q5);
             g_ntt[s * N + k] = (uint16_t)b;
-            encode_u160<ENC>(q5, e8); slab_put(wc.slab, 0, lane, e8);
-            encode_u32<ENC>(b, e8);   slab_put(wc.slab, 1, lane, e8);
+            encode_u160<ENC>(q5, e8, fa); slab_put(wc.slab, 0, lane, e8);
+            encode_u32<ENC>(b, e8, fa);   slab_put(wc.slab, 1, lane, e8);
             emit_tile<29>(rw, t * WAVE * 29 * 32, ltq_mask(b) << 2, wc);
         }
         lds_barrier();
@@ -1566,7 +1591,8 @@ __global__ __launch_bounds__(BLOCK) void ntt_modq_kernel(
 
 // ------------------------------------------------------------------------------------------------
 // kernel: FRW_ENC_COMPACT -> the arkworks buffers (witness_assignment / instance_assignment, Montgomery), i.e. exactly
-// what witness_ntt_verify_kernel<LOGN, 1> writes.  The integers of the compact buffer are converted to Montgomery form
+// what witness_ntt_verify_kernel<LOGN, ENC> writes (ENC = 1: BLS12-381's Fr; 3: the field of the argument).
+// The integers of the compact buffer are converted to Montgomery form
 // (the same CIOS rounds the generator uses) into the wave's slab, the booleans of a tile are cut out of the bit array
 // (two ds_bpermute per lane) and handed to emit_tile as the per-block mask.  A receiver of an all-gathered compact chunk
 // runs this locally: 0.11 MB cross the fabric per Falcon-1024 signature instead of 5.08 MB.
@@ -1586,9 +1612,9 @@ __device__ __forceinline__ uint32_t unpack_bits(uint32_t word, int lane)
     return (uint32_t)(both >> o) & ((1u << NB) - 1u);
 }
 
-template <int LOGN>
+template <int LOGN, int ENC>
 __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsigned char *__restrict__ g_compact,
-                                                       v4u *__restrict__ g_wit, v4u *__restrict__ g_inst)
+                                                       v4u *__restrict__ g_wit, v4u *__restrict__ g_inst, const field_arg_t<ENC> fa)
 {
     constexpr int N = 1 << LOGN;
     constexpr int NB = LOGN == 9 ? 50 : 52;
@@ -1605,10 +1631,9 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsig
     wc.vtab = (uint32_t)(uintptr_t)(FRW_LDS void *)sm.vtab + lane * 2;
     wc.lane = lane;
     init_vtab(sm.vtab, VTAB_ROWS, tid);
-    init_slab_const<1>(wc.slab, lane);
+    init_slab_const<ENC>(wc.slab, lane, fa);
     lds_barrier();
-    constexpr uint32_t R[8] = FRW_R32;
-    const v4u one = lane & 1 ? mk4(R[4], R[5], R[6], R[7]) : mk4(R[0], R[1], R[2], R[3]);
+    const v4u one = one_half<ENC>(lane & 1, fa);
 
     for (size_t s = blockIdx.x; s < batch; s += gridDim.x) {
         const unsigned char *cbase = g_compact + s * CL.bytes;
@@ -1644,13 +1669,13 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsig
             for (int t = wave; t < TILES; t += WAVES) {
                 const uint32_t c_pk = n_pk, c_hm = n_hm, c_sig = n_sig, c_v = n_v, c_wd = n_wd;
                 if (t + WAVES < TILES) ld(t + WAVES);
-                encode_u32<1>(c_pk, e8); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_pk, e8, fa); slab_put(wc.slab, 0, lane, e8);
                 emit_values(ri, 32 + t * TILE1, wc);
-                encode_u32<1>(c_hm, e8); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_hm, e8, fa); slab_put(wc.slab, 0, lane, e8);
                 emit_values(ri, 32 + (N / WAVE + t) * TILE1, wc);
-                encode_u32<1>(c_sig, e8); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_sig, e8, fa); slab_put(wc.slab, 0, lane, e8);
                 emit_values(rw, t * TILE1, wc);
-                encode_u32<1>(c_v, e8); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_v, e8, fa); slab_put(wc.slab, 0, lane, e8);
                 emit_values(rw, (N / WAVE + t) * TILE1, wc);
                 emit_tile<27>(rw, (2 * N + t * WAVE * 27) * 32, unpack_bits<27>(c_wd, lane), wc);
             }
@@ -1673,8 +1698,8 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsig
                 for (int i = 0; i < 5; i++) q5[i] = n_q[i];
                 const uint32_t c_b = n_b, c_wd = n_wd;
                 if (t + WAVES < TILES) ld(t + WAVES);
-                encode_u160<1>(q5, e8); slab_put(wc.slab, 0, lane, e8);
-                encode_u32<1>(c_b, e8); slab_put(wc.slab, 1, lane, e8);
+                encode_u160<ENC>(q5, e8, fa); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_b, e8, fa); slab_put(wc.slab, 1, lane, e8);
                 emit_tile<29>(rw, ((which ? 58 : 29) * N + t * WAVE * 29) * 32, unpack_bits<27>(c_wd, lane) << 2, wc);
             }
         }
@@ -1691,9 +1716,9 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsig
             for (int t = wave; t < TILES; t += WAVES) {
                 const uint32_t c0 = n_a[0], c1 = n_a[1], c2 = n_a[2], c_wd = n_wd;
                 if (t + WAVES < TILES) ld(t + WAVES);
-                encode_u32<1>(c0, e8); slab_put(wc.slab, 0, lane, e8);
-                encode_u32<1>(c1, e8); slab_put(wc.slab, 1, lane, e8);
-                encode_u32<1>(c2, e8); slab_put(wc.slab, 2, lane, e8);
+                encode_u32<ENC>(c0, e8, fa); slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c1, e8, fa); slab_put(wc.slab, 1, lane, e8);
+                encode_u32<ENC>(c2, e8, fa); slab_put(wc.slab, 2, lane, e8);
                 emit_tile<30>(rw, (87 * N + t * WAVE * 30) * 32, unpack_bits<27>(c_wd, lane) << 3, wc);
             }
         }
@@ -1709,8 +1734,8 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(size_t batch, const unsig
             for (int t = wave; t < 2 * TILES; t += WAVES) {
                 const uint32_t c_r = n_r, c_sq = n_sq, c_wd = n_wd;
                 if (t + WAVES < 2 * TILES) ld(t + WAVES);
-                encode_u32<1>(c_r, e8);  slab_put(wc.slab, 0, lane, e8);
-                encode_u32<1>(c_sq, e8); slab_put(wc.slab, 1, lane, e8);
+                encode_u32<ENC>(c_r, e8, fa);  slab_put(wc.slab, 0, lane, e8);
+                encode_u32<ENC>(c_sq, e8, fa); slab_put(wc.slab, 1, lane, e8);
                 emit_tile<18>(rw, (117 * N + t * WAVE * 18) * 32, unpack_bits<16>(c_wd, lane), wc);
             }
         }
@@ -1745,7 +1770,7 @@ template <> struct GadgetShape<G_NORM_1024>   { static constexpr int BLK = 52, N
 template <int KIND, int ENC>
 __global__ __launch_bounds__(BLOCK) void gadget_kernel(size_t count, const void *__restrict__ in_a,
                                                        const uint64_t *__restrict__ in_b, v4u *__restrict__ out,
-                                                       int32_t *__restrict__ status)
+                                                       int32_t *__restrict__ status, const field_arg_t<ENC> fa)
 {
     using S = GadgetShape<KIND>;
     using mask_t = typename S::mask_t;
@@ -1767,8 +1792,8 @@ __global__ __launch_bounds__(BLOCK) void gadget_kernel(size_t count, const void 
 #pragma unroll
             for (int i = 0; i < 5; i++) a[i] = live ? ((const uint32_t *)in_a)[item * 5 + i] : 0;
             const uint32_t b = divmod_q_u160(a, q5);
-            encode_u160<ENC>(q5, e8); gslab_put(slab, 0, lane, e8);
-            encode_u32<ENC>(b, e8);   gslab_put(slab, 1, lane, e8);
+            encode_u160<ENC>(q5, e8, fa); gslab_put(slab, 0, lane, e8);
+            encode_u32<ENC>(b, e8, fa);   gslab_put(slab, 1, lane, e8);
             mask = ltq_mask(b) << 2;
         } else if (KIND == G_ADD_MOD) {
             const uint64_t a = live ? ((const uint64_t *)in_a)[item] : 0, b = live ? in_b[item] : 0;
@@ -1777,8 +1802,8 @@ __global__ __launch_bounds__(BLOCK) void gadget_kernel(size_t count, const void 
             const uint64_t tq = ab / Q;
             const uint32_t c = (uint32_t)(ab - tq * Q);               // :242-243
             const uint32_t t5[5] = {(uint32_t)tq, (uint32_t)(tq >> 32), 0, 0, 0};
-            encode_u160<ENC>(t5, e8); gslab_put(slab, 0, lane, e8);
-            encode_u32<ENC>(c, e8);   gslab_put(slab, 1, lane, e8);
+            encode_u160<ENC>(t5, e8, fa); gslab_put(slab, 0, lane, e8);
+            encode_u32<ENC>(c, e8, fa);   gslab_put(slab, 1, lane, e8);
             mask = ltq_mask(c) << 2;
         } else if (KIND == G_L2_ELEM) {
             const uint64_t a = live ? ((const uint64_t *)in_a)[item] : 0;
@@ -1786,10 +1811,10 @@ __global__ __launch_bounds__(BLOCK) void gadget_kernel(size_t count, const void 
             const uint32_t e = (uint32_t)a;
             mask = lt6144_mask(e & 0x3fffu);
             const uint32_t r = (mask >> 15) & 1u ? e : Q - e;
-            encode_u32<ENC>(r, e8); gslab_put(slab, 0, lane, e8);
+            encode_u32<ENC>(r, e8, fa); gslab_put(slab, 0, lane, e8);
             const uint64_t sq = (uint64_t)r * r;
             const uint32_t s5[5] = {(uint32_t)sq, (uint32_t)(sq >> 32), 0, 0, 0};
-            encode_u160<ENC>(s5, e8); gslab_put(slab, 1, lane, e8);
+            encode_u160<ENC>(s5, e8, fa); gslab_put(slab, 1, lane, e8);
         } else {
             const uint64_t a = live ? ((const uint64_t *)in_a)[item] : 0;
             mask = KIND == G_NORM_512 ? norm_mask_512(a) : norm_mask_1024(a);
@@ -1797,7 +1822,7 @@ __global__ __launch_bounds__(BLOCK) void gadget_kernel(size_t count, const void 
         if (live && status) status[item] = st;
         const size_t remaining = count - t * WAVE;
         const int nchunks = (int)(remaining >= WAVE ? WAVE : remaining) * S::BLK * 2;
-        emit_tile_generic<ENC, S::BLK, S::NVAL, S::VFIRST, mask_t>(out + t * WAVE * S::BLK * 2, slab, mask, lane, nchunks);
+        emit_tile_generic<ENC, S::BLK, S::NVAL, S::VFIRST, mask_t>(out + t * WAVE * S::BLK * 2, slab, mask, lane, nchunks, fa);
     }
 }
 
@@ -1873,6 +1898,8 @@ static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4], g_occ_schoolbook[4];   
 static int g_occ_compact[2], g_occ_expand[2];                  // [LOGN - 9]
 static int g_occ_statement[8];                                 // [(LOGN - 9) * 4 + FORM * 2 + ENC]
 static int g_occ_falcon_verify[4];                             // [(LOGN - 9) * 2 + RULE]
+// the ENC = 3 instantiations (a field registered on the context): [LOGN - 9], the statement's [(LOGN - 9) * 2 + FORM]
+static int g_occ_verify_field[2], g_occ_ntt_field[2], g_occ_expand_field[2], g_occ_statement_field[4];
 static std::once_flag g_occ_once;
 
 template <typename K>
@@ -1931,8 +1958,8 @@ void init_launch_config()
 #undef FRW_Q
         query_residency(witness_ntt_verify_kernel<9, 2>, g_occ_compact[0]);
         query_residency(witness_ntt_verify_kernel<10, 2>, g_occ_compact[1]);
-        query_residency(expand_kernel<9>, g_occ_expand[0]);
-        query_residency(expand_kernel<10>, g_occ_expand[1]);
+        query_residency(expand_kernel<9, 1>, g_occ_expand[0]);
+        query_residency(expand_kernel<10, 1>, g_occ_expand[1]);
 #define FRW_QS(LOGN, FORM, ENC) query_residency(statement_kernel<LOGN, FORM, ENC>, g_occ_statement[(LOGN - 9) * 4 + FORM * 2 + ENC])
         FRW_QS(9, 0, 0); FRW_QS(9, 0, 1); FRW_QS(9, 1, 0); FRW_QS(9, 1, 1);
         FRW_QS(10, 0, 0); FRW_QS(10, 0, 1); FRW_QS(10, 1, 0); FRW_QS(10, 1, 1);
@@ -1941,7 +1968,24 @@ void init_launch_config()
         query_residency(falcon_verify_kernel<9, 1>, g_occ_falcon_verify[1]);
         query_residency(falcon_verify_kernel<10, 0>, g_occ_falcon_verify[2]);
         query_residency(falcon_verify_kernel<10, 1>, g_occ_falcon_verify[3]);
+        query_residency(witness_ntt_verify_kernel<9, 3>, g_occ_verify_field[0]);
+        query_residency(witness_ntt_verify_kernel<10, 3>, g_occ_verify_field[1]);
+        query_residency(ntt_modq_kernel<9, 3>, g_occ_ntt_field[0]);
+        query_residency(ntt_modq_kernel<10, 3>, g_occ_ntt_field[1]);
+        query_residency(expand_kernel<9, 3>, g_occ_expand_field[0]);
+        query_residency(expand_kernel<10, 3>, g_occ_expand_field[1]);
+        query_residency(statement_kernel<9, 0, 3>, g_occ_statement_field[0]);
+        query_residency(statement_kernel<9, 1, 3>, g_occ_statement_field[1]);
+        query_residency(statement_kernel<10, 0, 3>, g_occ_statement_field[2]);
+        query_residency(statement_kernel<10, 1, 3>, g_occ_statement_field[3]);
     });
+}
+
+// the kernel argument of an instantiation: the registered field's constants for ENC 3, nothing otherwise
+template <int ENC> static field_arg_t<ENC> field_arg(const FieldConsts *fc)
+{
+    if constexpr (ENC == 3) return *fc;
+    else return NoField();
 }
 
 // (grid, full) of a witness launch: all-split for small batches, one workgroup per signature up to the resident capacity,
@@ -1960,7 +2004,7 @@ static void verify_shape(size_t batch, int num_cu, int occ, bool may_split, int 
 
 void launch_shape_witness_ntt_verify(int num_cu, int logn, int enc, size_t batch, int out[4])
 {
-    const int occ = enc == 2 ? g_occ_compact[logn - 9] : g_occ_verify[(logn - 9) * 2 + (enc & 1)];
+    const int occ = enc == 3 ? g_occ_verify_field[logn - 9] : enc == 2 ? g_occ_compact[logn - 9] : g_occ_verify[(logn - 9) * 2 + (enc & 1)];
     int grid;
     size_t full;
     verify_shape(batch, num_cu, occ, true, grid, full);
@@ -1972,16 +2016,18 @@ void launch_shape_witness_ntt_verify(int num_cu, int logn, int enc, size_t batch
 
 hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, int enc, size_t batch,
                                      const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
-                                     uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st)
+                                     uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st, const FieldConsts *fc)
 {
     if (batch == 0) return hipSuccess;
     int grid;
     size_t full;
-    verify_shape(batch, num_cu, g_occ_verify[(logn - 9) * 2 + enc], true, grid, full);
+    verify_shape(batch, num_cu, fc ? g_occ_verify_field[logn - 9] : g_occ_verify[(logn - 9) * 2 + enc], true, grid, full);
 #define FRW_LAUNCH(LOGN, ENC)                                                                                              \
     hipLaunchKernelGGL((witness_ntt_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm, \
-                       (v4u *)wit, (v4u *)inst, status)
-    if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
+                       (v4u *)wit, (v4u *)inst, status, field_arg<ENC>(fc))
+    if (fc && logn == 9) FRW_LAUNCH(9, 3);
+    else if (fc) FRW_LAUNCH(10, 3);
+    else if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
     else if (logn == 9) FRW_LAUNCH(9, 1);
     else if (enc == 0) FRW_LAUNCH(10, 0);
     else FRW_LAUNCH(10, 1);
@@ -1999,23 +2045,26 @@ hipError_t launch_witness_ntt_verify_compact(const Tables *tab, int num_cu, int 
     verify_shape(batch, num_cu, g_occ_compact[logn - 9], true, grid, full);
     if (logn == 9)
         hipLaunchKernelGGL((witness_ntt_verify_kernel<9, 2>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm,
-                           (v4u *)compact, (v4u *)nullptr, status);
+                           (v4u *)compact, (v4u *)nullptr, status, NoField());
     else
         hipLaunchKernelGGL((witness_ntt_verify_kernel<10, 2>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm,
-                           (v4u *)compact, (v4u *)nullptr, status);
+                           (v4u *)compact, (v4u *)nullptr, status, NoField());
     return hipGetLastError();
 }
 
-hipError_t launch_expand(int num_cu, int logn, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st)
+hipError_t launch_expand(int num_cu, int logn, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st,
+                         const FieldConsts *fc)
 {
     if (batch == 0) return hipSuccess;
-    const int grid = resident_grid(batch, num_cu, g_occ_expand[logn - 9], 8);
-    if (logn == 9)
-        hipLaunchKernelGGL((expand_kernel<9>), dim3(grid), dim3(BLOCK), 0, st, batch, (const unsigned char *)compact, (v4u *)wit,
-                           (v4u *)inst);
-    else
-        hipLaunchKernelGGL((expand_kernel<10>), dim3(grid), dim3(BLOCK), 0, st, batch, (const unsigned char *)compact, (v4u *)wit,
-                           (v4u *)inst);
+    const int grid = resident_grid(batch, num_cu, fc ? g_occ_expand_field[logn - 9] : g_occ_expand[logn - 9], 8);
+#define FRW_LAUNCH(LOGN, ENC)                                                                                                       \
+    hipLaunchKernelGGL((expand_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, batch, (const unsigned char *)compact, (v4u *)wit, \
+                       (v4u *)inst, field_arg<ENC>(fc))
+    if (fc && logn == 9) FRW_LAUNCH(9, 3);
+    else if (fc) FRW_LAUNCH(10, 3);
+    else if (logn == 9) FRW_LAUNCH(9, 1);
+    else FRW_LAUNCH(10, 1);
+#undef FRW_LAUNCH
     return hipGetLastError();
 }
 
@@ -2061,14 +2110,19 @@ hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int l
 // one launch: 2 x batch work items (statement, polynomial) strided over the resident grid
 hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
                             const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
-                            int32_t *status, const uint32_t *status_index, hipStream_t st)
+                            int32_t *status, const uint32_t *status_index, hipStream_t st, const FieldConsts *fc)
 {
     if (batch == 0) return hipSuccess;
-    const int grid = resident_grid(batch * 2, num_cu, g_occ_statement[(logn - 9) * 4 + form * 2 + enc]);
+    const int grid = resident_grid(batch * 2, num_cu, fc ? g_occ_statement_field[(logn - 9) * 2 + form]
+                                                         : g_occ_statement[(logn - 9) * 4 + form * 2 + enc]);
 #define FRW_LAUNCH(LOGN, FORM, ENC)                                                                                       \
     hipLaunchKernelGGL((statement_kernel<LOGN, FORM, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, pk, hm, (v4u *)out, \
-                       offs, lead, pre, status, status_index)
-    switch ((logn - 9) * 4 + form * 2 + enc) {
+                       offs, lead, pre, status, status_index, field_arg<ENC>(fc))
+    switch (fc ? 8 + (logn - 9) * 2 + form : (logn - 9) * 4 + form * 2 + enc) {
+    case 8: FRW_LAUNCH(9, 0, 3); break;
+    case 9: FRW_LAUNCH(9, 1, 3); break;
+    case 10: FRW_LAUNCH(10, 0, 3); break;
+    case 11: FRW_LAUNCH(10, 1, 3); break;
     case 0: FRW_LAUNCH(9, 0, 0); break;
     case 1: FRW_LAUNCH(9, 0, 1); break;
     case 2: FRW_LAUNCH(9, 1, 0); break;
@@ -2105,16 +2159,18 @@ hipError_t launch_falcon_verify(const Tables *tab, int num_cu, int logn, int rul
 }
 
 hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, size_t batch, const uint16_t *poly,
-                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st)
+                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st, const FieldConsts *fc)
 {
     if (batch == 0) return hipSuccess;
 #define FRW_LAUNCH(LOGN, ENC)                                                                                  \
     do {                                                                                                       \
-        const int grid = resident_grid(batch, num_cu, g_occ_ntt[(LOGN - 9) * 2 + ENC]);                        \
+        const int grid = resident_grid(batch, num_cu, ENC == 3 ? g_occ_ntt_field[LOGN - 9] : g_occ_ntt[(LOGN - 9) * 2 + (ENC & 1)]); \
         hipLaunchKernelGGL((ntt_modq_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch,           \
-                           poly, (v4u *)wit, ntt_out, status);                                                 \
+                           poly, (v4u *)wit, ntt_out, status, field_arg<ENC>(fc));                             \
     } while (0)
-    if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
+    if (fc && logn == 9) FRW_LAUNCH(9, 3);
+    else if (fc) FRW_LAUNCH(10, 3);
+    else if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
     else if (logn == 9) FRW_LAUNCH(9, 1);
     else if (enc == 0) FRW_LAUNCH(10, 0);
     else FRW_LAUNCH(10, 1);
@@ -2123,7 +2179,7 @@ hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, siz
 }
 
 hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,
-                         int32_t *status, hipStream_t st)
+                         int32_t *status, hipStream_t st, const FieldConsts *fc)
 {
     if (count == 0) return hipSuccess;
     size_t tiles = (count + WAVE - 1) / WAVE;
@@ -2131,8 +2187,9 @@ hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const u
     if (grid > 8192) grid = 8192;
 #define FRW_LAUNCH(KIND)                                                                                         \
     case KIND:                                                                                                   \
-        if (enc == 0) hipLaunchKernelGGL((gadget_kernel<KIND, 0>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status); \
-        else hipLaunchKernelGGL((gadget_kernel<KIND, 1>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status);          \
+        if (fc) hipLaunchKernelGGL((gadget_kernel<KIND, 3>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, *fc); \
+        else if (enc == 0) hipLaunchKernelGGL((gadget_kernel<KIND, 0>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, NoField()); \
+        else hipLaunchKernelGGL((gadget_kernel<KIND, 1>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, NoField()); \
         break
     switch (kind) {
         FRW_LAUNCH(G_LESS_THAN_Q);

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import CompactLayoutStruct, FrwError, LayoutDualStruct, LayoutSchoolbookStruct, LayoutStruct, check, load_library
+from ._lib import CompactLayoutStruct, FieldInfoStruct, FrwError, LayoutDualStruct, LayoutSchoolbookStruct, LayoutStruct, check, load_library
 
 ENC_CANONICAL, ENC_MONTGOMERY, ENC_COMPACT = 0, 1, 2
 ST_OK, ST_COEFF_RANGE, ST_NORM_BOUND, ST_DECODE = 0, 1, 2, 3
@@ -96,6 +96,45 @@ def compact_layout(logn) -> CompactLayout:
     check(load_library().frw_compact_layout(int(logn), C.byref(s)), "frw_compact_layout")
     return CompactLayout(s.logn, s.n, s.bytes_per_signature, s.small_off, s.num_small, s.t_off, s.num_t, s.bits_off, s.num_bit_words,
                          tuple(s.bit_seg_off), s.instance_off, s.num_instance_values, s.status_off)
+
+
+ENC_FIELD_BASE, MAX_FIELDS = 16, 8                 # frw.h FRW_ENC_FIELD_BASE, FRW_MAX_FIELDS
+
+
+@dataclass(frozen=True)
+class FieldInfo:
+    modulus: int
+    one: int            # 2^256 mod p
+    r2: int             # 2^512 mod p
+    ninv32: int         # -p^-1 mod 2^32
+    bits: int
+
+
+def _limbs4(x):
+    return (C.c_uint64 * 4)(*[(int(x) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)])
+
+
+def field_info(p) -> FieldInfo:
+    """frw_field_info: the Montgomery constants of an odd modulus 2^160 < p < 2^255 (no device needed)."""
+    if p < 0 or p >> 256:
+        raise FrwError(-1, "frw_field_info", "the modulus does not fit four limbs")
+    s = FieldInfoStruct()
+    check(load_library().frw_field_info(_limbs4(p), C.byref(s)), "frw_field_info")
+    val = lambda l: sum(int(v) << (64 * i) for i, v in enumerate(l))
+    return FieldInfo(val(s.modulus), val(s.one), val(s.r2), int(s.ninv32), int(s.bits))
+
+
+def expand_field_host(p, logn, compact):
+    """frw_expand_field_host (no device): compact u8[batch, bytes_per_signature] -> (witness u64[batch, W, 4], instance
+    u64[batch, I, 4]) with every element in Montgomery form over the modulus p."""
+    L = layout(logn)
+    compact = np.ascontiguousarray(compact, dtype=np.uint8)
+    batch = compact.shape[0]
+    wit = np.empty((batch, L.num_witness, 4), dtype=np.uint64)
+    inst = np.empty((batch, L.num_instance, 4), dtype=np.uint64)
+    q = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(load_library().frw_expand_field_host(_limbs4(p), logn, batch, q(compact), q(wit), q(inst)), "frw_expand_field_host")
+    return wit, inst
 
 
 def synth_triples(logn, batch, seed=0x46414C434F4E, first_index=0):
@@ -621,6 +660,17 @@ class WitnessEngine:
         check(self._lib.frw_expand_host(logn, batch, p(compact), p(wit), p(inst)), "frw_expand_host")
         return wit, inst
 
+    def field_encoding(self, p):
+        """frw_ctx_field_encoding: registers the modulus p on this context (or finds it) -> the encoding to pass wherever
+        ENC_MONTGOMERY goes in the witness, ntt_modq, gadget and statement calls: elements come out as x * 2^256 mod p."""
+        if p < 0 or p >> 256:
+            raise FrwError(-1, "frw_ctx_field_encoding", "the modulus does not fit four limbs")
+        enc = C.c_int()
+        check(self._lib.frw_ctx_field_encoding(self._ctx, _limbs4(p), C.byref(enc)), "frw_ctx_field_encoding")
+        return int(enc.value)
+
+    expand_field_host = staticmethod(expand_field_host)      # needs no device: also a module-level function
+
     def aggregate(self, items, encoding=ENC_MONTGOMERY, strict=True):
         """Aggregate driver (the reference's falcon-aggregate-sig is an empty stub, so the behaviour
         is defined here): a mixed batch of Falcon-512 / Falcon-1024 statements, each ``(logn, sig, pk, hm)``, is
@@ -717,6 +767,11 @@ class WitnessEngine:
         """compact -> the arkworks witness / instance buffers (FRW_ENC_MONTGOMERY bytes)."""
         check(self._lib.frw_expand_dev(self._ctx, logn, batch, self._ptr(d_compact), self._ptr(d_wit), self._ptr(d_inst),
                                        C.c_void_p(stream)), "frw_expand_dev")
+
+    def expand_field_dev(self, logn, batch, d_compact, encoding, d_wit, d_inst, stream=0):
+        """compact -> the witness / instance buffers over a field registered with field_encoding."""
+        check(self._lib.frw_expand_field_dev(self._ctx, logn, batch, self._ptr(d_compact), encoding, self._ptr(d_wit), self._ptr(d_inst),
+                                             C.c_void_p(stream)), "frw_expand_field_dev")
 
     def launch_shape(self, logn, batch, encoding=ENC_MONTGOMERY):
         """{grid, resident workgroups per CU, CUs, split_signatures} of a witness launch of `batch` signatures

@@ -26,9 +26,11 @@
  *   - a field element is 4 x uint64_t little-endian limbs (ark-ff Fp256 over the BLS12-381
  *     scalar field).  encoding FRW_ENC_MONTGOMERY stores x*2^256 mod p -- byte-identical to
  *     what arkworks keeps in witness_assignment; FRW_ENC_CANONICAL stores x itself.  The reference is generic
- *     over F: PrimeField but instantiates it with this one field everywhere (poly.rs:244, examples/pok_sig.rs:3);
- *     every witness value is an integer below 2^160, so FRW_ENC_CANONICAL and FRW_ENC_COMPACT are field-agnostic
- *     (a host on another >= 161-bit field converts them itself), only FRW_ENC_MONTGOMERY is BLS12-381-specific.
+ *     over F: PrimeField; every witness value is an integer below 2^160, so FRW_ENC_CANONICAL and FRW_ENC_COMPACT
+ *     are field-agnostic, and a field encoding (FRW_ENC_FIELD_BASE + i, frw_ctx_field_encoding) stores x*2^256 mod p
+ *     for any odd p with 2^160 < p < 2^255 in the witness, ntt, gadget and statement calls.  Everything downstream
+ *     that takes buffers rather than an encoding -- the R1CS check, the QAP map, the MSMs, proving and verifying --
+ *     is BLS12-381 only.
  *   - witness:  uint64_t[batch][W][4] in arkworks allocation order (layout: frw_layout()).
  *     instance: uint64_t[batch][I][4], I = 2N+1: [1, pk_ntt[0..N), hm_ntt[0..N)]
  *     (falcon_ntt.rs:63,67; public-input order as in examples/pok_sig.rs:38-45).
@@ -188,6 +190,45 @@ int frw_expand_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact,
  * strict) moves 0.11 MB per Falcon-1024 signature instead of 5.08 MB.  Signatures are independent: callers may split
  * `batch` over threads. */
 int frw_expand_host(int logn, size_t batch, const void *compact, uint64_t *witness, uint64_t *instance);
+
+/* ---- any four-limb scalar field: the Montgomery encoding over a modulus given at run time ------------------------
+ * The reference's circuits are generic over F: PrimeField (falcon_ntt.rs:20).  A host on another field -- BN254,
+ * BLS12-377, Pallas / Vesta, the Jubjub or Curve25519 scalar fields -- registers F's modulus on its context and passes
+ * the encoding it gets back wherever FRW_ENC_MONTGOMERY goes below; the bytes are x * 2^256 mod p, what ark-ff keeps for
+ * an Fp256 over that modulus.
+ *   admissible modulus   odd, 2^160 < p < 2^255 (the ladder values reach 160 bits and must not wrap; the top bit keeps the
+ *                        one conditional subtraction after a Montgomery reduction enough).  Anything else:
+ *                        FRW_E_INVALID_ARG.  Primality is the caller's business: a composite modulus still has
+ *                        well-defined bytes x * 2^256 mod p.
+ *   registry             a context holds up to FRW_MAX_FIELDS moduli; the same modulus twice gives the same encoding,
+ *                        one more distinct modulus FRW_E_INVALID_ARG; the registry lives and dies with the context, and
+ *                        an encoding means nothing on another context.  BLS12-381's own Fr may be registered: its field
+ *                        encoding writes FRW_ENC_MONTGOMERY's bytes.
+ *   accepted by          frw_witness_ntt_verify(_dev), frw_ntt_modq(_dev), frw_gadget(_dev), frw_statement(_dev) and
+ *                        frw_statement_from_bytes(_dev) for every circuit (instance values are below q in all three),
+ *                        frw_diag_launch_shape, frw_expand_field_dev.  Statuses, zero-fill of refused signatures,
+ *                        `strict`, stream ordering and capture safety as for FRW_ENC_MONTGOMERY.
+ *   refused by           (FRW_E_INVALID_ARG) the dual and schoolbook witness calls -- their is_zero multipliers and
+ *                        (-q)^-1 tables are field inverses made by BLS12-381 host code --, frw_aggregate_statement*, and
+ *                        every call when the id was not registered on that context.
+ * frw_field_info needs no device: the constants ark-ff's FpParameters would list for the modulus. */
+#define FRW_ENC_FIELD_BASE 16          /* encodings 16 .. 16 + FRW_MAX_FIELDS - 1: a field registered on the context */
+#define FRW_MAX_FIELDS     8
+typedef struct frw_field_info {
+    uint64_t modulus[4];               /* p, little-endian limbs */
+    uint64_t one[4];                   /* 2^256 mod p: what ark-ff stores for F::one() */
+    uint64_t r2[4];                    /* 2^512 mod p */
+    uint32_t ninv32;                   /* -p^-1 mod 2^32 */
+    uint32_t bits;                     /* bit length of p */
+} frw_field_info_t;
+int frw_field_info(const uint64_t modulus[4], frw_field_info_t *out);
+/* register `modulus` on the context, or look it up: *encoding = FRW_ENC_FIELD_BASE + its index */
+int frw_ctx_field_encoding(frw_ctx *ctx, const uint64_t modulus[4], int *encoding);
+/* frw_expand_dev / frw_expand_host over a registered field / a modulus: the bytes of the direct call with that encoding */
+int frw_expand_field_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact, int encoding,
+                         uint64_t *d_witness, uint64_t *d_instance, void *stream);
+int frw_expand_field_host(const uint64_t modulus[4], int logn, size_t batch, const void *compact,
+                          uint64_t *witness, uint64_t *instance);
 
 /* ---- the signed-split variant: FalconDualNTTVerificationCircuit (circuits/falcon_dual_ntt.rs:26-132) -----------
  * Same statement, signature and v split into non-negative (pos, neg) parts (gadgets/dual_poly.rs:15-31), four

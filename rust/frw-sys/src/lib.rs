@@ -82,6 +82,20 @@ pub struct frw_compact_layout_t {
     pub status_off: u64,
 }
 
+/// encodings 16 .. 16 + FRW_MAX_FIELDS - 1: a field registered on the context (`frw_ctx_field_encoding`)
+pub const FRW_ENC_FIELD_BASE: c_int = 16;
+pub const FRW_MAX_FIELDS: c_int = 8;
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_field_info_t {
+    pub modulus: [u64; 4],
+    pub one: [u64; 4],
+    pub r2: [u64; 4],
+    pub ninv32: u32,
+    pub bits: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct frw_msm_info_t {
@@ -227,6 +241,12 @@ extern "C" {
                           d_instance: *mut u64, stream: *mut c_void) -> c_int;
     pub fn frw_expand_host(logn: c_int, batch: usize, compact: *const c_void, witness: *mut u64,
                            instance: *mut u64) -> c_int;
+    pub fn frw_field_info(modulus: *const u64, out: *mut frw_field_info_t) -> c_int;
+    pub fn frw_ctx_field_encoding(ctx: *mut frw_ctx, modulus: *const u64, encoding: *mut c_int) -> c_int;
+    pub fn frw_expand_field_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_compact: *const c_void, encoding: c_int,
+                                d_witness: *mut u64, d_instance: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn frw_expand_field_host(modulus: *const u64, logn: c_int, batch: usize, compact: *const c_void, witness: *mut u64,
+                                 instance: *mut u64) -> c_int;
     pub fn frw_layout_dual(logn: c_int, out: *mut frw_layout_dual_t) -> c_int;
     pub fn frw_witness_dual_ntt_verify_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_sig: *const u16,
                                            d_pk: *const u16, d_hm: *const u16, encoding: c_int, d_witness: *mut u64,

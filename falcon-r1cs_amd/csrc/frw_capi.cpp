@@ -85,19 +85,27 @@ bool bad_common(const frw_ctx *ctx, int logn, int encoding)
     return !ctx || (logn != 9 && logn != 10) || (encoding != FRW_ENC_CANONICAL && encoding != FRW_ENC_MONTGOMERY);
 }
 
-// The calls that also take a field registered on the context (FRW_ENC_FIELD_BASE + i): *fc = its constants, or null for the two
-// BLS12-381 encodings.  An id that this context did not hand out is refused like any other unknown encoding.
-bool bad_field_common(const frw_ctx *ctx, int logn, int encoding, const frw::FieldConsts **fc)
+// An encoding of the ABI as the kernels know it: canonical, Montgomery and compact as they are, a field registered on the context
+// (FRW_ENC_FIELD_BASE + i) as ENC 3 with its constants.  False: not an encoding; an id that this context did not hand out is none.
+bool kernel_encoding(const frw_ctx *ctx, int encoding, frw::KernelEnc *ke)
 {
-    *fc = nullptr;
-    if (ctx && encoding >= FRW_ENC_FIELD_BASE && encoding < FRW_ENC_FIELD_BASE + ctx->num_fields) {
-        *fc = &ctx->fields[encoding - FRW_ENC_FIELD_BASE];
-        return logn != 9 && logn != 10;
-    }
-    return bad_common(ctx, logn, encoding);
+    *ke = frw::KernelEnc(encoding);
+    if (encoding == FRW_ENC_CANONICAL || encoding == FRW_ENC_MONTGOMERY || encoding == FRW_ENC_COMPACT) return true;
+    if (!ctx || encoding < FRW_ENC_FIELD_BASE || encoding >= FRW_ENC_FIELD_BASE + ctx->num_fields) return false;
+    *ke = frw::KernelEnc(3, &ctx->fields[encoding - FRW_ENC_FIELD_BASE]);
+    return true;
 }
-// what the launchers take as `enc` beside fc (they do not look at it when fc is set)
-int kernel_enc(int encoding, const frw::FieldConsts *fc) { return fc ? FRW_ENC_MONTGOMERY : encoding; }
+// the calls that take the two BLS12-381 encodings or a registered field
+bool bad_field_common(const frw_ctx *ctx, int logn, int encoding, frw::KernelEnc *ke)
+{
+    return !ctx || (logn != 9 && logn != 10) || !kernel_encoding(ctx, encoding, ke) || ke->enc == FRW_ENC_COMPACT;
+}
+// The encodings a witness circuit takes.  NTT: canonical, Montgomery, compact, a registered field; dual and schoolbook: canonical and
+// Montgomery only (no compact form, and their field inverses are made by BLS12-381 host code).
+bool bad_witness(const frw_ctx *ctx, int circuit, int logn, int encoding, frw::KernelEnc *ke)
+{
+    return !ctx || (logn != 9 && logn != 10) || !kernel_encoding(ctx, encoding, ke) || (circuit != FRW_CIRCUIT_NTT && ke->enc > FRW_ENC_MONTGOMERY);
+}
 
 
 // frw_layout*: the segment table of a circuit's witness laid end to end.  The counts are frw::circuit_shape's; the table has to add up
@@ -226,32 +234,15 @@ int frw_ctx_trim(frw_ctx *ctx)
     return FRW_OK;
 }
 
-int frw_witness_ntt_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
-                               const uint16_t *d_hm, int encoding, uint64_t *d_witness, uint64_t *d_instance,
-                               int32_t *d_status, void *stream)
-{
-    if (encoding == FRW_ENC_COMPACT)       // d_witness = compact buffer, d_instance unused (may be NULL)
-        return frw_witness_ntt_verify_compact_dev(ctx, logn, batch, d_sig, d_pk, d_hm, d_witness, d_status, stream);
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
-    if (batch == 0) return FRW_OK;
-    if (!d_sig || !d_pk || !d_hm || !d_witness || !d_instance || !d_status) return FRW_E_INVALID_ARG;
-    FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_sig, d_pk, d_hm,
-                                           d_witness, d_instance, d_status, (hipStream_t)stream, fc));
-    return FRW_OK;
-}
-
 int frw_ntt_modq_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_poly, int encoding, uint64_t *d_witness,
                      uint16_t *d_ntt_out, int32_t *d_status, void *stream)
 {
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_field_common(ctx, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!d_poly || !d_witness || !d_ntt_out || !d_status) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_poly, d_witness, d_ntt_out,
-                                 d_status, (hipStream_t)stream, fc));
+    FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, ke, batch, d_poly, d_witness, d_ntt_out, d_status, (hipStream_t)stream));
     return FRW_OK;
 }
 
@@ -278,21 +269,33 @@ hipError_t stage_rows(std::initializer_list<const uint16_t *> src, size_t n, siz
     }
     return hipMemcpyAsync(d_in, stage, (size_t)(h - stage), hipMemcpyHostToDevice, st);
 }
-// the witness kernel of a circuit (FRW_ENC_COMPACT: the NTT circuit's compact form; d_witness is the compact buffer, d_instance unused)
-hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, int encoding, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
-                          const uint16_t *d_hm, void *d_witness, uint64_t *d_instance, int32_t *d_status, hipStream_t st,
-                          const frw::FieldConsts *fc = nullptr)
+// the witness kernel of a circuit (the NTT circuit's compact form: d_witness is the compact buffer, d_instance unused)
+hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, frw::KernelEnc ke, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
+                          const uint16_t *d_hm, void *d_witness, uint64_t *d_instance, int32_t *d_status, hipStream_t st)
 {
     if (circuit == FRW_CIRCUIT_SCHOOLBOOK)
-        return frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
+        return frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, ke.enc, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
                                                      d_instance, d_status, st);
     if (circuit == FRW_CIRCUIT_DUAL_NTT)
-        return frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
+        return frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, ke.enc, batch, d_sig, d_pk, d_hm, (uint64_t *)d_witness,
                                                    d_instance, d_status, st);
-    if (encoding == FRW_ENC_COMPACT)
-        return frw::launch_witness_ntt_verify_compact(ctx->d_tables, ctx->num_cu, logn, batch, d_sig, d_pk, d_hm, d_witness, d_status, st);
-    return frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), batch, d_sig, d_pk, d_hm,
-                                          (uint64_t *)d_witness, d_instance, d_status, st, fc);
+    return frw::launch_witness_ntt_verify(ctx->d_tables, ctx->num_cu, logn, ke, batch, d_sig, d_pk, d_hm, d_witness, d_instance, d_status, st);
+}
+
+// The device-buffer witness calls of the three circuits: one kernel launch on the caller's stream.  The compact form's d_witness is the
+// compact buffer (16-byte aligned), its d_instance is unused and may be NULL.
+int witness_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk, const uint16_t *d_hm,
+                int encoding, void *d_witness, uint64_t *d_instance, int32_t *d_status, void *stream)
+{
+    frw::KernelEnc ke;
+    if (bad_witness(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    const bool compact = ke.enc == FRW_ENC_COMPACT;
+    if (!d_sig || !d_pk || !d_hm || !d_witness || (!d_instance && !compact) || !d_status) return FRW_E_INVALID_ARG;
+    if (compact && ((uintptr_t)d_witness & 15)) return FRW_E_INVALID_ARG;
+    FRW_HIP(hipSetDevice(ctx->device));
+    FRW_HIP(launch_witness(ctx, circuit, logn, ke, batch, d_sig, d_pk, d_hm, d_witness, d_instance, d_status, (hipStream_t)stream));
+    return FRW_OK;
 }
 
 // The host-buffer witness calls of the three circuits.  The pass loop is frw::host_passes (frw_arena.h); this says what a pass is: the
@@ -303,12 +306,9 @@ hipError_t launch_witness(const frw_ctx *ctx, int circuit, int logn, int encodin
 int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
                  const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance, int32_t *status, int strict)
 {
-    const bool compact = circuit == FRW_CIRCUIT_NTT && encoding == FRW_ENC_COMPACT;    // `witness` = compact buffer, `instance` unused
-    // a field registered on the context: the NTT circuit only (the other two need field inverses made by BLS12-381 host code)
-    const frw::FieldConsts *fc = nullptr;
-    if (compact ? bad_common(ctx, logn, FRW_ENC_MONTGOMERY)
-                : circuit == FRW_CIRCUIT_NTT ? bad_field_common(ctx, logn, encoding, &fc) : bad_common(ctx, logn, encoding))
-        return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_witness(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
+    const bool compact = ke.enc == FRW_ENC_COMPACT;                                     // `witness` = compact buffer, `instance` unused
     if (batch == 0) return FRW_OK;
     if (!sig || !pk || !hm || !witness || (!instance && !compact) || !status) return FRW_E_INVALID_ARG;
     const frw::CircuitShape shape = frw::circuit_shape(circuit, logn);
@@ -329,8 +329,8 @@ int witness_host(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16
         [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
             const uint16_t *d_in = (const uint16_t *)(d + o_in);
             FRW_HIP(stage_rows({sig, pk, hm}, n, lo, cnt, stage, d + o_in, st));
-            FRW_HIP(launch_witness(ctx, circuit, logn, encoding, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, d + o_wit,
-                                   (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), st, fc));
+            FRW_HIP(launch_witness(ctx, circuit, logn, ke, cnt, d_in, d_in + cnt * n, d_in + 2 * cnt * n, d + o_wit,
+                                   (uint64_t *)(d + o_inst), (int32_t *)(d + o_st), st));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -344,6 +344,13 @@ int frw_witness_ntt_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t 
     return witness_host(ctx, FRW_CIRCUIT_NTT, logn, batch, sig, pk, hm, encoding, witness, instance, status, strict);
 }
 
+int frw_witness_ntt_verify_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
+                               const uint16_t *d_hm, int encoding, uint64_t *d_witness, uint64_t *d_instance,
+                               int32_t *d_status, void *stream)
+{
+    return witness_dev(ctx, FRW_CIRCUIT_NTT, logn, batch, d_sig, d_pk, d_hm, encoding, d_witness, d_instance, d_status, stream);
+}
+
 int frw_witness_dual_ntt_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
                                 const uint16_t *hm, int encoding, uint64_t *witness, uint64_t *instance,
                                 int32_t *status, int strict)
@@ -355,13 +362,7 @@ int frw_witness_dual_ntt_verify_dev(frw_ctx *ctx, int logn, size_t batch, const 
                                     const uint16_t *d_hm, int encoding, uint64_t *d_witness, uint64_t *d_instance,
                                     int32_t *d_status, void *stream)
 {
-    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;
-    if (batch == 0) return FRW_OK;
-    if (!d_sig || !d_pk || !d_hm || !d_witness || !d_instance || !d_status) return FRW_E_INVALID_ARG;
-    FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_witness_dual_ntt_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig,
-                                                d_pk, d_hm, d_witness, d_instance, d_status, (hipStream_t)stream));
-    return FRW_OK;
+    return witness_dev(ctx, FRW_CIRCUIT_DUAL_NTT, logn, batch, d_sig, d_pk, d_hm, encoding, d_witness, d_instance, d_status, stream);
 }
 
 int frw_compact_layout(int logn, frw_compact_layout_t *out)
@@ -389,13 +390,7 @@ int frw_compact_layout(int logn, frw_compact_layout_t *out)
 int frw_witness_ntt_verify_compact_dev(frw_ctx *ctx, int logn, size_t batch, const uint16_t *d_sig, const uint16_t *d_pk,
                                        const uint16_t *d_hm, void *d_compact, int32_t *d_status, void *stream)
 {
-    if (bad_common(ctx, logn, FRW_ENC_MONTGOMERY)) return FRW_E_INVALID_ARG;
-    if (batch == 0) return FRW_OK;
-    if (!d_sig || !d_pk || !d_hm || !d_compact || !d_status || ((uintptr_t)d_compact & 15)) return FRW_E_INVALID_ARG;
-    FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_witness_ntt_verify_compact(ctx->d_tables, ctx->num_cu, logn, batch, d_sig, d_pk, d_hm, d_compact,
-                                                   d_status, (hipStream_t)stream));
-    return FRW_OK;
+    return witness_dev(ctx, FRW_CIRCUIT_NTT, logn, batch, d_sig, d_pk, d_hm, FRW_ENC_COMPACT, d_compact, nullptr, d_status, stream);
 }
 
 int frw_expand_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact, uint64_t *d_witness, uint64_t *d_instance,
@@ -405,7 +400,7 @@ int frw_expand_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact, 
     if (batch == 0) return FRW_OK;
     if (!d_compact || !d_witness || !d_instance || ((uintptr_t)d_compact & 15)) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_expand(ctx->num_cu, logn, batch, d_compact, d_witness, d_instance, (hipStream_t)stream));
+    FRW_HIP(frw::launch_expand(ctx->num_cu, logn, FRW_ENC_MONTGOMERY, batch, d_compact, d_witness, d_instance, (hipStream_t)stream));
     return FRW_OK;
 }
 
@@ -564,12 +559,12 @@ int frw_ctx_field_encoding(frw_ctx *ctx, const uint64_t modulus[4], int *encodin
 int frw_expand_field_dev(frw_ctx *ctx, int logn, size_t batch, const void *d_compact, int encoding, uint64_t *d_witness,
                          uint64_t *d_instance, void *stream)
 {
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, logn, encoding, &fc) || !fc) return FRW_E_INVALID_ARG;          // a registered field, nothing else
+    frw::KernelEnc ke;
+    if (bad_field_common(ctx, logn, encoding, &ke) || !ke.fc) return FRW_E_INVALID_ARG;       // a registered field, nothing else
     if (batch == 0) return FRW_OK;
     if (!d_compact || !d_witness || !d_instance || ((uintptr_t)d_compact & 15)) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_expand(ctx->num_cu, logn, batch, d_compact, d_witness, d_instance, (hipStream_t)stream, fc));
+    FRW_HIP(frw::launch_expand(ctx->num_cu, logn, ke, batch, d_compact, d_witness, d_instance, (hipStream_t)stream));
     return FRW_OK;
 }
 
@@ -592,10 +587,10 @@ int frw_expand_field_host(const uint64_t modulus[4], int logn, size_t batch, con
 
 int frw_diag_launch_shape(frw_ctx *ctx, int logn, int encoding, size_t batch, int32_t out[4])
 {
-    const bool field = ctx && encoding >= FRW_ENC_FIELD_BASE && encoding < FRW_ENC_FIELD_BASE + ctx->num_fields;
-    if (!ctx || !out || (logn != 9 && logn != 10) || ((encoding < 0 || encoding > 2) && !field)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (!out || bad_witness(ctx, FRW_CIRCUIT_NTT, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     int o[4];
-    frw::launch_shape_witness_ntt_verify(ctx->num_cu, logn, field ? 3 : encoding, batch, o);
+    frw::launch_shape_witness_ntt_verify(ctx->num_cu, logn, ke, batch, o);
     for (int i = 0; i < 4; i++) out[i] = o[i];
     return FRW_OK;
 }
@@ -621,13 +616,7 @@ int frw_witness_schoolbook_verify_dev(frw_ctx *ctx, int logn, size_t batch, cons
                                       const uint16_t *d_hm, int encoding, uint64_t *d_witness, uint64_t *d_instance,
                                       int32_t *d_status, void *stream)
 {
-    if (bad_common(ctx, logn, encoding)) return FRW_E_INVALID_ARG;       // (no compact form of this circuit)
-    if (batch == 0) return FRW_OK;
-    if (!d_sig || !d_pk || !d_hm || !d_witness || !d_instance || !d_status) return FRW_E_INVALID_ARG;
-    FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_witness_schoolbook_verify(ctx->d_tables, ctx->num_cu, logn, encoding, batch, d_sig,
-                                                  d_pk, d_hm, d_witness, d_instance, d_status, (hipStream_t)stream));
-    return FRW_OK;
+    return witness_dev(ctx, FRW_CIRCUIT_SCHOOLBOOK, logn, batch, d_sig, d_pk, d_hm, encoding, d_witness, d_instance, d_status, stream);
 }
 
 int frw_witness_schoolbook_verify(frw_ctx *ctx, int logn, size_t batch, const uint16_t *sig, const uint16_t *pk,
@@ -640,8 +629,8 @@ int frw_witness_schoolbook_verify(frw_ctx *ctx, int logn, size_t batch, const ui
 int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int encoding, uint64_t *witness,
                  uint16_t *ntt_out, int32_t *status)
 {
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_field_common(ctx, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     if (!poly || !witness || !ntt_out || !status) return FRW_E_INVALID_ARG;
     // as witness_host: one slot and one stream for a batch that fits a chunk, else two
@@ -657,8 +646,8 @@ int frw_ntt_modq(frw_ctx *ctx, int logn, size_t batch, const uint16_t *poly, int
         {{witness, o_wit, wbytes}, {ntt_out, o_out, n * 2}, {status, o_st, sizeof(int32_t)}},
         [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
             FRW_HIP(stage_rows({poly}, n, lo, cnt, stage, d + o_in, st));
-            FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, kernel_enc(encoding, fc), cnt, (const uint16_t *)(d + o_in),
-                                         (uint64_t *)(d + o_wit), (uint16_t *)(d + o_out), (int32_t *)(d + o_st), st, fc));
+            FRW_HIP(frw::launch_ntt_modq(ctx->d_tables, ctx->num_cu, logn, ke, cnt, (const uint16_t *)(d + o_in),
+                                         (uint64_t *)(d + o_wit), (uint16_t *)(d + o_out), (int32_t *)(d + o_st), st));
             return FRW_OK;
         });
 }
@@ -746,9 +735,9 @@ int frw_prepare_inputs(frw_ctx *ctx, int logn, size_t batch, const uint8_t *pk_b
 // ---- the verifier's statement: instance_assignment from (pk, hm), or from the key's and the message's bytes; no signature -------------
 namespace {
 // (a registered field is accepted for every circuit: the instance values are below q in all three)
-bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding, const frw::FieldConsts **fc)
+bool bad_statement(const frw_ctx *ctx, int circuit, int logn, int encoding, frw::KernelEnc *ke)
 {
-    return bad_field_common(ctx, logn, encoding, fc) || !frw::known_circuit(circuit);
+    return bad_field_common(ctx, logn, encoding, ke) || !frw::known_circuit(circuit);
 }
 // the schoolbook circuit's public inputs are the coefficients themselves (falcon_schoolbook.rs:66-83), the NTT circuits' their transforms
 int statement_form(int circuit) { return circuit == FRW_CIRCUIT_SCHOOLBOOK ? 1 : 0; }
@@ -758,13 +747,13 @@ constexpr size_t STATEMENT_CHUNK = 4096;          // statements of one pass of t
 int frw_statement_dev(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *d_pk, const uint16_t *d_hm, int encoding,
                       uint64_t *d_instance, int32_t *d_status, void *stream)
 {
-    const frw::FieldConsts *fc;
-    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_statement(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (!d_pk || !d_hm || !d_instance || !d_status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), batch, d_pk, d_hm,
-                                  d_instance, nullptr, 1, nullptr, d_status, nullptr, (hipStream_t)stream, fc));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), ke, batch, d_pk, d_hm,
+                                  d_instance, nullptr, 1, nullptr, d_status, nullptr, (hipStream_t)stream));
     return FRW_OK;
 }
 
@@ -778,8 +767,8 @@ int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t bat
                                  const uint8_t *d_msgs, const uint64_t *d_msg_off, int encoding, uint64_t *d_instance, int32_t *d_status,
                                  void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    const frw::FieldConsts *fc;
-    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_statement(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (!d_pk_bytes || !d_nonces || !d_msgs || !d_msg_off || !d_instance || !d_status || !d_workspace) return FRW_E_INVALID_ARG;
     if (((uintptr_t)d_workspace & 15) || workspace_bytes < frw_statement_workspace_bytes(logn, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
@@ -788,16 +777,16 @@ int frw_statement_from_bytes_dev(frw_ctx *ctx, int circuit, int logn, size_t bat
     FRW_HIP(hipSetDevice(ctx->device));
     FRW_HIP(frw::launch_decode_public_keys(logn, batch, d_pk_bytes, ws.pk, ws.decode_status, st));
     FRW_HIP(frw::launch_hash_to_point(logn, batch, d_nonces, d_msgs, d_msg_off, ws.hm, st));
-    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), batch, ws.pk, ws.hm,
-                                  d_instance, nullptr, 1, ws.decode_status, d_status, nullptr, st, fc));
+    FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), ke, batch, ws.pk, ws.hm,
+                                  d_instance, nullptr, 1, ws.decode_status, d_status, nullptr, st));
     return FRW_OK;
 }
 
 int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint16_t *pk, const uint16_t *hm, int encoding,
                   uint64_t *instance, int32_t *status, int strict)
 {
-    const frw::FieldConsts *fc;
-    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_statement(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (!pk || !hm || !instance || !status) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     const size_t n = (size_t)1 << logn, ibytes = frw::circuit_shape(circuit, logn).num_instance * 32, chunk = std::min(batch, STATEMENT_CHUNK);
@@ -810,8 +799,8 @@ int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint1
         [&](char *d, char *stage, size_t lo, size_t cnt, hipStream_t st) -> int {
             const uint16_t *d_in = (const uint16_t *)(d + o_in);
             FRW_HIP(stage_rows({pk, hm}, n, lo, cnt, stage, d + o_in, st));
-            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), cnt, d_in,
-                                          d_in + cnt * n, (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st, fc));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), ke, cnt, d_in,
+                                          d_in + cnt * n, (uint64_t *)(d + o_inst), nullptr, 1, nullptr, (int32_t *)(d + o_st), nullptr, st));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -820,8 +809,8 @@ int frw_statement(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint1
 int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, const uint8_t *pk_bytes, const uint8_t *nonces,
                              const uint8_t *msgs, const uint64_t *msg_off, int encoding, uint64_t *instance, int32_t *status, int strict)
 {
-    const frw::FieldConsts *fc;
-    if (bad_statement(ctx, circuit, logn, encoding, &fc)) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_statement(ctx, circuit, logn, encoding, &ke)) return FRW_E_INVALID_ARG;
     if (!pk_bytes || !nonces || !msg_off || !instance || !status) return FRW_E_INVALID_ARG;
     if (!frw::message_offsets_ok(msgs, msg_off, batch)) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
@@ -840,8 +829,8 @@ int frw_statement_from_bytes(frw_ctx *ctx, int circuit, int logn, size_t batch, 
             const frw::StatementBufs ws = frw::statement_layout(d + o_ws, logn, cnt);
             FRW_HIP(frw::launch_decode_public_keys(logn, cnt, in.d_pk(d), ws.pk, ws.decode_status, st));
             FRW_HIP(frw::launch_hash_to_point(logn, cnt, in.d_second(d), in.d_msgs(d), in.d_off(d), ws.hm, st));
-            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), kernel_enc(encoding, fc), cnt, ws.pk, ws.hm,
-                                          (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st, fc));
+            FRW_HIP(frw::launch_statement(ctx->d_tables, ctx->num_cu, logn, statement_form(circuit), ke, cnt, ws.pk, ws.hm,
+                                          (uint64_t *)(d + o_inst), nullptr, 1, ws.decode_status, (int32_t *)(d + o_st), nullptr, st));
             return FRW_OK;
         });
     return strict_verdict(rc, strict, status, batch);
@@ -1381,20 +1370,20 @@ int frw_gadget_block_len(int kind)
 int frw_gadget_dev(frw_ctx *ctx, int kind, size_t count, const void *d_a, const uint64_t *d_b, int encoding,
                    uint64_t *d_out, int32_t *d_status, void *stream)
 {
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, 10, encoding, &fc) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_field_common(ctx, 10, encoding, &ke) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
     if (count == 0) return FRW_OK;
     if (!d_a || !d_out || (kind == FRW_G_ADD_MOD && !d_b)) return FRW_E_INVALID_ARG;
     FRW_HIP(hipSetDevice(ctx->device));
-    FRW_HIP(frw::launch_gadget(kind, kernel_enc(encoding, fc), count, d_a, d_b, d_out, d_status, (hipStream_t)stream, fc));
+    FRW_HIP(frw::launch_gadget(kind, ke, count, d_a, d_b, d_out, d_status, (hipStream_t)stream));
     return FRW_OK;
 }
 
 int frw_gadget(frw_ctx *ctx, int kind, size_t count, const void *a, const uint64_t *b, int encoding, uint64_t *out,
                int32_t *status)
 {
-    const frw::FieldConsts *fc;
-    if (bad_field_common(ctx, 10, encoding, &fc) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
+    frw::KernelEnc ke;
+    if (bad_field_common(ctx, 10, encoding, &ke) || frw_gadget_block_len(kind) < 0) return FRW_E_INVALID_ARG;
     if (count == 0) return FRW_OK;
     if (!a || !out || (kind == FRW_G_ADD_MOD && !b)) return FRW_E_INVALID_ARG;
     frw::HostArena &A = ctx->arena;
@@ -1414,7 +1403,7 @@ int frw_gadget(frw_ctx *ctx, int kind, size_t count, const void *a, const uint64
     hipStream_t st = A.compute;
     FRW_HIP(hipMemcpyAsync(d_a, a, in_bytes, hipMemcpyHostToDevice, st));
     if (b_bytes) FRW_HIP(hipMemcpyAsync(d_b, b, b_bytes, hipMemcpyHostToDevice, st));
-    FRW_HIP(frw::launch_gadget(kind, kernel_enc(encoding, fc), count, d_a, b_bytes ? d_b : nullptr, d_out, d_st, st, fc));
+    FRW_HIP(frw::launch_gadget(kind, ke, count, d_a, b_bytes ? d_b : nullptr, d_out, d_st, st));
     FRW_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     if (status) FRW_HIP(hipMemcpyAsync(status, d_st, count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FRW_HIP(hipStreamSynchronize(st));

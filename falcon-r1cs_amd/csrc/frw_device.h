@@ -67,18 +67,21 @@ void record_error(const char *fmt, ...);
 void init_launch_config();
 // q^-1 and (-q)^-1 in Fr for Tables::sb_qinv / sb_nqinv (frw_r1cs.cpp, which has the field inversion): [canonical | Montgomery][8]
 void schoolbook_inverses(uint32_t qinv[2][8], uint32_t nqinv[2][8]);
-hipError_t launch_witness_ntt_verify_compact(const Tables *tab, int num_cu, int logn, size_t batch,
-                                             const uint16_t *sig, const uint16_t *pk, const uint16_t *hm, void *compact,
-                                             int32_t *status, hipStream_t st);
-// The launchers that take `fc`: null = the encoding `enc` over BLS12-381's Fr (the hard-wired instantiations); else Montgomery form over
-// the field whose constants it points to (host memory; they travel by value as a kernel argument), `enc` is not looked at.
-hipError_t launch_expand(int num_cu, int logn, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st,
-                         const FieldConsts *fc = nullptr);
-// grid / resident workgroups per CU / split flag the witness launcher would use for `batch` (diagnostics for bench.py); enc 3 = a field's
-void launch_shape_witness_ntt_verify(int num_cu, int logn, int enc, size_t batch, int out[4]);
-hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, int enc, size_t batch,
+// The encoding a kernel is instantiated over (its ENC): 0 canonical, 1 Montgomery, 2 the compact record -- all three over BLS12-381's Fr,
+// hard-wired -- or 3: Montgomery form over the field whose constants `fc` points to (host memory; they travel by value as a kernel
+// argument).  The launchers that take one refuse an ENC their kernel has no instantiation for (hipErrorInvalidValue).
+struct KernelEnc {
+    int enc;
+    const FieldConsts *fc;      // ENC 3 only
+    KernelEnc(int enc_ = 1, const FieldConsts *fc_ = nullptr) : enc(enc_), fc(fc_) {}
+};
+hipError_t launch_expand(int num_cu, int logn, KernelEnc ke, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st);
+// grid / resident workgroups per CU / CUs / split signatures the witness launcher uses for `batch` (diagnostics for bench.py)
+void launch_shape_witness_ntt_verify(int num_cu, int logn, KernelEnc ke, size_t batch, int out[4]);
+// ENC 2: `wit` is the compact buffer, `inst` is not used
+hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, KernelEnc ke, size_t batch,
                                      const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
-                                     uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st, const FieldConsts *fc = nullptr);
+                                     void *wit, uint64_t *inst, int32_t *status, hipStream_t st);
 hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int logn, int enc,
                                           size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
                                           uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st);
@@ -86,23 +89,23 @@ hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int log
 hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int logn, int enc,
                                             size_t batch, const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
                                             uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st);
-hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, size_t batch, const uint16_t *poly,
-                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st, const FieldConsts *fc = nullptr);
+hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, KernelEnc ke, size_t batch, const uint16_t *poly,
+                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st);
 // the verifier's statement (statement_kernel): form 0 = [1, NTT(pk), NTT(hm)], 1 = [1, pk, hm].  offs null: statement s at element
 // s (2 N + 1) of `out`; else at 1 + offs[3 s + 1] (R1csAggSet::offs).  lead 1: every statement writes its own leading one; 0: none; 2:
 // none, and the launch writes the aggregate's one constant at element 0.  pre (may be null): statuses that refuse a statement before its
 // coefficients are looked at.  status_index (may be null): where statement s's status word goes.
-hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
+hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, KernelEnc ke, size_t batch, const uint16_t *pk,
                             const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
-                            int32_t *status, const uint32_t *status_index, hipStream_t st, const FieldConsts *fc = nullptr);
+                            int32_t *status, const uint32_t *status_index, hipStream_t st);
 // Falcon verification without a witness (falcon_verify_kernel): status[s] = FRW_ST_*, norm[s] (norm may be null) = the squared norm
 // of v || sig under `rule` (0 = the circuits' rule, the witness kernels' status word; 1 = the specification's), all ones where the
 // signature was refused before a norm exists.  pre0, pre1 (may be null): statuses that refuse a signature before its coefficients are read.
 hipError_t launch_falcon_verify(const Tables *tab, int num_cu, int logn, int rule, size_t batch, const uint16_t *sig,
                                 const uint16_t *pk, const uint16_t *hm, const int32_t *pre0, const int32_t *pre1,
                                 int32_t *status, uint64_t *norm, hipStream_t st);
-hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,
-                         int32_t *status, hipStream_t st, const FieldConsts *fc = nullptr);
+hipError_t launch_gadget(int kind, KernelEnc ke, size_t count, const void *a, const uint64_t *b, uint64_t *out,
+                         int32_t *status, hipStream_t st);
 hipError_t launch_hash_to_point(int logn, size_t batch, const uint8_t *nonces, const uint8_t *msgs, const uint64_t *msg_off,
                                 uint16_t *hm, hipStream_t st);
 hipError_t launch_decode_public_keys(int logn, size_t batch, const uint8_t *pk_bytes, uint16_t *pk, int32_t *status, hipStream_t st);

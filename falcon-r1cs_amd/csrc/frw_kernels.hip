@@ -36,6 +36,7 @@
 #include <mutex>
 #include "frw_device.h"
 #include "frw_field.h"
+#include "frw_launch.h"
 
 namespace frw {
 
@@ -674,7 +675,7 @@ __device__ __forceinline__ void emit_tile_generic(v4u *__restrict__ out, const v
 // each -- {instance, S0, S1, S2}, {S5}, {S6, S7, status}, {S3}, {S4} -- strided over the grid the same way, each
 // recomputing the part of the clear arithmetic it needs (a single Falcon-1024 witness: 167 us -> ~60 us).
 // ------------------------------------------------------------------------------------------------
-constexpr int PARTS = 5;
+// (PARTS = 5, the work items of a split signature: frw_launch.h, beside the launch shape that counts them)
 
 // ------------------------------------------------------------------------------------------------
 // LDS carve-up of one workgroup.  The NTT-domain arrays are dead once the small segments are written and the ladder
@@ -1890,95 +1891,57 @@ hipError_t launch_write_stream(void *buf, size_t bytes, size_t slab_bytes, int n
 // ------------------------------------------------------------------------------------------------
 // launchers (called from frw_capi.cpp)
 // ------------------------------------------------------------------------------------------------
-// Persistent grid: as many workgroups as the device keeps resident (LDS-limited: 2-3 per CU), each
-// striding over the batch.  Residency is asked from the runtime once per kernel instantiation.
-// Filled exactly once per process (std::call_once in init_launch_config, which every context creation calls before
-// any launch), read-only afterwards: contexts on several devices / threads share it safely.
-static int g_occ_verify[4], g_occ_dual[4], g_occ_ntt[4], g_occ_schoolbook[4];   // resident workgroups per CU, [(LOGN-9)*2 + ENC]
-static int g_occ_compact[2], g_occ_expand[2];                  // [LOGN - 9]
-static int g_occ_statement[8];                                 // [(LOGN - 9) * 4 + FORM * 2 + ENC]
-static int g_occ_falcon_verify[4];                             // [(LOGN - 9) * 2 + RULE]
-// the ENC = 3 instantiations (a field registered on the context): [LOGN - 9], the statement's [(LOGN - 9) * 2 + FORM]
-static int g_occ_verify_field[2], g_occ_ntt_field[2], g_occ_expand_field[2], g_occ_statement_field[4];
-static std::once_flag g_occ_once;
+// Persistent grid: as many workgroups as the device keeps resident (LDS-limited: 2-3 per CU), each striding over the batch.
+// A family = the variants of one kernel template (frw_launch.h) and the instantiation that belongs to each.  Everything else comes from
+// it: init_launch_config asks the runtime for the residency of every variant of the list, a launcher reads its variant's slot and
+// dispatches over the same list -- what can be launched has been asked, and what is not in the list is hipErrorInvalidValue.
+// The lists themselves are frw_launch.h's (tests/cpp/test_launch_host.cpp holds them to what each kernel is instantiated for).
+struct WitnessNtt : WitnessNttVariants {
+    template <class L, class E> static auto kernel(L, E) { return witness_ntt_verify_kernel<L::value, E::value>; }
+};
+struct Expand : ExpandVariants {
+    template <class L, class E> static auto kernel(L, E) { return expand_kernel<L::value, E::value>; }
+};
+struct WitnessDual : WitnessDualVariants {
+    template <class L, class E> static auto kernel(L, E) { return witness_dual_ntt_verify_kernel<L::value, E::value>; }
+};
+struct WitnessSchoolbook : WitnessSchoolbookVariants {
+    template <class L, class E> static auto kernel(L, E) { return witness_schoolbook_verify_kernel<L::value, E::value>; }
+};
+struct Statement : StatementVariants {
+    template <class L, class F, class E> static auto kernel(L, F, E) { return statement_kernel<L::value, F::value, E::value>; }
+};
+struct FalconVerify : FalconVerifyVariants {
+    template <class L, class R> static auto kernel(L, R) { return falcon_verify_kernel<L::value, R::value>; }
+};
+struct NttModq : NttModqVariants {
+    template <class L, class E> static auto kernel(L, E) { return ntt_modq_kernel<L::value, E::value>; }
+};
+struct Gadget : GadgetVariants {
+    template <class K, class E> static auto kernel(K, E) { return gadget_kernel<K::value, E::value>; }
+};
+static_assert(G_LESS_THAN_Q == 0 && G_NORM_1024 == 5, "GadgetVariants lists the kinds 0 .. 5");
 
-template <typename K>
-static void query_residency(K kernel, int &cache)
-{
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-    cache = per_cu;
-}
+// Resident workgroups per CU of a persistent family, one table each.  Filled exactly once per process (std::call_once in
+// init_launch_config, which every context creation calls before any launch), read-only afterwards: contexts on several devices /
+// threads share it safely.
+template <class Family> static Residency<Family> g_resident;
+static std::once_flag g_resident_once;
 
-// Workgroups to launch for `batch` items.  `cap` = what the device keeps resident (per_cu x CUs).  Launches with at least
-// two items per workgroup to spare use up to OVERSUB x cap: with more workgroups than the device holds, the ones that
-// finish are replaced at different moments, which keeps the workgroups' compute and store phases from lining up across
-// the chip (measured, tools/ab_variants.py: 32,768 Falcon-1024 signatures +1.3 ... 3.5 % at 2 x ... 4 x the resident 768,
-// no more at 6 x and 8 x; 8,192 Falcon-512 signatures +2.7 % at 2,048 and +4.4 % at 4,096 workgroups over 1,024, -9 % at
-// one signature per workgroup; the expansion kernel, whose items are all stores behind a few loads, +4.5 % at 8 x:
-// profiles/r02_scheduling_ab.txt).
-#ifndef FRW_OVERSUB
-#define FRW_OVERSUB 4
-#endif
-static int resident_grid(size_t batch, int num_cu, int per_cu, int oversub = FRW_OVERSUB)
+template <class... Family> static void query_residency()
 {
-    const size_t cap = (size_t)(per_cu > 0 ? per_cu : 2) * (size_t)num_cu;
-    if (batch <= cap) return (int)batch;
-#if defined(FRW_FORCE_GRID)          // A/B builds only
-    return FRW_FORCE_GRID;
-#endif
-    // beyond the resident capacity only while every workgroup keeps at least two items
-    size_t top = cap;
-    if (batch >= 2 * cap) top = std::min((size_t)oversub * cap, batch / 2);
-    // Every workgroup streams one 2.5-5 MB signature at a time, so a batch that is not a multiple of the grid ends in a
-    // tail where most CUs idle.  For short launches (< 8 rounds) a grid between 5/8 and 8/8 of the target that divides the
-    // batch wins (4,096 signatures: 512 x 8 rounds beats 768 x 5.33 by 1.1 %); long launches amortise the tail, and the
-    // witness kernel splits it besides.
-    if (batch < 8 * top)
-        for (size_t g = top; g * 8 >= top * 5; g--)
-            if (batch % g == 0) return (int)g;
-    return (int)top;
+    (g_resident<Family>.fill([](auto... variant) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Family::kernel(variant...), BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+        return per_cu;
+    }), ...);
 }
 
 // Called once per context: asks the runtime for the residency of every persistent kernel, so that no launch ever
 // has to (a launch may be inside a stream capture, where such queries are not allowed).
 void init_launch_config()
 {
-    std::call_once(g_occ_once, [] {
-#define FRW_Q(K, CACHE, LOGN, ENC) query_residency(K<LOGN, ENC>, CACHE[(LOGN - 9) * 2 + ENC])
-#define FRW_QV(LOGN, ENC) query_residency(witness_ntt_verify_kernel<LOGN, ENC>, g_occ_verify[(LOGN - 9) * 2 + ENC])
-        FRW_QV(9, 0); FRW_QV(9, 1); FRW_QV(10, 0); FRW_QV(10, 1);
-#undef FRW_QV
-        FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 9, 0); FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 9, 1);
-        FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 10, 0); FRW_Q(witness_dual_ntt_verify_kernel, g_occ_dual, 10, 1);
-        FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 9, 0); FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 9, 1);
-        FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 10, 0); FRW_Q(witness_schoolbook_verify_kernel, g_occ_schoolbook, 10, 1);
-        FRW_Q(ntt_modq_kernel, g_occ_ntt, 9, 0); FRW_Q(ntt_modq_kernel, g_occ_ntt, 9, 1);
-        FRW_Q(ntt_modq_kernel, g_occ_ntt, 10, 0); FRW_Q(ntt_modq_kernel, g_occ_ntt, 10, 1);
-#undef FRW_Q
-        query_residency(witness_ntt_verify_kernel<9, 2>, g_occ_compact[0]);
-        query_residency(witness_ntt_verify_kernel<10, 2>, g_occ_compact[1]);
-        query_residency(expand_kernel<9, 1>, g_occ_expand[0]);
-        query_residency(expand_kernel<10, 1>, g_occ_expand[1]);
-#define FRW_QS(LOGN, FORM, ENC) query_residency(statement_kernel<LOGN, FORM, ENC>, g_occ_statement[(LOGN - 9) * 4 + FORM * 2 + ENC])
-        FRW_QS(9, 0, 0); FRW_QS(9, 0, 1); FRW_QS(9, 1, 0); FRW_QS(9, 1, 1);
-        FRW_QS(10, 0, 0); FRW_QS(10, 0, 1); FRW_QS(10, 1, 0); FRW_QS(10, 1, 1);
-#undef FRW_QS
-        query_residency(falcon_verify_kernel<9, 0>, g_occ_falcon_verify[0]);
-        query_residency(falcon_verify_kernel<9, 1>, g_occ_falcon_verify[1]);
-        query_residency(falcon_verify_kernel<10, 0>, g_occ_falcon_verify[2]);
-        query_residency(falcon_verify_kernel<10, 1>, g_occ_falcon_verify[3]);
-        query_residency(witness_ntt_verify_kernel<9, 3>, g_occ_verify_field[0]);
-        query_residency(witness_ntt_verify_kernel<10, 3>, g_occ_verify_field[1]);
-        query_residency(ntt_modq_kernel<9, 3>, g_occ_ntt_field[0]);
-        query_residency(ntt_modq_kernel<10, 3>, g_occ_ntt_field[1]);
-        query_residency(expand_kernel<9, 3>, g_occ_expand_field[0]);
-        query_residency(expand_kernel<10, 3>, g_occ_expand_field[1]);
-        query_residency(statement_kernel<9, 0, 3>, g_occ_statement_field[0]);
-        query_residency(statement_kernel<9, 1, 3>, g_occ_statement_field[1]);
-        query_residency(statement_kernel<10, 0, 3>, g_occ_statement_field[2]);
-        query_residency(statement_kernel<10, 1, 3>, g_occ_statement_field[3]);
-    });
+    std::call_once(g_resident_once, query_residency<WitnessNtt, Expand, WitnessDual, WitnessSchoolbook, Statement, FalconVerify, NttModq>);
 }
 
 // the kernel argument of an instantiation: the registered field's constants for ENC 3, nothing otherwise
@@ -1988,84 +1951,48 @@ template <int ENC> static field_arg_t<ENC> field_arg(const FieldConsts *fc)
     else return NoField();
 }
 
-// (grid, full) of a witness launch: all-split for small batches, one workgroup per signature up to the resident capacity,
-// else the resident grid (or, for short launches, a divisor of the batch close to it) with the ragged tail split.
-static void verify_shape(size_t batch, int num_cu, int occ, bool may_split, int &grid, size_t &full)
+// what a launcher returns once its family's dispatch is through
+static hipError_t launched(bool found) { return found ? hipGetLastError() : hipErrorInvalidValue; }
+
+// residency, grid and whole-signature count of a witness_ntt_verify_kernel launch: the launch and the diagnostic both take them from here
+struct WitnessNttShape { int occ, grid; size_t full; };
+static WitnessNttShape witness_ntt_shape(int num_cu, int logn, int enc, size_t batch)
 {
-    const size_t cap = (size_t)(occ > 0 ? occ : 2) * (size_t)num_cu;
-    if (may_split && batch * PARTS <= cap) {     // measured: 1 signature 167 -> 56 us, 64 signatures 172 -> 95 us; at 256 it loses
-        grid = (int)(batch * PARTS);
-        full = 0;
-        return;
-    }
-    grid = resident_grid(batch, num_cu, occ);
-    full = may_split ? batch / (size_t)grid * (size_t)grid : batch;
+    WitnessNttShape s;
+    s.occ = g_resident<WitnessNtt>(logn, enc);
+    verify_shape(batch, num_cu, s.occ, true, s.grid, s.full);
+    return s;
 }
 
-void launch_shape_witness_ntt_verify(int num_cu, int logn, int enc, size_t batch, int out[4])
+void launch_shape_witness_ntt_verify(int num_cu, int logn, KernelEnc ke, size_t batch, int out[4])
 {
-    const int occ = enc == 3 ? g_occ_verify_field[logn - 9] : enc == 2 ? g_occ_compact[logn - 9] : g_occ_verify[(logn - 9) * 2 + (enc & 1)];
-    int grid;
-    size_t full;
-    verify_shape(batch, num_cu, occ, true, grid, full);
-    out[0] = grid;
-    out[1] = occ;
+    const WitnessNttShape s = witness_ntt_shape(num_cu, logn, ke.enc, batch);
+    out[0] = s.grid;
+    out[1] = s.occ;
     out[2] = num_cu;
-    out[3] = (int)(batch - full);          // signatures cut into five work items
+    out[3] = (int)(batch - s.full);        // signatures cut into five work items
 }
 
-hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, int enc, size_t batch,
+hipError_t launch_witness_ntt_verify(const Tables *tab, int num_cu, int logn, KernelEnc ke, size_t batch,
                                      const uint16_t *sig, const uint16_t *pk, const uint16_t *hm,
-                                     uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st, const FieldConsts *fc)
+                                     void *wit, uint64_t *inst, int32_t *status, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-    int grid;
-    size_t full;
-    verify_shape(batch, num_cu, fc ? g_occ_verify_field[logn - 9] : g_occ_verify[(logn - 9) * 2 + enc], true, grid, full);
-#define FRW_LAUNCH(LOGN, ENC)                                                                                              \
-    hipLaunchKernelGGL((witness_ntt_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm, \
-                       (v4u *)wit, (v4u *)inst, status, field_arg<ENC>(fc))
-    if (fc && logn == 9) FRW_LAUNCH(9, 3);
-    else if (fc) FRW_LAUNCH(10, 3);
-    else if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
-    else if (logn == 9) FRW_LAUNCH(9, 1);
-    else if (enc == 0) FRW_LAUNCH(10, 0);
-    else FRW_LAUNCH(10, 1);
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const WitnessNttShape s = witness_ntt_shape(num_cu, logn, ke.enc, batch);
+    return launched(WitnessNtt::dispatch([&](auto l, auto e) {
+        hipLaunchKernelGGL(WitnessNtt::kernel(l, e), dim3(s.grid), dim3(BLOCK), 0, st, tab, batch, s.full, sig, pk, hm, (v4u *)wit,
+                           e == 2 ? (v4u *)nullptr : (v4u *)inst, status, field_arg<e>(ke.fc));
+    }, logn, ke.enc));
 }
 
-hipError_t launch_witness_ntt_verify_compact(const Tables *tab, int num_cu, int logn, size_t batch,
-                                             const uint16_t *sig, const uint16_t *pk, const uint16_t *hm, void *compact,
-                                             int32_t *status, hipStream_t st)
+hipError_t launch_expand(int num_cu, int logn, KernelEnc ke, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-    int grid;
-    size_t full;
-    verify_shape(batch, num_cu, g_occ_compact[logn - 9], true, grid, full);
-    if (logn == 9)
-        hipLaunchKernelGGL((witness_ntt_verify_kernel<9, 2>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm,
-                           (v4u *)compact, (v4u *)nullptr, status, NoField());
-    else
-        hipLaunchKernelGGL((witness_ntt_verify_kernel<10, 2>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, full, sig, pk, hm,
-                           (v4u *)compact, (v4u *)nullptr, status, NoField());
-    return hipGetLastError();
-}
-
-hipError_t launch_expand(int num_cu, int logn, size_t batch, const void *compact, uint64_t *wit, uint64_t *inst, hipStream_t st,
-                         const FieldConsts *fc)
-{
-    if (batch == 0) return hipSuccess;
-    const int grid = resident_grid(batch, num_cu, fc ? g_occ_expand_field[logn - 9] : g_occ_expand[logn - 9], 8);
-#define FRW_LAUNCH(LOGN, ENC)                                                                                                       \
-    hipLaunchKernelGGL((expand_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, batch, (const unsigned char *)compact, (v4u *)wit, \
-                       (v4u *)inst, field_arg<ENC>(fc))
-    if (fc && logn == 9) FRW_LAUNCH(9, 3);
-    else if (fc) FRW_LAUNCH(10, 3);
-    else if (logn == 9) FRW_LAUNCH(9, 1);
-    else FRW_LAUNCH(10, 1);
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(batch, num_cu, g_resident<Expand>(logn, ke.enc), 8);
+    return launched(Expand::dispatch([&](auto l, auto e) {
+        hipLaunchKernelGGL(Expand::kernel(l, e), dim3(grid), dim3(BLOCK), 0, st, batch, (const unsigned char *)compact, (v4u *)wit,
+                           (v4u *)inst, field_arg<e>(ke.fc));
+    }, logn, ke.enc));
 }
 
 hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int logn, int enc,
@@ -2073,18 +2000,10 @@ hipError_t launch_witness_dual_ntt_verify(const Tables *tab, int num_cu, int log
                                           uint64_t *wit, uint64_t *inst, int32_t *status, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-#define FRW_LAUNCH(LOGN, ENC)                                                                                       \
-    do {                                                                                                            \
-        const int grid = resident_grid(batch, num_cu, g_occ_dual[(LOGN - 9) * 2 + ENC]);                            \
-        hipLaunchKernelGGL((witness_dual_ntt_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab,        \
-                           batch, sig, pk, hm, (v4u *)wit, (v4u *)inst, status);                                    \
-    } while (0)
-    if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
-    else if (logn == 9) FRW_LAUNCH(9, 1);
-    else if (enc == 0) FRW_LAUNCH(10, 0);
-    else FRW_LAUNCH(10, 1);
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(batch, num_cu, g_resident<WitnessDual>(logn, enc));
+    return launched(WitnessDual::dispatch([&](auto l, auto e) {
+        hipLaunchKernelGGL(WitnessDual::kernel(l, e), dim3(grid), dim3(BLOCK), 0, st, tab, batch, sig, pk, hm, (v4u *)wit, (v4u *)inst, status);
+    }, logn, enc));
 }
 
 hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int logn, int enc,
@@ -2093,48 +2012,24 @@ hipError_t launch_witness_schoolbook_verify(const Tables *tab, int num_cu, int l
 {
     if (batch == 0) return hipSuccess;
     const size_t items = batch * (((size_t)1 << logn) / SB_COLS + 1);
-#define FRW_LAUNCH(LOGN, ENC)                                                                                       \
-    do {                                                                                                            \
-        const int grid = resident_grid(items, num_cu, g_occ_schoolbook[(LOGN - 9) * 2 + ENC]);                      \
-        hipLaunchKernelGGL((witness_schoolbook_verify_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab,      \
-                           batch, sig, pk, hm, (v4u *)wit, (v4u *)inst, status);                                    \
-    } while (0)
-    if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
-    else if (logn == 9) FRW_LAUNCH(9, 1);
-    else if (enc == 0) FRW_LAUNCH(10, 0);
-    else FRW_LAUNCH(10, 1);
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(items, num_cu, g_resident<WitnessSchoolbook>(logn, enc));
+    return launched(WitnessSchoolbook::dispatch([&](auto l, auto e) {
+        hipLaunchKernelGGL(WitnessSchoolbook::kernel(l, e), dim3(grid), dim3(BLOCK), 0, st, tab, batch, sig, pk, hm, (v4u *)wit, (v4u *)inst,
+                           status);
+    }, logn, enc));
 }
 
 // one launch: 2 x batch work items (statement, polynomial) strided over the resident grid
-hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, int enc, size_t batch, const uint16_t *pk,
+hipError_t launch_statement(const Tables *tab, int num_cu, int logn, int form, KernelEnc ke, size_t batch, const uint16_t *pk,
                             const uint16_t *hm, uint64_t *out, const uint64_t *offs, int lead, const int32_t *pre,
-                            int32_t *status, const uint32_t *status_index, hipStream_t st, const FieldConsts *fc)
+                            int32_t *status, const uint32_t *status_index, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-    const int grid = resident_grid(batch * 2, num_cu, fc ? g_occ_statement_field[(logn - 9) * 2 + form]
-                                                         : g_occ_statement[(logn - 9) * 4 + form * 2 + enc]);
-#define FRW_LAUNCH(LOGN, FORM, ENC)                                                                                       \
-    hipLaunchKernelGGL((statement_kernel<LOGN, FORM, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, pk, hm, (v4u *)out, \
-                       offs, lead, pre, status, status_index, field_arg<ENC>(fc))
-    switch (fc ? 8 + (logn - 9) * 2 + form : (logn - 9) * 4 + form * 2 + enc) {
-    case 8: FRW_LAUNCH(9, 0, 3); break;
-    case 9: FRW_LAUNCH(9, 1, 3); break;
-    case 10: FRW_LAUNCH(10, 0, 3); break;
-    case 11: FRW_LAUNCH(10, 1, 3); break;
-    case 0: FRW_LAUNCH(9, 0, 0); break;
-    case 1: FRW_LAUNCH(9, 0, 1); break;
-    case 2: FRW_LAUNCH(9, 1, 0); break;
-    case 3: FRW_LAUNCH(9, 1, 1); break;
-    case 4: FRW_LAUNCH(10, 0, 0); break;
-    case 5: FRW_LAUNCH(10, 0, 1); break;
-    case 6: FRW_LAUNCH(10, 1, 0); break;
-    case 7: FRW_LAUNCH(10, 1, 1); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(batch * 2, num_cu, g_resident<Statement>(logn, form, ke.enc));
+    return launched(Statement::dispatch([&](auto l, auto f, auto e) {
+        hipLaunchKernelGGL(Statement::kernel(l, f, e), dim3(grid), dim3(BLOCK), 0, st, tab, batch, pk, hm, (v4u *)out, offs, lead, pre, status,
+                           status_index, field_arg<e>(ke.fc));
+    }, logn, form, ke.enc));
 }
 
 // one launch: the signatures strided over the resident grid, one workgroup a signature
@@ -2143,65 +2038,34 @@ hipError_t launch_falcon_verify(const Tables *tab, int num_cu, int logn, int rul
                                 int32_t *status, uint64_t *norm, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-    const int grid = resident_grid(batch, num_cu, g_occ_falcon_verify[(logn - 9) * 2 + rule]);
-#define FRW_LAUNCH(LOGN, RULE)                                                                                            \
-    hipLaunchKernelGGL((falcon_verify_kernel<LOGN, RULE>), dim3(grid), dim3(BLOCK), 0, st, tab, batch, sig, pk, hm, pre0, \
-                       pre1, status, (unsigned long long *)norm)
-    switch ((logn - 9) * 2 + rule) {
-    case 0: FRW_LAUNCH(9, 0); break;
-    case 1: FRW_LAUNCH(9, 1); break;
-    case 2: FRW_LAUNCH(10, 0); break;
-    case 3: FRW_LAUNCH(10, 1); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(batch, num_cu, g_resident<FalconVerify>(logn, rule));
+    return launched(FalconVerify::dispatch([&](auto l, auto r) {
+        hipLaunchKernelGGL(FalconVerify::kernel(l, r), dim3(grid), dim3(BLOCK), 0, st, tab, batch, sig, pk, hm, pre0, pre1, status,
+                           (unsigned long long *)norm);
+    }, logn, rule));
 }
 
-hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, int enc, size_t batch, const uint16_t *poly,
-                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st, const FieldConsts *fc)
+hipError_t launch_ntt_modq(const Tables *tab, int num_cu, int logn, KernelEnc ke, size_t batch, const uint16_t *poly,
+                           uint64_t *wit, uint16_t *ntt_out, int32_t *status, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
-#define FRW_LAUNCH(LOGN, ENC)                                                                                  \
-    do {                                                                                                       \
-        const int grid = resident_grid(batch, num_cu, ENC == 3 ? g_occ_ntt_field[LOGN - 9] : g_occ_ntt[(LOGN - 9) * 2 + (ENC & 1)]); \
-        hipLaunchKernelGGL((ntt_modq_kernel<LOGN, ENC>), dim3(grid), dim3(BLOCK), 0, st, tab, batch,           \
-                           poly, (v4u *)wit, ntt_out, status, field_arg<ENC>(fc));                             \
-    } while (0)
-    if (fc && logn == 9) FRW_LAUNCH(9, 3);
-    else if (fc) FRW_LAUNCH(10, 3);
-    else if (logn == 9 && enc == 0) FRW_LAUNCH(9, 0);
-    else if (logn == 9) FRW_LAUNCH(9, 1);
-    else if (enc == 0) FRW_LAUNCH(10, 0);
-    else FRW_LAUNCH(10, 1);
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    const int grid = resident_grid(batch, num_cu, g_resident<NttModq>(logn, ke.enc));
+    return launched(NttModq::dispatch([&](auto l, auto e) {
+        hipLaunchKernelGGL(NttModq::kernel(l, e), dim3(grid), dim3(BLOCK), 0, st, tab, batch, poly, (v4u *)wit, ntt_out, status,
+                           field_arg<e>(ke.fc));
+    }, logn, ke.enc));
 }
 
-hipError_t launch_gadget(int kind, int enc, size_t count, const void *a, const uint64_t *b, uint64_t *out,
-                         int32_t *status, hipStream_t st, const FieldConsts *fc)
+hipError_t launch_gadget(int kind, KernelEnc ke, size_t count, const void *a, const uint64_t *b, uint64_t *out,
+                         int32_t *status, hipStream_t st)
 {
     if (count == 0) return hipSuccess;
     size_t tiles = (count + WAVE - 1) / WAVE;
     size_t grid = (tiles + WAVES - 1) / WAVES;
     if (grid > 8192) grid = 8192;
-#define FRW_LAUNCH(KIND)                                                                                         \
-    case KIND:                                                                                                   \
-        if (fc) hipLaunchKernelGGL((gadget_kernel<KIND, 3>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, *fc); \
-        else if (enc == 0) hipLaunchKernelGGL((gadget_kernel<KIND, 0>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, NoField()); \
-        else hipLaunchKernelGGL((gadget_kernel<KIND, 1>), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, NoField()); \
-        break
-    switch (kind) {
-        FRW_LAUNCH(G_LESS_THAN_Q);
-        FRW_LAUNCH(G_MOD_Q);
-        FRW_LAUNCH(G_ADD_MOD);
-        FRW_LAUNCH(G_L2_ELEM);
-        FRW_LAUNCH(G_NORM_512);
-        FRW_LAUNCH(G_NORM_1024);
-    default: return hipErrorInvalidValue;
-    }
-#undef FRW_LAUNCH
-    return hipGetLastError();
+    return launched(Gadget::dispatch([&](auto k, auto e) {
+        hipLaunchKernelGGL(Gadget::kernel(k, e), dim3((unsigned)grid), dim3(BLOCK), 0, st, count, a, b, (v4u *)out, status, field_arg<e>(ke.fc));
+    }, kind, ke.enc));
 }
 
 hipError_t launch_digest(const uint64_t *buf, size_t words, size_t items, uint64_t *out, hipStream_t st)

@@ -55,3 +55,7 @@ ASAN_OPTIONS=detect_leaks=0 /tmp/frw_rerand_host_asan | tail -1
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" \
     -o /tmp/frw_stage_host_asan "$ROOT/tests/cpp/test_stage_host.cpp" -L"$ROOT/falcon-r1cs_amd" -lfrw -Wl,-rpath,"$ROOT/falcon-r1cs_amd"
 ASAN_OPTIONS=detect_leaks=0 /tmp/frw_stage_host_asan | tail -1
+# the host side of the launchers (frw_launch.h: the variant dispatcher, the residency tables, the grid arithmetic): a program of its own
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -Werror -I "$ROOT/falcon-r1cs_amd/csrc" \
+    -o /tmp/frw_launch_host_asan "$ROOT/tests/cpp/test_launch_host.cpp"
+/tmp/frw_launch_host_asan | tail -1

@@ -203,6 +203,8 @@ PROTOTYPES = {
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "frw_r1cs_export": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_void_p]),
     "frw_r1cs_load": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_r1cs_load_csr": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "frw_r1cs_load_file": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_free": (None, [C.c_void_p]),
     "frw_r1cs_load_aggregate": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_info": (C.c_int, [C.c_void_p, C.POINTER(R1csInfoStruct)]),

@@ -984,6 +984,9 @@ bool pok_prove_shape(const frw_groth16_pk *pk, const frw_r1cs *r, int circuit, i
     frw_r1cs_info_t info;
     frw_groth16_pk_info_t ki;
     if (frw_r1cs_info(r, &info) != FRW_OK || frw_groth16_pk_info(pk, &ki) != FRW_OK) return false;
+    // the handle frw_r1cs_load made for this circuit: a system that came in as matrices is not it, whatever its counts (the export loaded
+    // back has Falcon's) -- the witness kernels behind these calls know the Falcon circuits only
+    if (!frw::r1cs_is_circuit(r, circuit, logn)) return false;
     if (info.num_statements != 1 || info.num_instance != s.num_instance || info.num_witness != s.num_witness ||
         info.num_constraints != s.num_constraints)
         return false;

@@ -235,6 +235,9 @@ struct R1csAgg {
 const R1csAgg *r1cs_aggregate(const ::frw_r1cs *r, int *device);
 // the device any handle's matrices are on
 int r1cs_device(const ::frw_r1cs *r);
+// whether the handle is frw_r1cs_load(circuit, logn)'s: not an aggregate, and not a system that came in as matrices (frw_r1cs_load_csr /
+// frw_r1cs_load_file), whatever its counts
+bool r1cs_is_circuit(const ::frw_r1cs *r, int circuit, int logn);
 size_t r1cs_check_scratch_bytes(const R1csDev &r, size_t batch, bool with_abc);
 hipError_t launch_r1cs_check(const R1csDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance,
                              uint32_t *num_unsatisfied, uint64_t *abc, hipStream_t st, void *scratch = nullptr);
@@ -273,6 +276,9 @@ struct QapDev {
     const uint32_t *scale_psi_in; // psi^k / n
     const uint32_t *scale_psi_out;// -16 psi^-k / n           (-1/2, and 32 for the data x data product in R' arithmetic)
     uint32_t sixteen_over_n[9];   // 16 / n, x R' in nine limbs
+    // domains below 2^QAP_MIN_LOG_N (frw_qap_small.hip; num_passes == 0): ONE table, x R' packed, [w^k | w^-k (k < n / 2) | g^k / n |
+    // 2^5 g^k / n | g^-k / (n (g^n - 1)) (k < n)] = qap_small_table_words(log_n) words; null where the passes above apply
+    const uint32_t *small_tab;
 };
 size_t qap_workspace_bytes_per_signature(const R1csDev &r, const QapDev &q);
 // ---- setup on the device (frw_setup.hip): transform tables, the QAP at the toxic point, the queries' scalars ------------------------
@@ -325,6 +331,10 @@ hipError_t launch_qap_quotient(const R1csDev &r, const QapDev &q, size_t batch, 
 hipError_t launch_qap_witness_map(const R1csDev &r, const QapDev &q, size_t batch, const uint64_t *witness,
                                   const uint64_t *instance, uint64_t *h, uint32_t *num_unsatisfied, void *workspace,
                                   size_t workspace_bytes, hipStream_t st);
+// the witness map on the domains 2^1 .. 2^13 (frw_qap_small.hip): same arguments, workspace and result as launch_qap_witness_map
+size_t qap_small_table_words(int L);
+hipError_t launch_qap_small(const R1csDev &r, const QapDev &q, size_t batch, const uint64_t *witness, const uint64_t *instance,
+                            uint64_t *h, uint32_t *num_unsatisfied, void *workspace, size_t workspace_bytes, hipStream_t st);
 hipError_t launch_write_stream(void *buf, size_t bytes, size_t slab_bytes, int num_cu, hipStream_t st);
 hipError_t launch_digest(const uint64_t *buf, size_t words, size_t items, uint64_t *out, hipStream_t st);
 

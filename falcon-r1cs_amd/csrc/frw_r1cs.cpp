@@ -22,6 +22,7 @@
 #include "../../include/frw.h"
 #include "frw_arena.h"
 #include "frw_device.h"
+#include "frw_r1cs_file.h"
 #include "frw_stage.h"
 #include "host/frw_host.hpp"
 
@@ -43,7 +44,8 @@ frw::host::ConstraintMatrices build_matrices(int circuit, int logn)
 // Device-resident matrices for frw_r1cs_check_dev
 struct frw_r1cs {
     int device;
-    int circuit = FRW_CIRCUIT_NTT, logn = 0;            // logn == 0: an aggregate statement
+    // logn == 0: an aggregate statement, or (circuit == -1) a system that came in as matrices (frw_r1cs_load_csr / frw_r1cs_load_file)
+    int circuit = FRW_CIRCUIT_NTT, logn = 0;
     frw::R1csDev dev;
     frw::QapDev qap;
     std::vector<void *> allocs;
@@ -179,8 +181,26 @@ void upload_qap_tables(frw_r1cs *r, uint64_t num_constraints, uint64_t num_insta
     if (L > 32) throw std::runtime_error("PolynomialDegreeTooLarge");
     r->qap.log_n = L;
     r->qap.num_passes = frw::qap_pass_schedule(L, r->qap.pass_t, r->qap.pass_sh);
-    if (!r->qap.num_passes) return;                                 // no device witness map for such a domain (frw_qap.hip)
     const size_t n = (size_t)1 << L;
+    if (!r->qap.num_passes) {
+        // below 2^14 (frw_qap_small.hip): one table of 4 n entries, made here -- the device's table kernel takes its powers from a 2^14-entry
+        // table and one of 2^(L - 14)
+        if (L < 1 || L >= frw::QAP_MIN_LOG_N) return;
+        Fr w = Fr::from_montgomery(TWO_ADIC_ROOT_LIMBS);
+        for (int i = L; i < 32; i++) w = w * w;
+        const Fr winv = inverse(w), g = Fr::from(7), ginv = inverse(g), ninv = inverse(Fr::from(n));
+        const Fr first[3] = {ninv, ninv * Fr::from(32), ninv * inverse(g.pow(n) - Fr::one())}, base[3] = {g, g, ginv};
+        std::vector<uint32_t> tab(frw::qap_small_table_words(L));
+        const size_t half = n / 2;
+        Fr x = Fr::one(), y = Fr::one();
+        for (size_t k = 0; k < half; k++) { packed29(x, &tab[8 * k]); packed29(y, &tab[8 * (half + k)]); x = x * w; y = y * winv; }
+        for (int t = 0; t < 3; t++) {
+            x = first[t];
+            for (size_t k = 0; k < n; k++) { packed29(x, &tab[8 * ((1 + t) * n + k)]); x = x * base[t]; }
+        }
+        r->qap.small_tab = (const uint32_t *)upload(tab.data(), tab.size() * 4);
+        return;
+    }
     // what the tables take: 2 (K - 1) twists + 5 scale tables of 32 n bytes -- asked of the device before anything is allocated
     {
         size_t free_b = 0, total_b = 0;
@@ -243,18 +263,13 @@ void upload_qap_tables(frw_r1cs *r, uint64_t num_constraints, uint64_t num_insta
     r->qap.roots_fwd = roots(w);
     r->qap.roots_inv = roots(winv);
 }
-}  // namespace
 
-extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
+// The loader: any system's matrices onto `device` (the current one), in every form the kernels read.  circuit / logn: what
+// frw_r1cs_load built them from, or -1 / 0 for matrices that came in from outside.
+int load_matrices(int device, std::shared_ptr<const frw::host::ConstraintMatrices> matrices, int circuit, int logn, frw_r1cs **out)
 {
-    if (!out || (logn != 9 && logn != 10) || !frw::known_circuit(circuit)) return FRW_E_INVALID_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FRW_E_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return FRW_E_HIP;
     frw_r1cs *r = nullptr;
     try {
-        auto matrices = std::make_shared<const frw::host::ConstraintMatrices>(build_matrices(circuit, logn));
         const frw::host::ConstraintMatrices &m = *matrices;
         r = new frw_r1cs;
         r->host_matrices = matrices;
@@ -303,6 +318,21 @@ extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
             return m.a[x].size() + m.b[x].size() + m.c[x].size() > m.a[y].size() + m.b[y].size() + m.c[y].size();
         });
         r->dev.order = (const uint32_t *)upload(order.data(), order.size() * 4);
+        // Rows of R1CS_LONG_ROW terms and more go to a wavefront each, and the witness map lends the plain values of the variables they
+        // read, four bytes apiece, out of its working arrays (96 n bytes a statement).  A system whose long rows read more variables
+        // than that holds (no Falcon circuit does: a few thousand against 2^17) has no long rows: the CSR walk takes rows of any length.
+        size_t long_row = frw::R1CS_LONG_ROW;
+        {
+            std::vector<uint32_t> seen{0u};
+            for (const auto *mat : {&m.a, &m.b, &m.c})
+                for (const auto &row : *mat)
+                    if (row.size() >= frw::R1CS_LONG_ROW)
+                        for (const auto &t : row) seen.push_back(t.second);
+            std::sort(seen.begin(), seen.end());
+            seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
+            const size_t n = (size_t)1 << domain_log(m.num_constraints + m.num_instance_variables);
+            if (seen.size() * 4 + 255 > 96 * n) long_row = SIZE_MAX;
+        }
         // the short rows flattened (frw_device.h: flat_*): one header and one run of term words per row, coefficients by index
         {
             const std::vector<frw::host::ConstraintMatrices::Row> *ms[3] = {&m.a, &m.b, &m.c};
@@ -310,13 +340,14 @@ extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
             std::vector<Fr> coefs{one, minus_one};
             std::vector<uint32_t> fhead, fterm;
             bool fits = std::getenv("FRW_R1CS_NO_FLAT") == nullptr;     // (diagnostics: tests run the CSR walk, the route of a circuit that does not fit)
+            fits = fits && long_row == frw::R1CS_LONG_ROW;               // (a header counts a short row's terms in eight bits)
             for (size_t i = 0; i < m.num_constraints && fits; i++) {
                 const uint32_t row = order[i];               // (rows in their own order instead: stores coalesce, lengths diverge -- 1,727 us against 618)
                 const size_t first_term = fterm.size();
                 uint32_t counts = 0;
                 for (uint32_t mi = 0; mi < 3 && fits; mi++) {
                     const auto &terms = (*ms[mi])[row];
-                    if (terms.size() >= frw::R1CS_LONG_ROW) { counts |= 1u << (24 + mi); continue; }
+                    if (terms.size() >= long_row) { counts |= 1u << (24 + mi); continue; }
                     counts |= (uint32_t)terms.size() << (8 * mi);
                     for (const auto &t : terms) {
                         size_t idx = 0;
@@ -355,7 +386,7 @@ extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
         for (uint32_t mi = 0; mi < 3; mi++)
             for (size_t row = 0; row < m.num_constraints; row++) {
                 const auto &terms = (*mats[mi])[row];
-                if (terms.size() < frw::R1CS_LONG_ROW) continue;
+                if (terms.size() < long_row) continue;
                 const uint32_t chunks = (uint32_t)((terms.size() + 63) / 64), first = (uint32_t)(lcol.size() / 64);
                 lslot[(size_t)mi * m.num_constraints + row] = (uint32_t)lrows.size();
                 lrows.push_back({mi, (uint32_t)row, first, chunks});
@@ -396,6 +427,63 @@ extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
         return FRW_OK;
     } catch (const std::exception &) {
         frw_r1cs_free(r);
+        return FRW_E_OUT_OF_MEMORY;
+    }
+}
+}  // namespace
+
+extern "C" int frw_r1cs_load(int device, int circuit, int logn, frw_r1cs **out)
+{
+    if (!out || (logn != 9 && logn != 10) || !frw::known_circuit(circuit)) return FRW_E_INVALID_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FRW_E_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return FRW_E_HIP;
+    try {
+        return load_matrices(device, std::make_shared<const frw::host::ConstraintMatrices>(build_matrices(circuit, logn)), circuit, logn, out);
+    } catch (const std::exception &) {
+        return FRW_E_OUT_OF_MEMORY;
+    }
+}
+
+// ---- a system that comes in as matrices (frw_r1cs_file.h parses and validates; nothing of the device is touched before) ----------
+namespace {
+int load_custom(int device, const std::string &refusal, std::shared_ptr<frw::host::ConstraintMatrices> matrices, const char *what, frw_r1cs **out)
+{
+    if (!refusal.empty()) {
+        frw::record_error("%s: %s", what, refusal.c_str());
+        return FRW_E_INVALID_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FRW_E_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return FRW_E_HIP;
+    return load_matrices(device, matrices, -1, 0, out);
+}
+}  // namespace
+
+extern "C" int frw_r1cs_load_csr(int device, const uint64_t counts[6], const uint64_t *const row_ptr[3], const uint32_t *const col[3],
+                                 const uint64_t *const val[3], frw_r1cs **out)
+{
+    if (!out) return FRW_E_INVALID_ARG;
+    *out = nullptr;
+    try {
+        auto m = std::make_shared<frw::host::ConstraintMatrices>();
+        const std::string refusal = frw::r1cs_from_csr(counts, row_ptr, col, val, m.get());
+        return load_custom(device, refusal, m, "frw_r1cs_load_csr", out);
+    } catch (const std::exception &) {
+        return FRW_E_OUT_OF_MEMORY;
+    }
+}
+
+extern "C" int frw_r1cs_load_file(int device, const char *path, frw_r1cs **out)
+{
+    if (!out) return FRW_E_INVALID_ARG;
+    *out = nullptr;
+    try {
+        auto m = std::make_shared<frw::host::ConstraintMatrices>();
+        const std::string refusal = frw::r1cs_from_file(path, m.get());
+        return load_custom(device, refusal, m, "frw_r1cs_load_file", out);
+    } catch (const std::exception &) {
         return FRW_E_OUT_OF_MEMORY;
     }
 }
@@ -494,6 +582,8 @@ const frw::R1csAgg *frw::r1cs_aggregate(const frw_r1cs *r, int *device)
 
 int frw::r1cs_device(const frw_r1cs *r) { return r->device; }
 
+bool frw::r1cs_is_circuit(const frw_r1cs *r, int circuit, int logn) { return r && !r->dev.agg && r->circuit == circuit && r->logn == logn; }
+
 extern "C" int frw_r1cs_info(const frw_r1cs *r, frw_r1cs_info_t *out)
 {
     if (!r || !out) return FRW_E_INVALID_ARG;
@@ -502,11 +592,11 @@ extern "C" int frw_r1cs_info(const frw_r1cs *r, frw_r1cs_info_t *out)
     out->num_witness = r->dev.num_witness;
     out->num_constraints = r->dev.num_constraints;
     out->log_domain_size = r->qap.log_n;
-    out->witness_map_on_device = r->qap.num_passes >= 2;
+    out->witness_map_on_device = r->qap.num_passes >= 2 || r->qap.small_tab != nullptr;
     out->count_logn9 = out->count_logn10 = 0;
     if (r->dev.agg) {
         for (int32_t l : r->statement_logn) (l == 9 ? out->count_logn9 : out->count_logn10)++;
-    } else {
+    } else if (r->logn) {                                             // (neither for a system that came in as matrices)
         (r->logn == 9 ? out->count_logn9 : out->count_logn10) = 1;
     }
     return FRW_OK;
@@ -600,10 +690,13 @@ extern "C" int frw_qap_witness_map_dev(const frw_r1cs *r, size_t batch, const ui
                                        void *stream)
 {
     if (!r || (batch && (!d_witness || !d_instance || !d_h || !d_workspace))) return FRW_E_INVALID_ARG;
-    if (r->qap.num_passes < 2) return FRW_E_INVALID_ARG;                       // no pass schedule for this domain (frw_device.h qap_pass_schedule)
+    if (r->qap.num_passes < 2 && !r->qap.small_tab) return FRW_E_INVALID_ARG;   // neither a pass schedule nor the small-domain table
     if (batch && workspace_bytes < frw::qap_workspace_bytes_per_signature(r->dev, r->qap)) return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(r->device);
-    if (e == hipSuccess)
+    if (e == hipSuccess && r->qap.small_tab)
+        e = frw::launch_qap_small(r->dev, r->qap, batch, d_witness, d_instance, d_h, d_num_unsatisfied, d_workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+    else if (e == hipSuccess)
         e = frw::launch_qap_witness_map(r->dev, r->qap, batch, d_witness, d_instance, d_h, d_num_unsatisfied, d_workspace,
                                         workspace_bytes, (hipStream_t)stream);
     return e == hipSuccess ? FRW_OK : frw::record_hip_error(e, "frw_qap_witness_map_dev");
@@ -614,10 +707,13 @@ extern "C" int frw_qap_quotient_dev(const frw_r1cs *r, size_t batch, const uint6
                                     void *stream)
 {
     if (!r || (batch && (!d_witness || !d_instance || !d_h || !d_workspace))) return FRW_E_INVALID_ARG;
-    if (r->qap.num_passes < 2) return FRW_E_INVALID_ARG;
+    if (r->qap.num_passes < 2 && !r->qap.small_tab) return FRW_E_INVALID_ARG;
     if (batch && workspace_bytes < frw::qap_workspace_bytes_per_signature(r->dev, r->qap)) return FRW_E_INVALID_ARG;
     hipError_t e = hipSetDevice(r->device);
-    if (e == hipSuccess)
+    if (e == hipSuccess && r->qap.small_tab)      // the small domains have one map: ark-groth16's as written, whatever the witness
+        e = frw::launch_qap_small(r->dev, r->qap, batch, d_witness, d_instance, d_h, d_num_unsatisfied, d_workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+    else if (e == hipSuccess)
         e = frw::launch_qap_quotient(r->dev, r->qap, batch, d_witness, d_instance, d_h, d_num_unsatisfied, d_workspace,
                                      workspace_bytes, (hipStream_t)stream);
     return e == hipSuccess ? FRW_OK : frw::record_hip_error(e, "frw_qap_quotient_dev");
@@ -629,7 +725,7 @@ extern "C" int frw_qap_witness_map(const frw_r1cs *r, size_t batch, const uint64
                                    uint64_t *h, uint32_t *num_unsatisfied)
 {
     if (!r || (batch && (!witness || !instance || !h))) return FRW_E_INVALID_ARG;
-    if (r->qap.num_passes < 2) return FRW_E_INVALID_ARG;
+    if (r->qap.num_passes < 2 && !r->qap.small_tab) return FRW_E_INVALID_ARG;
     if (batch == 0) return FRW_OK;
     const size_t n = (size_t)1 << r->qap.log_n, W = r->dev.num_witness, I = r->dev.num_instance;
     const size_t chunk = std::min<size_t>(batch, 64), per = frw::qap_workspace_bytes_per_signature(r->dev, r->qap);
@@ -646,8 +742,9 @@ extern "C" int frw_qap_witness_map(const frw_r1cs *r, size_t batch, const uint64
             hipError_t e = hipMemcpyAsync(d + o_wit, witness + lo * W * 4, cnt * W * 32, hipMemcpyHostToDevice, st);
             if (e == hipSuccess) e = hipMemcpyAsync(d + o_inst, instance + lo * I * 4, cnt * I * 32, hipMemcpyHostToDevice, st);
             if (e == hipSuccess)
-                e = frw::launch_qap_witness_map(r->dev, r->qap, cnt, (const uint64_t *)(d + o_wit), (const uint64_t *)(d + o_inst),
-                                                (uint64_t *)(d + o_h), (uint32_t *)(d + o_bad), d + o_ws, chunk * per, st);
+                e = (r->qap.small_tab ? frw::launch_qap_small : frw::launch_qap_witness_map)(
+                    r->dev, r->qap, cnt, (const uint64_t *)(d + o_wit), (const uint64_t *)(d + o_inst), (uint64_t *)(d + o_h),
+                    (uint32_t *)(d + o_bad), d + o_ws, chunk * per, st);
             return e == hipSuccess ? FRW_OK : frw::record_hip_error(e, "frw_qap_witness_map");
         });
 }
@@ -693,8 +790,9 @@ namespace {
 // variables sit in the whole (a single circuit is one block at zero)
 struct SetupBlock { const frw::host::ConstraintMatrices *m; size_t row_off, pub_off, wit_off; };
 
+// key: how the key is kept (null: window tables, as frw_groth16_pk_load makes them)
 int groth16_setup_blocks(int device, const std::vector<SetupBlock> &blocks, size_t ni, size_t nw, size_t nc, const uint64_t *toxic,
-                         frw_groth16_pk **pk_out, uint64_t *vk_out)
+                         frw_groth16_pk **pk_out, uint64_t *vk_out, const frw_groth16_key_opts_t *key = nullptr)
 {
     using namespace frw::host;
     const size_t nv = ni + nw;
@@ -789,7 +887,7 @@ int groth16_setup_blocks(int device, const std::vector<SetupBlock> &blocks, size
     d.alpha_g1 = &f1[0]; d.beta_g1 = &f1[12]; d.delta_g1 = &f1[24];
     d.beta_g2 = &f2[24]; d.delta_g2 = &f2[48];
     d.a_query = a_q.data(); d.b_g1_query = b1_q.data(); d.b_g2_query = b2_q.data(); d.h_query = h_q.data(); d.l_query = l_q.data();
-    rc = frw_groth16_pk_load(device, &d, pk_out);
+    rc = key ? frw_groth16_pk_load_opts(device, &d, key, pk_out) : frw_groth16_pk_load(device, &d, pk_out);
     if (rc == FRW_OK && vk_out) {
         std::memcpy(vk_out, &f1[0], 96);                       // alpha_g1
         std::memcpy(vk_out + 12, &f2[24], 192);                // beta_g2
@@ -1064,6 +1162,13 @@ extern "C" int frw_groth16_setup_r1cs_opts(const frw_r1cs *r, const uint64_t *to
             if (on_host)
                 return groth16_setup_blocks(r->device, {SetupBlock{&m, 0, 0, 0}}, m.num_instance_variables, m.num_witness_variables, m.num_constraints,
                                             toxic, pk_out, vk_out);
+            // below 2^14 the host makes the key, of either kind: the device's power tables start at 2^14 entries, and such a system is a
+            // moment's work
+            if (domain_log(m.num_constraints + m.num_instance_variables) < frw::SETUP_POW_LO_BITS) {
+                const frw_groth16_key_opts_t key = {mode, rank, world};
+                return groth16_setup_blocks(r->device, {SetupBlock{&m, 0, 0, 0}}, m.num_instance_variables, m.num_witness_variables, m.num_constraints,
+                                            toxic, pk_out, vk_out, &key);
+            }
             return groth16_setup_device(r->device, {DeviceRun{&m, 0, 1, 0, 0, 0}}, 1, m.num_instance_variables, m.num_witness_variables,
                                         m.num_constraints, toxic, mode == FRW_KEY_TABLES, rank, world, pk_out, vk_out);
         }

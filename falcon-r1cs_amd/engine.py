@@ -6,6 +6,7 @@ hand over (sig, pk, hm) coefficient vectors, receive ``witness_assignment`` / ``
 of every signature in arkworks order.  torch is used only to own device memory and streams.
 """
 import ctypes as C
+import os
 import weakref
 from dataclasses import dataclass
 
@@ -807,6 +808,29 @@ class WitnessEngine:
         """Device-resident A/B/C of circuit 0 (NTT) / 1 (dual NTT) / 2 (schoolbook) for r1cs_check_dev; free with r1cs_free."""
         h = C.c_void_p()
         check(self._lib.frw_r1cs_load(self.device, circuit, logn, C.byref(h)), "frw_r1cs_load")
+        return h
+
+    def r1cs_load_csr(self, num_instance, num_witness, matrices):
+        """A handle for ANY constraint system: matrices = three (row_ptr uint64[C + 1], col uint32[nnz], val uint64[nnz][4] canonical)
+        for A, B, C -- the arrays of the FRWR1CS1 file (column 0 the constant one, 1 .. I - 1 the public inputs, I + k witness k).  The
+        handle goes wherever an r1cs_load handle goes but into the calls that start from Falcon signatures; free with r1cs_free."""
+        if len(matrices) != 3:
+            raise ValueError("three matrices: A, B, C")
+        ptr = [np.ascontiguousarray(m[0], dtype=np.uint64) for m in matrices]
+        col = [np.ascontiguousarray(m[1], dtype=np.uint32) for m in matrices]
+        val = [np.ascontiguousarray(m[2], dtype=np.uint64).reshape(-1, 4) for m in matrices]
+        if any(len(c) != len(v) for c, v in zip(col, val)) or any(len(p) != len(ptr[0]) or len(p) == 0 for p in ptr):
+            raise ValueError("col and val of a matrix have one entry per term; the three row_ptr have C + 1 entries")
+        counts = (C.c_uint64 * 6)(num_instance, num_witness, len(ptr[0]) - 1, len(col[0]), len(col[1]), len(col[2]))
+        three = lambda arrs: (C.c_void_p * 3)(*[a.ctypes.data_as(C.c_void_p) for a in arrs])
+        h = C.c_void_p()
+        check(self._lib.frw_r1cs_load_csr(self.device, counts, three(ptr), three(col), three(val), C.byref(h)), "frw_r1cs_load_csr")
+        return h
+
+    def r1cs_load_file(self, path):
+        """The same from an FRWR1CS1 file (what r1cs_export writes, or any system written in that layout)."""
+        h = C.c_void_p()
+        check(self._lib.frw_r1cs_load_file(self.device, os.fsencode(str(path)), C.byref(h)), "frw_r1cs_load_file")
         return h
 
     def r1cs_free(self, handle):

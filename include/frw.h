@@ -326,6 +326,33 @@ int frw_r1cs_eval_scratch_dev(const frw_r1cs *r, size_t batch, const uint64_t *d
                               uint32_t *d_num_unsatisfied, uint64_t *d_abc, void *d_scratch, size_t scratch_bytes,
                               void *stream);
 
+/* ---- any constraint system: A, B, C as CSR arrays, or the FRWR1CS1 file frw_r1cs_export writes ------------------------------
+ * Everything behind a `frw_r1cs *` -- the satisfaction check and A z, B z, C z, the witness map, frw_groth16_setup_r1cs(_opts),
+ * the prove / partial / verify / wire / re-randomise calls and their keys -- is Groth16 over BLS12-381 for the system the handle holds;
+ * these two make a handle from matrices that come from anywhere (a Rust host: ark-relations' cs.to_matrices()).
+ *     counts   {I, W, C, nnz_A, nnz_B, nnz_C}
+ *     for m = 0, 1, 2 (A, B, C): row_ptr[m] u64[C + 1], col[m] u32[nnz_m], val[m] u64[nnz_m][4] canonical little-endian -- the
+ *     arrays of the file, in host memory (read during the call only)
+ * Columns as in the export: 0 is the constant one, 1 .. I - 1 the public inputs, I + k witness k.  Every consumer's buffers are
+ * witness uint64_t[batch][W][4] and instance uint64_t[batch][I][4] in ark-ff's Montgomery bytes, element 0 of the instance = one;
+ * every element canonical (limbs < p) -- the precondition of frw_qap_witness_map_dev below holds for these handles too.
+ * Accepted on purpose: unsorted columns, a column repeated within a row (the terms add), zero coefficients, empty rows, variables no
+ * row mentions (their a_query, b_*_query and l_query entries are the point at infinity).
+ * Refused with FRW_E_INVALID_ARG before any device call, frw_last_error() naming the matrix and the row: a null pointer; I == 0 or
+ * C == 0; I + W >= 2^30 or C + I > 2^30; row_ptr[m][0] != 0, a decreasing row_ptr, row_ptr[m][C] != nnz_m; a column >= I + W; a
+ * value >= the group order; and for files one that cannot be opened, another magic, or a length that is not exactly what the
+ * header implies.  Validation comes first, then the device: without a GPU a malformed system is FRW_E_INVALID_ARG and a
+ * well-formed one FRW_E_NO_DEVICE.
+ * The QAP domain is next_power_of_two(C + I), as ark-groth16 takes it (the key depends on it): 2^1 .. 2^30, every one of them with
+ * a witness map on the device (below 2^14: frw_qap_small.hip).
+ * What stays Falcon-only: the witness kernels, and with them frw_pok_prove_from_bytes(_dev), frw_pok_prove_workspace_bytes (0) and
+ * the aggregate calls -- they refuse these handles, also one whose counts are a Falcon circuit's (the export loaded back).
+ * frw_r1cs_info reports num_statements = 1 and count_logn9 = count_logn10 = 0 for them: how a caller tells them from
+ * frw_r1cs_load's. */
+int frw_r1cs_load_csr(int device, const uint64_t counts[6], const uint64_t *const row_ptr[3], const uint32_t *const col[3],
+                      const uint64_t *const val[3], frw_r1cs **out);
+int frw_r1cs_load_file(int device, const char *path, frw_r1cs **out);
+
 /* ---- QAP witness map (the step after the hot path in a Groth16 prover) ------------------------------------------
  * examples/pok_sig.rs:30-47 hands the circuit to Groth16::<Bls12_381>::prove; after generate_constraints the prover's
  * first step is ark-groth16 0.3.0's R1CStoQAP::witness_map (r1cs_to_qap.rs): the coefficients of
@@ -341,7 +368,10 @@ int frw_r1cs_eval_scratch_dev(const frw_r1cs *r, size_t batch, const uint64_t *d
  *     d_num_unsatisfied optional uint32_t[batch]: constraint rows the witness violates (h is then not a quotient)
  *     d_workspace       at least workspace_bytes_per_signature bytes; the batch is processed in chunks of as many
  *                       signatures as fit.
- * Returns FRW_E_INVALID_ARG for a null pointer, a workspace smaller than one signature's, or a domain outside 2^14 .. 2^30
+ * Returns FRW_E_INVALID_ARG for a null pointer, a workspace smaller than one signature's, or a domain outside 2^1 .. 2^30.
+ * Domains 2^1 .. 2^13 (systems loaded by frw_r1cs_load_csr / frw_r1cs_load_file; tests/test_gpu_r1cs_custom.py): ark-groth16's seven
+ * transforms as written for every statement, plain radix-2 stages, one workgroup per array -- in LDS up to 2^12, through the workspace
+ * at 2^13 (frw_qap_small.hip); same buffers, same workspace formula, same properties.  From 2^14
  * (the transforms run as passes of six, five or four radix-2 stages: 2^17 = 6 + 6 + 5 and 2^18 = 6 + 6 + 6 for the Falcon
  * circuits, 2^19 = 6 + 5 + 4 + 4 .. 2^24 = 6 + 6 + 6 + 6, 2^25 = 6 + 5 + 5 + 5 + 4 .. 2^27 = 6 + 6 + 5 + 5 + 5 for aggregate statements.
  * RUN AND TESTED: every domain 2^17 .. 2^27 (tests/test_gpu_qap.py, tests/test_gpu_aggregate.py) -- 2^27 is the 1,024-statement
@@ -368,7 +398,8 @@ int frw_qap_witness_map_dev(const frw_r1cs *r, size_t batch, const uint64_t *d_w
  * products on the domain, the second from those on the coset psi H, psi^n = -1; C z is computed for d_num_unsatisfied but
  * not transformed.  d_num_unsatisfied[i] == 0  =>  d_h[i] is exactly frw_qap_witness_map_dev's (ark-groth16's) h.
  * Otherwise d_h[i] is still hi, which is NOT what ark-groth16 returns for an unsatisfied system (nor a quotient).
- * Same arguments and workspace as frw_qap_witness_map_dev. */
+ * Same arguments and workspace as frw_qap_witness_map_dev.  On the domains below 2^14 there is one map: this call returns
+ * frw_qap_witness_map_dev's h there, for every witness. */
 int frw_qap_quotient_dev(const frw_r1cs *r, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
                          uint64_t *d_h, uint32_t *d_num_unsatisfied, void *d_workspace, size_t workspace_bytes,
                          void *stream);
@@ -412,11 +443,11 @@ int frw_r1cs_diag_host_allocations(const frw_r1cs *r, uint64_t *count);
  * statements of BASELINE configs[4] (513 Falcon-512 + 511 Falcon-1024: C + I = 126.6 M, the 2^27 domain -- round 4 had written 2^28
  * and 480 GB here, both wrong) are 121.9 M variables, 83 GB of points, ONE proof in 0.6 s on one MI355X. */
 typedef struct {
-    uint64_t num_statements;                    /* 1 for the handles of frw_r1cs_load */
-    uint64_t count_logn9, count_logn10;
+    uint64_t num_statements;                    /* 1 for the handles of frw_r1cs_load, frw_r1cs_load_csr and frw_r1cs_load_file */
+    uint64_t count_logn9, count_logn10;         /* both 0: a system that came in as matrices (frw_r1cs_load_csr / _file) */
     uint64_t num_instance, num_witness, num_constraints;    /* I (with the constant one), W, C of the whole system */
     int32_t log_domain_size;
-    int32_t witness_map_on_device;              /* 0: the device has no transform schedule for this domain (2^14 .. 2^30 have) */
+    int32_t witness_map_on_device;              /* 0: the device has no transform for this domain (2^1 .. 2^30 have) */
 } frw_r1cs_info_t;
 int frw_r1cs_load_aggregate(int device, size_t count, const int32_t *logn, frw_r1cs **out);
 int frw_r1cs_info(const frw_r1cs *r, frw_r1cs_info_t *out);

@@ -263,6 +263,8 @@ extern "C" {
                                          status: *mut i32, strict: c_int) -> c_int;
     pub fn frw_r1cs_export(circuit: c_int, logn: c_int, path: *const c_char, counts: *mut u64) -> c_int;
     pub fn frw_r1cs_load(device: c_int, circuit: c_int, logn: c_int, out: *mut *mut frw_r1cs) -> c_int;
+    pub fn frw_r1cs_load_csr(device: c_int, counts: *const u64, row_ptr: *const *const u64, col: *const *const u32, val: *const *const u64, out: *mut *mut frw_r1cs) -> c_int;
+    pub fn frw_r1cs_load_file(device: c_int, path: *const c_char, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_free(r: *mut frw_r1cs);
     pub fn frw_r1cs_load_aggregate(device: c_int, count: usize, logn: *const i32, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_info(r: *const frw_r1cs, out: *mut frw_r1cs_info_t) -> c_int;

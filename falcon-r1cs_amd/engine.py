@@ -23,6 +23,137 @@ E_RANGE = -5
 G_LESS_THAN_Q, G_MOD_Q, G_ADD_MOD, G_L2_ELEM, G_NORM_BOUND_512, G_NORM_BOUND_1024 = range(6)
 CIRCUIT_NTT, CIRCUIT_DUAL_NTT, CIRCUIT_SCHOOLBOOK = 0, 1, 2
 RULE_CIRCUIT, RULE_SPEC = 0, 1          # FRW_RULE_*: how falcon_verify* centres a coefficient and compares the norm
+WIRE_COMPRESSED, WIRE_UNCOMPRESSED = 0, 1      # frw.h FRW_WIRE_*
+VERIFY_POINTS_ARE_CHECKED = 1
+VERIFY_BATCHED = 2
+
+
+# ---- what every entry point below does the same way: pointers, packed inputs, uploads, workspaces, refusals ------------------------
+# torch is imported inside the helpers that own device memory, so that the host-only paths never need it.
+def _p(x):
+    """The one pointer rule: None, an address, a numpy array, or anything with data_ptr() (a torch tensor) -> a void* argument."""
+    if x is None:
+        return None
+    if isinstance(x, int):
+        return C.c_void_p(x)
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data_as(C.c_void_p)
+    return C.c_void_p(x.data_ptr())
+
+
+def _wire_mode(compressed):
+    return WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+
+
+def proof_wire_bytes(compressed=True):
+    return 192 if compressed else 384
+
+
+def _pack(keys, second, msgs):
+    """Encoded inputs as the *_from_bytes calls read them: the keys end to end, the `second` items (signatures or nonces) end to end,
+    the message blob (uint8 arrays; one zero byte for an empty join, so that each has an address) and the blob's uint64[batch + 1]
+    offsets.  The callers check the lengths."""
+    join = lambda items: np.frombuffer(b"".join(bytes(x) for x in items) or b"\0", dtype=np.uint8)
+    off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(m) for m in msgs])
+    return join(keys), join(second), join(msgs), off
+
+
+def _empty(shape, dtype, device):
+    """An uninitialised device tensor: dtype by name, device a torch.device or a HIP device index."""
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=device if isinstance(device, torch.device) else torch.device("cuda", device))
+
+
+def _upload(arrays, device):
+    """numpy arrays -> tensors on HIP device `device`, each copied once; a uint64 array goes as int64, which torch has."""
+    import torch
+    dev = torch.device("cuda", device)
+    return [torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a).copy()).to(dev) for a in arrays]
+
+
+def _encoded_dev(device, logn, pk_bytes, second, msgs, sig_len, pack):
+    """The encoded inputs of a *_from_bytes_dev call -> (batch, sig_len, d_pkb, d_second, d_blob, d_off).  Device tensors (msgs a
+    (blob, offsets) pair) pass through, a sig_len of None worked out from them; host lists go through `pack` (_statement_bytes, or
+    _falcon_verify_bytes, which also says the sig_len) and are uploaded.  The caller holds the tensors until its C call has returned."""
+    import torch
+    if isinstance(pk_bytes, torch.Tensor):
+        d_blob, d_off = msgs
+        batch = pk_bytes.numel() // PK_LEN[logn]
+        if sig_len is None:
+            sig_len = second.numel() // batch if batch else SIG_LEN[logn]
+        return batch, sig_len, pk_bytes, second, d_blob, d_off
+    batch, *packed_len, pkb, sec, blob, off = pack(logn, pk_bytes, second, msgs)
+    return (batch, packed_len[0] if packed_len else sig_len, *_upload((pkb, sec, blob, off), device))
+
+
+def _wire_dev(wire, device):
+    """Wire bytes (a tensor, bytes, or anything numpy reads as uint8) -> the flat uint8 tensor on HIP device `device`."""
+    import torch
+    dev = torch.device("cuda", device)
+    if isinstance(wire, torch.Tensor):
+        return wire.to(dev).contiguous().view(torch.uint8).reshape(-1)
+    raw = wire if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire, dtype=np.uint8).tobytes()
+    return torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+
+
+def _wire_batch(d_wire, compressed, where):
+    """The number of proofs in d_wire; FrwError in the name of `where` unless it is a contiguous uint8 tensor of whole proofs."""
+    import torch
+    per = proof_wire_bytes(compressed)
+    if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
+        raise FrwError(-1, where, "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
+    return d_wire.numel() // per
+
+
+def _workspace(workspace, device, floor, needed_bytes, *args):
+    """(workspace tensor, its bytes): the caller's, or a fresh uint8 one of needed_bytes(*args) bytes, `floor` at the least."""
+    if workspace is None:
+        workspace = _empty(max(needed_bytes(*args), floor), "uint8", device)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def _batched_seed(flags, batched, seed):
+    """(flags with VERIFY_BATCHED where `batched`, the batched check's seed as 4 uint64 -- 32 fresh random bytes for None -- or None
+    where that check is off)."""
+    flags = int(flags) | (VERIFY_BATCHED if batched else 0)
+    if not flags & VERIFY_BATCHED:
+        return flags, None
+    if seed is None:
+        return flags, np.frombuffer(os.urandom(32), dtype=np.uint64).copy()
+    return flags, np.ascontiguousarray(seed, dtype=np.uint64).reshape(4)
+
+
+def _refusal(status, noun, verdict="refused", head="Invalid input"):
+    """The message that names the first 8 slots of `status` (a numpy array or a tensor) that are not zero, and their statuses."""
+    st = np.asarray(status.tolist())
+    bad = np.nonzero(st)[0]
+    return "%s: %s %s %s (status %s)" % (head, noun, bad[:8], verdict, st[bad][:8])
+
+
+def _check_refusal(rc, where, status, noun, verdict="refused"):
+    """check(rc, where), with FRW_E_RANGE raised as the FrwError that says which slots were refused."""
+    if rc == E_RANGE:
+        raise FrwError(rc, where, _refusal(status, noun, verdict))
+    check(rc, where)
+
+
+_VK_KEYS = ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")
+
+
+def _vk_flat(vk, where):
+    """A verifying key (the dict groth16_setup returns, or flat limbs) -> (the flat uint64 array of frw_groth16_setup's vk_out, its
+    num_instance); FrwError in the name of `where` for a length no key has."""
+    if isinstance(vk, dict):
+        vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in _VK_KEYS])
+    vk = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
+    if vk.size < 96 or (vk.size - 84) % 12:
+        raise FrwError(-1, where, "verifying key: expected 84 + 12 x num_instance uint64 values")
+    return vk, (vk.size - 84) // 12
+
+
+def _vk_dict(vk):
+    return {"alpha_g1": vk[:12], "beta_g2": vk[12:36], "gamma_g2": vk[36:60], "delta_g2": vk[60:84], "gamma_abc_g1": vk[84:].reshape(-1, 12)}
 
 
 @dataclass(frozen=True)
@@ -133,8 +264,7 @@ def expand_field_host(p, logn, compact):
     batch = compact.shape[0]
     wit = np.empty((batch, L.num_witness, 4), dtype=np.uint64)
     inst = np.empty((batch, L.num_instance, 4), dtype=np.uint64)
-    q = lambda a: a.ctypes.data_as(C.c_void_p)
-    check(load_library().frw_expand_field_host(_limbs4(p), logn, batch, q(compact), q(wit), q(inst)), "frw_expand_field_host")
+    check(load_library().frw_expand_field_host(_limbs4(p), logn, batch, _p(compact), _p(wit), _p(inst)), "frw_expand_field_host")
     return wit, inst
 
 
@@ -142,13 +272,10 @@ def synth_triples(logn, batch, seed=0x46414C434F4E, first_index=0):
     """Synthetic valid (sig, pk, hm) -- frw_synth_triples; uint16 arrays of shape [batch, N]."""
     n = 1 << logn
     out = [np.empty((batch, n), dtype=np.uint16) for _ in range(3)]
-    check(load_library().frw_synth_triples(int(logn), batch, seed, first_index,
-                                           *[a.ctypes.data_as(C.c_void_p) for a in out]), "frw_synth_triples")
+    check(load_library().frw_synth_triples(int(logn), batch, seed, first_index, *[_p(a) for a in out]), "frw_synth_triples")
     return tuple(out)
 
 
-VERIFY_POINTS_ARE_CHECKED = 1
-VERIFY_BATCHED = 2
 RERAND_ZERO_FACTOR = -2                            # frw.h FRW_RERAND_ZERO_FACTOR
 VK_POINTS_ARE_CHECKED = 1
 KEY_AUTO, KEY_TABLES, KEY_BARE = 0, 1, 2           # frw.h FRW_KEY_*: window tables, or the points only (keys that would not fit)
@@ -165,20 +292,14 @@ class Groth16Verifier:
 
     def __init__(self, vk, points_are_checked=False, device=None):
         self._lib = load_library()
-        if isinstance(vk, dict):
-            vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
-        vk = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
-        if vk.size < 96 or (vk.size - 84) % 12:
-            raise FrwError("verifying key: expected 84 + 12 x num_instance uint64 values")
-        self.num_instance = (vk.size - 84) // 12
+        vk, self.num_instance = _vk_flat(vk, "Groth16Verifier")
         self.device = device
         self._h = C.c_void_p()
         flags = VK_POINTS_ARE_CHECKED if points_are_checked else 0
         if device is None:
-            check(self._lib.frw_groth16_vk_load_opts(vk.ctypes.data_as(C.c_void_p), self.num_instance, flags, C.byref(self._h)),
-                  "frw_groth16_vk_load")
+            check(self._lib.frw_groth16_vk_load_opts(_p(vk), self.num_instance, flags, C.byref(self._h)), "frw_groth16_vk_load")
         else:
-            check(self._lib.frw_groth16_vk_load_dev(int(device), vk.ctypes.data_as(C.c_void_p), self.num_instance, flags, C.byref(self._h)),
+            check(self._lib.frw_groth16_vk_load_dev(int(device), _p(vk), self.num_instance, flags, C.byref(self._h)),
                   "frw_groth16_vk_load_dev")
 
     def verify(self, instance, proofs, encoding=ENC_MONTGOMERY, flags=0):
@@ -187,32 +308,24 @@ class Groth16Verifier:
         proofs = np.ascontiguousarray(proofs).view(np.uint64).reshape(-1, 48)
         instance = np.ascontiguousarray(instance).view(np.uint64).reshape(proofs.shape[0], self.num_instance, 4)
         out = np.zeros(proofs.shape[0], dtype=np.int32)
-        check(self._lib.frw_groth16_verify(self._h, proofs.shape[0], instance.ctypes.data_as(C.c_void_p), int(encoding),
-                                           proofs.ctypes.data_as(C.c_void_p), int(flags), out.ctypes.data_as(C.c_void_p)), "frw_groth16_verify")
+        check(self._lib.frw_groth16_verify(self._h, proofs.shape[0], _p(instance), int(encoding), _p(proofs), int(flags), _p(out)),
+              "frw_groth16_verify")
         return out
 
     def workspace_bytes(self, batch_in_flight):
         """Device workspace for `batch_in_flight` proofs (frw_groth16_verify_workspace_bytes; 0 for a host-only key)."""
         return int(self._lib.frw_groth16_verify_workspace_bytes(self._h, int(batch_in_flight)))
 
-    def _workspace(self, batch, workspace):
-        import torch
-        if workspace is None:
-            workspace = torch.empty(max(self.workspace_bytes(batch), 16), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        return workspace, workspace.numel() * workspace.element_size()
-
     def prepare_inputs_dev(self, d_instance, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
         """d_instance: device tensor [batch, num_instance, 4] of 64-bit limbs -> (prepared int64[batch, 12] in ark-ff's bytes,
         status int32[batch]: 0 or -1 malformed), device tensors, ordered on `stream`."""
-        import torch
         batch = d_instance.shape[0]
         dev = d_instance.device
-        prepared = torch.empty((batch, 12), dtype=torch.int64, device=dev)
-        status = torch.empty(batch, dtype=torch.int32, device=dev)
-        ws, ws_bytes = self._workspace(batch, workspace)
-        check(self._lib.frw_groth16_prepare_inputs_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding), C.c_void_p(prepared.data_ptr()),
-                                                       C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(stream)),
-              "frw_groth16_prepare_inputs_dev")
+        prepared = _empty((batch, 12), "int64", dev)
+        status = _empty(batch, "int32", dev)
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.workspace_bytes, batch)
+        check(self._lib.frw_groth16_prepare_inputs_dev(self._h, batch, _p(d_instance), int(encoding), _p(prepared), _p(status), _p(ws),
+                                                       ws_bytes, C.c_void_p(stream)), "frw_groth16_prepare_inputs_dev")
         return prepared, status
 
     def verify_dev(self, d_instance, d_proofs, encoding=ENC_MONTGOMERY, flags=0, stream=0, workspace=None):
@@ -221,10 +334,9 @@ class Groth16Verifier:
         workspace: a device tensor (16-byte aligned) or None for one of the whole batch."""
         batch = d_proofs.shape[0]
         out = np.zeros(batch, dtype=np.int32)
-        ws, ws_bytes = self._workspace(batch, workspace)
-        check(self._lib.frw_groth16_verify_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding), C.c_void_p(d_proofs.data_ptr()),
-                                               int(flags), out.ctypes.data_as(C.c_void_p), C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(stream)),
-              "frw_groth16_verify_dev")
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.workspace_bytes, batch)
+        check(self._lib.frw_groth16_verify_dev(self._h, batch, _p(d_instance), int(encoding), _p(d_proofs), int(flags), _p(out), _p(ws),
+                                               ws_bytes, C.c_void_p(stream)), "frw_groth16_verify_dev")
         return out
 
     def full_workspace_bytes(self, batch_in_flight, flags=0):
@@ -238,23 +350,12 @@ class Groth16Verifier:
         synchronising.  batched: the batched check first (FRW_VERIFY_BATCHED); seed: 4 uint64 (None: 32 fresh random bytes, drawn now,
         after the proofs); batch_passed: an optional device int32 tensor of one element that receives whether the batched check passed.
         workspace: a device tensor (16-byte aligned) or None for one of the whole batch."""
-        import os
-        import torch
         batch = d_proofs.shape[0]
-        flags = int(flags) | (VERIFY_BATCHED if batched else 0)
-        out = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
-        seed_arr = None
-        if flags & VERIFY_BATCHED:
-            seed_arr = np.frombuffer(os.urandom(32), dtype=np.uint64).copy() if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(4)
-        if workspace is None:
-            workspace = torch.empty(max(self.full_workspace_bytes(batch, flags), 16), dtype=torch.uint8, device=d_proofs.device)
-        ws_bytes = workspace.numel() * workspace.element_size()
-        check(self._lib.frw_groth16_verify_full_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding),
-                                                    C.c_void_p(d_proofs.data_ptr()), flags,
-                                                    None if seed_arr is None else seed_arr.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
-                                                    None if batch_passed is None else C.c_void_p(batch_passed.data_ptr()),
-                                                    C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
-              "frw_groth16_verify_full_dev")
+        out = _empty(batch, "int32", d_proofs.device)
+        flags, seed_arr = _batched_seed(flags, batched, seed)
+        ws, ws_bytes = _workspace(workspace, d_proofs.device, 16, self.full_workspace_bytes, batch, flags)
+        check(self._lib.frw_groth16_verify_full_dev(self._h, batch, _p(d_instance), int(encoding), _p(d_proofs), flags, _p(seed_arr), _p(out),
+                                                    _p(batch_passed), _p(ws), ws_bytes, C.c_void_p(stream)), "frw_groth16_verify_full_dev")
         return out
 
     @classmethod
@@ -267,7 +368,7 @@ class Groth16Verifier:
         self._h = C.c_void_p()
         self.device = device
         data = bytes(data)
-        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
+        mode = _wire_mode(compressed)
         head = 336 if compressed else 672
         self.num_instance = int.from_bytes(data[head:head + 8], "little") if len(data) >= head + 8 else 0
         buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
@@ -279,34 +380,19 @@ class Groth16Verifier:
 
     def wire_workspace_bytes(self, batch_in_flight, flags=0, compressed=True):
         """Device workspace of verify_wire_dev for `batch_in_flight` proofs (0 for a host-only key)."""
-        return int(self._lib.frw_groth16_verify_wire_workspace_bytes(self._h, int(batch_in_flight), int(flags),
-                                                                     WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED))
+        return int(self._lib.frw_groth16_verify_wire_workspace_bytes(self._h, int(batch_in_flight), int(flags), _wire_mode(compressed)))
 
     def verify_wire_dev(self, d_instance, d_wire, compressed=True, encoding=ENC_MONTGOMERY, flags=0, batched=False, seed=None, stream=0,
                         workspace=None, batch_passed=None):
         """verify_full_dev with the proofs as ark-serialize's bytes (frw_groth16_verify_wire_dev): d_wire is a device uint8 tensor
         [batch, 192] (compressed) or [batch, 384]; decoded on the device, -1 where the bytes are malformed, otherwise
         verify_full_dev's verdict for the decoded proof.  Everything else as verify_full_dev."""
-        import os
-        import torch
-        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
-        per = 192 if compressed else 384
-        if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
-            raise FrwError(-1, "verify_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
-        batch = d_wire.numel() // per
-        flags = int(flags) | (VERIFY_BATCHED if batched else 0)
-        out = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
-        seed_arr = None
-        if flags & VERIFY_BATCHED:
-            seed_arr = np.frombuffer(os.urandom(32), dtype=np.uint64).copy() if seed is None else np.ascontiguousarray(seed, dtype=np.uint64).reshape(4)
-        if workspace is None:
-            workspace = torch.empty(max(self.wire_workspace_bytes(batch, flags, compressed), 16), dtype=torch.uint8, device=d_wire.device)
-        ws_bytes = workspace.numel() * workspace.element_size()
-        check(self._lib.frw_groth16_verify_wire_dev(self._h, batch, C.c_void_p(d_instance.data_ptr()), int(encoding),
-                                                    C.c_void_p(d_wire.data_ptr()), mode, flags,
-                                                    None if seed_arr is None else seed_arr.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
-                                                    None if batch_passed is None else C.c_void_p(batch_passed.data_ptr()),
-                                                    C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
+        batch = _wire_batch(d_wire, compressed, "verify_wire_dev")
+        out = _empty(batch, "int32", d_wire.device)
+        flags, seed_arr = _batched_seed(flags, batched, seed)
+        ws, ws_bytes = _workspace(workspace, d_wire.device, 16, self.wire_workspace_bytes, batch, flags, compressed)
+        check(self._lib.frw_groth16_verify_wire_dev(self._h, batch, _p(d_instance), int(encoding), _p(d_wire), _wire_mode(compressed), flags,
+                                                    _p(seed_arr), _p(out), _p(batch_passed), _p(ws), ws_bytes, C.c_void_p(stream)),
               "frw_groth16_verify_wire_dev")
         return out
 
@@ -317,13 +403,7 @@ class Groth16Verifier:
         statements are made on the device by `engine` (a WitnessEngine on this key's device: statement_from_bytes_dev) and go to
         verify_wire_dev as they are; batched / seed / flags are passed through.  Returns (statuses, verdicts), device int32 tensors
         [batch]: FRW_ST_* of the statement and 1 / 0 / -1 -- a refused statement is a zero-filled instance vector, hence -1."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(wire, torch.Tensor):
-            d_wire = wire.to(dev).contiguous().view(torch.uint8).reshape(-1)
-        else:
-            raw = wire if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire, dtype=np.uint8).tobytes()
-            d_wire = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+        d_wire = _wire_dev(wire, self.device)
         d_inst, d_status = engine.statement_from_bytes_dev(circuit, logn, pk_bytes, nonces, msgs, ENC_MONTGOMERY, stream)
         verdicts = self.verify_wire_dev(d_inst, d_wire, compressed, ENC_MONTGOMERY, flags, batched, seed, stream)
         return d_status, verdicts
@@ -334,13 +414,7 @@ class Groth16Verifier:
         (aggregate_statement_from_bytes_dev on `handle`, the constraint system this key was set up for) and goes to verify_wire_dev as
         it is.  Returns (statuses int32[count], verdict int32[1]) device tensors: a refused statement leaves zeros in its slots, an
         instance vector that is well formed and verifies against no proof."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(wire, torch.Tensor):
-            d_wire = wire.to(dev).contiguous().view(torch.uint8).reshape(-1)
-        else:
-            raw = wire if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire, dtype=np.uint8).tobytes()
-            d_wire = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev)
+        d_wire = _wire_dev(wire, self.device)
         d_inst, d_status = engine.aggregate_statement_from_bytes_dev(handle, pk_bytes, nonces, msgs, ENC_MONTGOMERY, stream)
         verdict = self.verify_wire_dev(d_inst.reshape(1, -1, 4), d_wire, compressed, ENC_MONTGOMERY, flags, False, None, stream)
         return d_status, verdict
@@ -356,8 +430,8 @@ class Groth16Verifier:
         factors = np.ascontiguousarray(factors).view(np.uint64).reshape(batch, 2, 4)
         out = np.zeros((batch, 48), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
-        check(self._lib.frw_groth16_rerandomize(self._h, batch, proofs.ctypes.data_as(C.c_void_p), factors.ctypes.data_as(C.c_void_p), int(flags),
-                                                out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_rerandomize")
+        check(self._lib.frw_groth16_rerandomize(self._h, batch, _p(proofs), _p(factors), int(flags), _p(out), _p(status)),
+              "frw_groth16_rerandomize")
         return out, status
 
     def rerandomize_workspace_bytes(self, in_flight, wire_mode=None):
@@ -371,16 +445,12 @@ class Groth16Verifier:
         synchronised or allocated by the call itself: capture-safe when `out` and `workspace` are given.  out may be d_proofs (in
         place); workspace: a device tensor (16-byte aligned) or None for one of the whole batch -- a smaller one runs the batch in
         chunks."""
-        import torch
         batch = d_proofs.shape[0]
         if out is None:
-            out = torch.empty((batch, 48), dtype=torch.int64, device=d_proofs.device)
-        status = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
-        if workspace is None:
-            workspace = torch.empty(max(self.rerandomize_workspace_bytes(batch), 16), dtype=torch.uint8, device=d_proofs.device)
-        ws_bytes = workspace.numel() * workspace.element_size()
-        check(self._lib.frw_groth16_rerandomize_dev(self._h, batch, C.c_void_p(d_proofs.data_ptr()), C.c_void_p(d_factors.data_ptr()), int(flags),
-                                                    C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()),
+            out = _empty((batch, 48), "int64", d_proofs.device)
+        status = _empty(batch, "int32", d_proofs.device)
+        ws, ws_bytes = _workspace(workspace, d_proofs.device, 16, self.rerandomize_workspace_bytes, batch)
+        check(self._lib.frw_groth16_rerandomize_dev(self._h, batch, _p(d_proofs), _p(d_factors), int(flags), _p(out), _p(status), _p(ws),
                                                     ws_bytes, C.c_void_p(stream)), "frw_groth16_rerandomize_dev")
         return out, status
 
@@ -388,22 +458,14 @@ class Groth16Verifier:
         """rerandomize_dev with the proofs as ark-serialize's bytes, in and out (frw_groth16_rerandomize_wire_dev): d_wire a device
         uint8 tensor of batch x 192 (compressed) or 384 bytes.  Returns (bytes uint8[batch, 192 or 384], status int32[batch]); -1 also
         where the decoder refuses the bytes; a refused slot is all zero bytes.  out may be d_wire."""
-        import torch
-        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
-        per = 192 if compressed else 384
-        if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
-            raise FrwError(-1, "rerandomize_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
-        batch = d_wire.numel() // per
+        mode = _wire_mode(compressed)
+        batch = _wire_batch(d_wire, compressed, "rerandomize_wire_dev")
         if out is None:
-            out = torch.empty((batch, per), dtype=torch.uint8, device=d_wire.device)
-        status = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
-        if workspace is None:
-            workspace = torch.empty(max(self.rerandomize_workspace_bytes(batch, mode), 16), dtype=torch.uint8, device=d_wire.device)
-        ws_bytes = workspace.numel() * workspace.element_size()
-        check(self._lib.frw_groth16_rerandomize_wire_dev(self._h, batch, C.c_void_p(d_wire.data_ptr()), mode, C.c_void_p(d_factors.data_ptr()),
-                                                         int(flags), C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()),
-                                                         C.c_void_p(workspace.data_ptr()), ws_bytes, C.c_void_p(stream)),
-              "frw_groth16_rerandomize_wire_dev")
+            out = _empty((batch, proof_wire_bytes(compressed)), "uint8", d_wire.device)
+        status = _empty(batch, "int32", d_wire.device)
+        ws, ws_bytes = _workspace(workspace, d_wire.device, 16, self.rerandomize_workspace_bytes, batch, mode)
+        check(self._lib.frw_groth16_rerandomize_wire_dev(self._h, batch, _p(d_wire), mode, _p(d_factors), int(flags), _p(out), _p(status),
+                                                         _p(ws), ws_bytes, C.c_void_p(stream)), "frw_groth16_rerandomize_wire_dev")
         return out, status
 
     def close(self):
@@ -418,13 +480,6 @@ class Groth16Verifier:
             pass
 
 
-WIRE_COMPRESSED, WIRE_UNCOMPRESSED = 0, 1      # frw.h FRW_WIRE_*
-
-
-def proof_wire_bytes(compressed=True):
-    return 192 if compressed else 384
-
-
 def proofs_to_wire(proofs, compressed=True):
     """Proofs in limbs (uint64[batch, 48], as the prover writes them) -> (uint8[batch, 192 or 384] in ark-serialize's format, what
     Proof::deserialize / deserialize_uncompressed reads; int32[batch] status: -1 and zero bytes where a coordinate's limbs are >= q).
@@ -432,8 +487,8 @@ def proofs_to_wire(proofs, compressed=True):
     proofs = np.ascontiguousarray(proofs).view(np.uint64).reshape(-1, 48)
     out = np.zeros((proofs.shape[0], proof_wire_bytes(compressed)), dtype=np.uint8)
     status = np.zeros(proofs.shape[0], dtype=np.int32)
-    check(load_library().frw_groth16_proofs_to_wire(proofs.shape[0], proofs.ctypes.data_as(C.c_void_p), 0 if compressed else 1,
-                                                    out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_proofs_to_wire")
+    check(load_library().frw_groth16_proofs_to_wire(proofs.shape[0], _p(proofs), _wire_mode(compressed), _p(out), _p(status)),
+          "frw_groth16_proofs_to_wire")
     return out, status
 
 
@@ -444,67 +499,49 @@ def proofs_from_wire(wire, compressed=True):
     wire = np.ascontiguousarray(np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray)) else wire, dtype=np.uint8).reshape(-1, per)
     out = np.zeros((wire.shape[0], 48), dtype=np.uint64)
     status = np.zeros(wire.shape[0], dtype=np.int32)
-    check(load_library().frw_groth16_proofs_from_wire(wire.shape[0], wire.ctypes.data_as(C.c_void_p), 0 if compressed else 1,
-                                                      out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "frw_groth16_proofs_from_wire")
+    check(load_library().frw_groth16_proofs_from_wire(wire.shape[0], _p(wire), _wire_mode(compressed), _p(out), _p(status)),
+          "frw_groth16_proofs_from_wire")
     return out, status
 
 
 def proofs_to_wire_dev(d_proofs, compressed=True, stream=0):
     """proofs_to_wire on the device of `d_proofs` (a device tensor [batch, 48] of 64-bit limbs): (uint8[batch, 192 or 384], int32[batch])
     device tensors, ordered on `stream`, the host function's bytes."""
-    import torch
     batch = d_proofs.shape[0]
-    out = torch.empty((batch, proof_wire_bytes(compressed)), dtype=torch.uint8, device=d_proofs.device)
-    status = torch.empty(batch, dtype=torch.int32, device=d_proofs.device)
-    check(load_library().frw_groth16_proofs_to_wire_dev(d_proofs.device.index or 0, batch, C.c_void_p(d_proofs.data_ptr()), 0 if compressed else 1,
-                                                        C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)),
-          "frw_groth16_proofs_to_wire_dev")
+    out = _empty((batch, proof_wire_bytes(compressed)), "uint8", d_proofs.device)
+    status = _empty(batch, "int32", d_proofs.device)
+    check(load_library().frw_groth16_proofs_to_wire_dev(d_proofs.device.index or 0, batch, _p(d_proofs), _wire_mode(compressed), _p(out),
+                                                        _p(status), C.c_void_p(stream)), "frw_groth16_proofs_to_wire_dev")
     return out, status
 
 
 def proofs_from_wire_dev(d_wire, compressed=True, stream=0):
     """proofs_from_wire on the device of `d_wire` (a contiguous device uint8 tensor of batch x 192 or 384 bytes): (int64[batch, 48] limbs,
     int32[batch] status) device tensors, ordered on `stream`, the host function's values."""
-    import torch
-    per = proof_wire_bytes(compressed)
-    if d_wire.dtype != torch.uint8 or not d_wire.is_contiguous() or d_wire.numel() % per:
-        raise FrwError(-1, "proofs_from_wire_dev", "d_wire: a contiguous uint8 tensor of %d bytes per proof" % per)
-    batch = d_wire.numel() // per
-    out = torch.empty((batch, 48), dtype=torch.int64, device=d_wire.device)
-    status = torch.empty(batch, dtype=torch.int32, device=d_wire.device)
-    check(load_library().frw_groth16_proofs_from_wire_dev(d_wire.device.index or 0, batch, C.c_void_p(d_wire.data_ptr()), 0 if compressed else 1,
-                                                          C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)),
-          "frw_groth16_proofs_from_wire_dev")
+    batch = _wire_batch(d_wire, compressed, "proofs_from_wire_dev")
+    out = _empty((batch, 48), "int64", d_wire.device)
+    status = _empty(batch, "int32", d_wire.device)
+    check(load_library().frw_groth16_proofs_from_wire_dev(d_wire.device.index or 0, batch, _p(d_wire), _wire_mode(compressed), _p(out),
+                                                          _p(status), C.c_void_p(stream)), "frw_groth16_proofs_from_wire_dev")
     return out, status
 
 
 def vk_to_wire(vk, compressed=True):
     """A verifying key in limbs (the dict WitnessEngine.groth16_setup returns, or the flat uint64 array of frw_groth16_setup's vk_out)
     -> bytes in ark-serialize's format (what VerifyingKey::deserialize reads): 344 + 48 n or 680 + 96 n bytes."""
-    if isinstance(vk, dict):
-        vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
-    vk = np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
-    if vk.size < 96 or (vk.size - 84) % 12:
-        raise FrwError(-1, "vk_to_wire", "verifying key: expected 84 + 12 x num_instance uint64 values")
-    n = (vk.size - 84) // 12
+    vk, n = _vk_flat(vk, "vk_to_wire")
     lib = load_library()
-    out = np.zeros(lib.frw_groth16_vk_wire_bytes(n, 0 if compressed else 1), dtype=np.uint8)
-    check(lib.frw_groth16_vk_to_wire(vk.ctypes.data_as(C.c_void_p), n, 0 if compressed else 1, out.ctypes.data_as(C.c_void_p)), "frw_groth16_vk_to_wire")
+    out = np.zeros(lib.frw_groth16_vk_wire_bytes(n, _wire_mode(compressed)), dtype=np.uint8)
+    check(lib.frw_groth16_vk_to_wire(_p(vk), n, _wire_mode(compressed), _p(out)), "frw_groth16_vk_to_wire")
     return out.tobytes()
 
 
 PK_POINTS_ARE_CHECKED = 1                           # frw.h FRW_PK_POINTS_ARE_CHECKED: skip the subgroup ladders of a key the caller made itself
 
 
-def _vk_flat(vk):
-    if isinstance(vk, dict):
-        vk = np.concatenate([np.asarray(vk[k], dtype=np.uint64).reshape(-1) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")])
-    return np.ascontiguousarray(vk, dtype=np.uint64).reshape(-1)
-
-
 def groth16_pk_wire_bytes(num_instance, num_witness, domain_size, compressed=True):
     """Bytes of an ark-groth16 ProvingKey with these counts (I with the constant one, W, n) in ark-serialize's format; 0 for counts no key has."""
-    return int(load_library().frw_groth16_pk_wire_bytes(int(num_instance), int(num_witness), int(domain_size), 0 if compressed else 1))
+    return int(load_library().frw_groth16_pk_wire_bytes(int(num_instance), int(num_witness), int(domain_size), _wire_mode(compressed)))
 
 
 def groth16_pk_wire_info(data, compressed=True):
@@ -514,8 +551,7 @@ def groth16_pk_wire_info(data, compressed=True):
     from ._lib import Groth16PkWireInfoStruct
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
     info = Groth16PkWireInfoStruct()
-    check(load_library().frw_groth16_pk_wire_info(buf.ctypes.data_as(C.c_void_p), buf.size, 0 if compressed else 1, C.byref(info)),
-          "frw_groth16_pk_wire_info")
+    check(load_library().frw_groth16_pk_wire_info(_p(buf), buf.size, _wire_mode(compressed), C.byref(info)), "frw_groth16_pk_wire_info")
     return {name: int(getattr(info, name)) for name, _ in Groth16PkWireInfoStruct._fields_}
 
 
@@ -524,9 +560,8 @@ def diag_pairing(g1, g2):
     g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(12)
     g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(24)
     out = np.zeros((12, 6), dtype=np.uint64)
-    check(load_library().frw_diag_pairing(g1.ctypes.data_as(C.c_void_p), g2.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "frw_diag_pairing")
+    check(load_library().frw_diag_pairing(_p(g1), _p(g2), _p(out)), "frw_diag_pairing")
     return out
-
 
 
 def diag_pairing_dev(g1, g2, device=0):
@@ -537,9 +572,9 @@ def diag_pairing_dev(g1, g2, device=0):
     if g1.shape[0] != g2.shape[0]:
         raise FrwError("diag_pairing_dev: as many G1 as G2 points")
     out = np.zeros((g1.shape[0], 12, 6), dtype=np.uint64)
-    check(load_library().frw_diag_pairing_dev(int(device), g1.shape[0], g1.ctypes.data_as(C.c_void_p), g2.ctypes.data_as(C.c_void_p),
-                                              out.ctypes.data_as(C.c_void_p)), "frw_diag_pairing_dev")
+    check(load_library().frw_diag_pairing_dev(int(device), g1.shape[0], _p(g1), _p(g2), _p(out)), "frw_diag_pairing_dev")
     return out
+
 
 def _u16(a, n):
     a = np.ascontiguousarray(a, dtype=np.uint16)
@@ -591,8 +626,7 @@ class WitnessEngine:
         check(self._lib.frw_host_alloc(self._ctx, nbytes, C.byref(ptr)), "frw_host_alloc")
         buf = (C.c_char * max(nbytes, 1)).from_address(ptr.value)
         arr = np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
-        lib, addr = self._lib, ptr.value
-        weakref.finalize(buf, lambda: lib.frw_host_free(None, C.c_void_p(addr)))     # may outlive this engine
+        weakref.finalize(buf, self._lib.frw_host_free, None, C.c_void_p(ptr.value))     # may outlive this engine
         return arr
 
     # ---- host buffers ------------------------------------------------------------------
@@ -625,14 +659,9 @@ class WitnessEngine:
             wit = np.zeros((batch, L.num_witness, 4), dtype=np.uint64)
             inst = np.zeros((batch, L.num_instance, 4), dtype=np.uint64)
             st = np.zeros(batch, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
         fn = (self._lib.frw_witness_ntt_verify, self._lib.frw_witness_dual_ntt_verify, self._lib.frw_witness_schoolbook_verify)[circuit]
-        rc = fn(self._ctx, logn, batch, p(sig), p(pk), p(hm), encoding, p(wit), p(inst), p(st), 1 if strict else 0)
-        if rc == E_RANGE:
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_witness_ntt_verify",
-                           "Invalid input: signature(s) %s failed range checks (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_witness_ntt_verify")
+        rc = fn(self._ctx, logn, batch, _p(sig), _p(pk), _p(hm), encoding, _p(wit), _p(inst), _p(st), 1 if strict else 0)
+        _check_refusal(rc, "frw_witness_ntt_verify", st, "signature(s)", "failed range checks")
         return wit, inst, st
 
     def witness_ntt_verify_compact(self, logn, sig, pk, hm, strict=True, pinned=False):
@@ -642,8 +671,7 @@ class WitnessEngine:
         batch = sig.shape[0]
         mk = (lambda shape, dt: self.pinned_empty(shape, dt)) if pinned else (lambda shape, dt: np.zeros(shape, dtype=dt))
         comp, st = mk((batch, CL.bytes_per_signature), np.uint8), mk((batch,), np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_witness_ntt_verify(self._ctx, logn, batch, p(sig), p(pk), p(hm), ENC_COMPACT, p(comp), None, p(st),
+        rc = self._lib.frw_witness_ntt_verify(self._ctx, logn, batch, _p(sig), _p(pk), _p(hm), ENC_COMPACT, _p(comp), None, _p(st),
                                               1 if strict else 0)
         if rc == E_RANGE:
             raise FrwError(rc, "frw_witness_ntt_verify", "Invalid input: a signature failed its range checks")
@@ -657,8 +685,7 @@ class WitnessEngine:
         batch = compact.shape[0]
         wit = np.empty((batch, L.num_witness, 4), dtype=np.uint64)
         inst = np.empty((batch, L.num_instance, 4), dtype=np.uint64)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(self._lib.frw_expand_host(logn, batch, p(compact), p(wit), p(inst)), "frw_expand_host")
+        check(self._lib.frw_expand_host(logn, batch, _p(compact), _p(wit), _p(inst)), "frw_expand_host")
         return wit, inst
 
     def field_encoding(self, p):
@@ -700,8 +727,7 @@ class WitnessEngine:
         wit = np.zeros((batch, 29 * n, 4), dtype=np.uint64)
         out = np.zeros((batch, n), dtype=np.uint16)
         st = np.zeros(batch, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(self._lib.frw_ntt_modq(self._ctx, logn, batch, p(poly), encoding, p(wit), p(out), p(st)), "frw_ntt_modq")
+        check(self._lib.frw_ntt_modq(self._ctx, logn, batch, _p(poly), encoding, _p(wit), _p(out), _p(st)), "frw_ntt_modq")
         return wit, out, st
 
     def prepare_inputs(self, logn, pks, msgs, sigs):
@@ -714,16 +740,11 @@ class WitnessEngine:
         if any(len(p) != PK_LEN[logn] for p in pks) or any(len(s) != sig_len for s in sigs):
             raise ValueError("public keys must be %d bytes and signatures of one common length" % PK_LEN[logn])
         n = 1 << logn
-        pkb = np.frombuffer(b"".join(pks), dtype=np.uint8)
-        sgb = np.frombuffer(b"".join(sigs), dtype=np.uint8)
-        blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8)
-        off = np.zeros(batch + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(m) for m in msgs])
+        pkb, sgb, blob, off = _pack(pks, sigs, msgs)
         out = [np.zeros((batch, n), dtype=np.uint16) for _ in range(3)]
         st = np.zeros(batch, dtype=np.int32)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)
-        check(self._lib.frw_prepare_inputs(self._ctx, logn, batch, p(pkb), p(sgb), sig_len, p(blob), p(off),
-                                           p(out[0]), p(out[1]), p(out[2]), p(st)), "frw_prepare_inputs")
+        check(self._lib.frw_prepare_inputs(self._ctx, logn, batch, _p(pkb), _p(sgb), sig_len, _p(blob), _p(off),
+                                           _p(out[0]), _p(out[1]), _p(out[2]), _p(st)), "frw_prepare_inputs")
         return out[0], out[1], out[2], st
 
     def gadget(self, kind, a, b=None, encoding=ENC_MONTGOMERY):
@@ -742,37 +763,30 @@ class WitnessEngine:
         barr = np.array([int(x) for x in b], dtype=np.uint64) if b is not None else None
         out = np.zeros((count, blk, 4), dtype=np.uint64)
         st = np.zeros(count, dtype=np.int32)
-        p = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
-        check(self._lib.frw_gadget(self._ctx, kind, count, p(arr), p(barr), encoding, p(out), p(st)), "frw_gadget")
+        check(self._lib.frw_gadget(self._ctx, kind, count, _p(arr), _p(barr), encoding, _p(out), _p(st)), "frw_gadget")
         return out, st
 
     # ---- device buffers (torch tensors or raw pointers) ---------------------------------
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+    _ptr = staticmethod(_p)
 
     def witness_ntt_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_wit, d_inst, d_status,
                                encoding=ENC_MONTGOMERY, stream=0):
-        check(self._lib.frw_witness_ntt_verify_dev(self._ctx, logn, batch, self._ptr(d_sig), self._ptr(d_pk),
-                                                   self._ptr(d_hm), encoding, self._ptr(d_wit), self._ptr(d_inst),
-                                                   self._ptr(d_status), C.c_void_p(stream)),
-              "frw_witness_ntt_verify_dev")
+        check(self._lib.frw_witness_ntt_verify_dev(self._ctx, logn, batch, _p(d_sig), _p(d_pk), _p(d_hm), encoding, _p(d_wit), _p(d_inst),
+                                                   _p(d_status), C.c_void_p(stream)), "frw_witness_ntt_verify_dev")
 
     def witness_ntt_verify_compact_dev(self, logn, batch, d_sig, d_pk, d_hm, d_compact, d_status, stream=0):
         """FRW_ENC_COMPACT producer: d_compact = batch x compact_layout(logn).bytes_per_signature bytes."""
-        check(self._lib.frw_witness_ntt_verify_compact_dev(self._ctx, logn, batch, self._ptr(d_sig), self._ptr(d_pk),
-                                                           self._ptr(d_hm), self._ptr(d_compact), self._ptr(d_status),
-                                                           C.c_void_p(stream)), "frw_witness_ntt_verify_compact_dev")
+        check(self._lib.frw_witness_ntt_verify_compact_dev(self._ctx, logn, batch, _p(d_sig), _p(d_pk), _p(d_hm), _p(d_compact),
+                                                           _p(d_status), C.c_void_p(stream)), "frw_witness_ntt_verify_compact_dev")
 
     def expand_dev(self, logn, batch, d_compact, d_wit, d_inst, stream=0):
         """compact -> the arkworks witness / instance buffers (FRW_ENC_MONTGOMERY bytes)."""
-        check(self._lib.frw_expand_dev(self._ctx, logn, batch, self._ptr(d_compact), self._ptr(d_wit), self._ptr(d_inst),
-                                       C.c_void_p(stream)), "frw_expand_dev")
+        check(self._lib.frw_expand_dev(self._ctx, logn, batch, _p(d_compact), _p(d_wit), _p(d_inst), C.c_void_p(stream)), "frw_expand_dev")
 
     def expand_field_dev(self, logn, batch, d_compact, encoding, d_wit, d_inst, stream=0):
         """compact -> the witness / instance buffers over a field registered with field_encoding."""
-        check(self._lib.frw_expand_field_dev(self._ctx, logn, batch, self._ptr(d_compact), encoding, self._ptr(d_wit), self._ptr(d_inst),
-                                             C.c_void_p(stream)), "frw_expand_field_dev")
+        check(self._lib.frw_expand_field_dev(self._ctx, logn, batch, _p(d_compact), encoding, _p(d_wit), _p(d_inst), C.c_void_p(stream)),
+              "frw_expand_field_dev")
 
     def launch_shape(self, logn, batch, encoding=ENC_MONTGOMERY):
         """{grid, resident workgroups per CU, CUs, split_signatures} of a witness launch of `batch` signatures
@@ -783,25 +797,20 @@ class WitnessEngine:
 
     def witness_dual_ntt_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_wit, d_inst, d_status,
                                     encoding=ENC_MONTGOMERY, stream=0):
-        check(self._lib.frw_witness_dual_ntt_verify_dev(self._ctx, logn, batch, self._ptr(d_sig), self._ptr(d_pk),
-                                                        self._ptr(d_hm), encoding, self._ptr(d_wit), self._ptr(d_inst),
-                                                        self._ptr(d_status), C.c_void_p(stream)),
-              "frw_witness_dual_ntt_verify_dev")
+        check(self._lib.frw_witness_dual_ntt_verify_dev(self._ctx, logn, batch, _p(d_sig), _p(d_pk), _p(d_hm), encoding, _p(d_wit),
+                                                        _p(d_inst), _p(d_status), C.c_void_p(stream)), "frw_witness_dual_ntt_verify_dev")
 
     def witness_schoolbook_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_wit, d_inst, d_status,
                                       encoding=ENC_MONTGOMERY, stream=0):
-        check(self._lib.frw_witness_schoolbook_verify_dev(self._ctx, logn, batch, self._ptr(d_sig), self._ptr(d_pk),
-                                                          self._ptr(d_hm), encoding, self._ptr(d_wit), self._ptr(d_inst),
-                                                          self._ptr(d_status), C.c_void_p(stream)),
-              "frw_witness_schoolbook_verify_dev")
+        check(self._lib.frw_witness_schoolbook_verify_dev(self._ctx, logn, batch, _p(d_sig), _p(d_pk), _p(d_hm), encoding, _p(d_wit),
+                                                          _p(d_inst), _p(d_status), C.c_void_p(stream)), "frw_witness_schoolbook_verify_dev")
 
     def ntt_modq_dev(self, logn, batch, d_poly, d_wit, d_ntt, d_status, encoding=ENC_MONTGOMERY, stream=0):
-        check(self._lib.frw_ntt_modq_dev(self._ctx, logn, batch, self._ptr(d_poly), encoding, self._ptr(d_wit),
-                                         self._ptr(d_ntt), self._ptr(d_status), C.c_void_p(stream)),
-              "frw_ntt_modq_dev")
+        check(self._lib.frw_ntt_modq_dev(self._ctx, logn, batch, _p(d_poly), encoding, _p(d_wit), _p(d_ntt), _p(d_status),
+                                         C.c_void_p(stream)), "frw_ntt_modq_dev")
 
     def diag_write_stream_dev(self, d_buf, nbytes, slab_bytes, stream=0):
-        check(self._lib.frw_diag_write_stream_dev(self._ctx, self._ptr(d_buf), nbytes, slab_bytes, C.c_void_p(stream)),
+        check(self._lib.frw_diag_write_stream_dev(self._ctx, _p(d_buf), nbytes, slab_bytes, C.c_void_p(stream)),
               "frw_diag_write_stream_dev")
 
     def r1cs_load(self, circuit, logn):
@@ -822,9 +831,9 @@ class WitnessEngine:
         if any(len(c) != len(v) for c, v in zip(col, val)) or any(len(p) != len(ptr[0]) or len(p) == 0 for p in ptr):
             raise ValueError("col and val of a matrix have one entry per term; the three row_ptr have C + 1 entries")
         counts = (C.c_uint64 * 6)(num_instance, num_witness, len(ptr[0]) - 1, len(col[0]), len(col[1]), len(col[2]))
-        three = lambda arrs: (C.c_void_p * 3)(*[a.ctypes.data_as(C.c_void_p) for a in arrs])
+        three = [(C.c_void_p * 3)(*map(_p, arrs)) for arrs in (ptr, col, val)]
         h = C.c_void_p()
-        check(self._lib.frw_r1cs_load_csr(self.device, counts, three(ptr), three(col), three(val), C.byref(h)), "frw_r1cs_load_csr")
+        check(self._lib.frw_r1cs_load_csr(self.device, counts, *three, C.byref(h)), "frw_r1cs_load_csr")
         return h
 
     def r1cs_load_file(self, path):
@@ -842,7 +851,7 @@ class WitnessEngine:
         aggregate's own (aggregate_assign_dev makes them).  Free with r1cs_free."""
         arr = np.ascontiguousarray(logns, dtype=np.int32)
         h = C.c_void_p()
-        check(self._lib.frw_r1cs_load_aggregate(self.device, len(arr), arr.ctypes.data_as(C.c_void_p), C.byref(h)), "frw_r1cs_load_aggregate")
+        check(self._lib.frw_r1cs_load_aggregate(self.device, len(arr), _p(arr), C.byref(h)), "frw_r1cs_load_aggregate")
         return h
 
     def r1cs_info(self, handle):
@@ -854,16 +863,15 @@ class WitnessEngine:
     def aggregate_assign_dev(self, handle, d_wit512, d_inst512, d_wit1024, d_inst1024, d_wit, d_inst, stream=0):
         """instance_assignment / witness_assignment of the aggregate from the per-parameter-set batches of the witness entry points
         (either pair may be None when the aggregate has no such statement)."""
-        P = lambda t: self._ptr(t) if t is not None else None
-        check(self._lib.frw_aggregate_assign_dev(handle, P(d_wit512), P(d_inst512), P(d_wit1024), P(d_inst1024), self._ptr(d_wit),
-                                                 self._ptr(d_inst), C.c_void_p(stream)), "frw_aggregate_assign_dev")
+        check(self._lib.frw_aggregate_assign_dev(handle, _p(d_wit512), _p(d_inst512), _p(d_wit1024), _p(d_inst1024), _p(d_wit), _p(d_inst),
+                                                 C.c_void_p(stream)), "frw_aggregate_assign_dev")
 
     # ---- the verifier's statement: instance vectors without a signature -----------------------------------------------------------
     def statement_dev(self, circuit, logn, batch, d_pk, d_hm, d_inst, d_status, encoding=ENC_MONTGOMERY, stream=0):
         """instance_assignment of `batch` statements from (pk, hm) in device memory (frw_statement_dev): the bytes the witness entry
         points write to d_inst for the same pk and hm, without a signature and without a witness."""
-        check(self._lib.frw_statement_dev(self._ctx, int(circuit), int(logn), batch, self._ptr(d_pk), self._ptr(d_hm), int(encoding),
-                                          self._ptr(d_inst), self._ptr(d_status), C.c_void_p(stream)), "frw_statement_dev")
+        check(self._lib.frw_statement_dev(self._ctx, int(circuit), int(logn), batch, _p(d_pk), _p(d_hm), int(encoding), _p(d_inst),
+                                          _p(d_status), C.c_void_p(stream)), "frw_statement_dev")
 
     def statement(self, circuit, logn, pk, hm, encoding=ENC_MONTGOMERY, strict=True):
         """Host buffers (frw_statement): pk, hm uint16[batch, N] -> (instance u64[batch, 2 N + 1, 4], status i32[batch])."""
@@ -874,12 +882,9 @@ class WitnessEngine:
             raise ValueError("batch mismatch")
         inst = np.zeros((batch, 2 * n + 1, 4), dtype=np.uint64)
         st = np.zeros(batch, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_statement(self._ctx, int(circuit), int(logn), batch, p(pk), p(hm), int(encoding), p(inst), p(st), 1 if strict else 0)
-        if rc == E_RANGE:
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_statement", "Invalid input: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_statement")
+        rc = self._lib.frw_statement(self._ctx, int(circuit), int(logn), batch, _p(pk), _p(hm), int(encoding), _p(inst), _p(st),
+                                     1 if strict else 0)
+        _check_refusal(rc, "frw_statement", st, "statement(s)")
         return inst, st
 
     @staticmethod
@@ -889,12 +894,7 @@ class WitnessEngine:
             raise ValueError("batch mismatch")
         if any(len(k) != PK_LEN[logn] for k in pk_bytes) or any(len(x) != NONCE_LEN for x in nonces):
             raise ValueError("public keys must be %d bytes and nonces %d" % (PK_LEN[logn], NONCE_LEN))
-        pkb = np.frombuffer(b"".join(bytes(k) for k in pk_bytes) or b"\0", dtype=np.uint8)
-        non = np.frombuffer(b"".join(bytes(x) for x in nonces) or b"\0", dtype=np.uint8)
-        blob = np.frombuffer(b"".join(bytes(m) for m in msgs) or b"\0", dtype=np.uint8)
-        off = np.zeros(batch + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(m) for m in msgs])
-        return batch, pkb, non, blob, off
+        return (batch, *_pack(pk_bytes, nonces, msgs))
 
     def statement_workspace_bytes(self, logn, batch):
         return int(self._lib.frw_statement_workspace_bytes(int(logn), int(batch)))
@@ -906,13 +906,9 @@ class WitnessEngine:
         n = 1 << logn
         inst = np.zeros((batch, 2 * n + 1, 4), dtype=np.uint64)
         st = np.zeros(batch, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_statement_from_bytes(self._ctx, int(circuit), int(logn), batch, p(pkb), p(non), p(blob), p(off), int(encoding),
-                                                p(inst), p(st), 1 if strict else 0)
-        if rc == E_RANGE:
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_statement_from_bytes", "Invalid input: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_statement_from_bytes")
+        rc = self._lib.frw_statement_from_bytes(self._ctx, int(circuit), int(logn), batch, _p(pkb), _p(non), _p(blob), _p(off), int(encoding),
+                                                _p(inst), _p(st), 1 if strict else 0)
+        _check_refusal(rc, "frw_statement_from_bytes", st, "statement(s)")
         return inst, st
 
     def statement_from_bytes_dev(self, circuit, logn, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
@@ -920,40 +916,29 @@ class WitnessEngine:
         kernel run on `stream`.  -> (instance int64[batch, 2 N + 1, 4], status int32[batch]) device tensors, not synchronised.
         pk_bytes may be a device uint8 tensor [batch, PK_LEN] with nonces a device uint8 tensor [batch, 40], msgs a (blob, offsets)
         pair of device tensors (uint8, int64[batch + 1]): nothing is uploaded then."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(pk_bytes, torch.Tensor):
-            d_pkb, d_non, (d_blob, d_off) = pk_bytes, nonces, msgs
-            batch = d_pkb.numel() // PK_LEN[logn]
-        else:
-            batch, pkb, non, blob, off = self._statement_bytes(logn, pk_bytes, nonces, msgs)
-            d_pkb, d_non, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, non, blob))
-            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        batch, _, d_pkb, d_non, d_blob, d_off = _encoded_dev(self.device, logn, pk_bytes, nonces, msgs, NONCE_LEN, self._statement_bytes)
         n = 1 << logn
-        d_inst = torch.empty((batch, 2 * n + 1, 4), dtype=torch.int64, device=dev)
-        d_status = torch.empty(batch, dtype=torch.int32, device=dev)
-        if workspace is None:
-            workspace = torch.empty(max(self.statement_workspace_bytes(logn, batch), 16), dtype=torch.uint8, device=dev)
-        check(self._lib.frw_statement_from_bytes_dev(self._ctx, int(circuit), int(logn), batch, self._ptr(d_pkb), self._ptr(d_non), self._ptr(d_blob),
-                                                     self._ptr(d_off), int(encoding), self._ptr(d_inst), self._ptr(d_status),
-                                                     self._ptr(workspace), workspace.numel(), C.c_void_p(stream)), "frw_statement_from_bytes_dev")
+        d_inst = _empty((batch, 2 * n + 1, 4), "int64", self.device)
+        d_status = _empty(batch, "int32", self.device)
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.statement_workspace_bytes, logn, batch)
+        check(self._lib.frw_statement_from_bytes_dev(self._ctx, int(circuit), int(logn), batch, _p(d_pkb), _p(d_non), _p(d_blob), _p(d_off),
+                                                     int(encoding), _p(d_inst), _p(d_status), _p(ws), ws_bytes, C.c_void_p(stream)),
+              "frw_statement_from_bytes_dev")
         return d_inst, d_status
 
     def aggregate_statement_dev(self, handle, d_pk512, d_hm512, d_pk1024, d_hm1024, d_inst, d_status, encoding=ENC_MONTGOMERY, stream=0):
         """instance_assignment of the aggregate from the statements' keys and hashed messages, per parameter set in statement order
         (either pair may be None): aggregate_assign_dev's d_inst without a witness.  d_status: int32[num_statements]."""
-        P = lambda t: self._ptr(t) if t is not None else None
-        check(self._lib.frw_aggregate_statement_dev(handle, self._ctx, P(d_pk512), P(d_hm512), P(d_pk1024), P(d_hm1024), int(encoding),
-                                                    self._ptr(d_inst), self._ptr(d_status), C.c_void_p(stream)), "frw_aggregate_statement_dev")
+        check(self._lib.frw_aggregate_statement_dev(handle, self._ctx, _p(d_pk512), _p(d_hm512), _p(d_pk1024), _p(d_hm1024), int(encoding),
+                                                    _p(d_inst), _p(d_status), C.c_void_p(stream)), "frw_aggregate_statement_dev")
 
     # ---- Falcon verification: verdicts and norms without a witness -------------------------------------------------------------------
     def falcon_verify_dev(self, logn, batch, d_sig, d_pk, d_hm, d_status, d_norm=None, rule=RULE_CIRCUIT, stream=0):
         """The verdicts of `batch` signatures from (sig, pk, hm) in device memory (frw_falcon_verify_dev): d_status int32[batch] is FRW_ST_*
         -- under RULE_CIRCUIT the word the witness entry points write for the same inputs --, d_norm (int64[batch] or None) the squared
         norm under `rule`, all ones where none exists.  Not synchronised."""
-        check(self._lib.frw_falcon_verify_dev(self._ctx, int(logn), batch, self._ptr(d_sig), self._ptr(d_pk), self._ptr(d_hm), int(rule),
-                                              self._ptr(d_status), self._ptr(d_norm) if d_norm is not None else None, C.c_void_p(stream)),
-              "frw_falcon_verify_dev")
+        check(self._lib.frw_falcon_verify_dev(self._ctx, int(logn), batch, _p(d_sig), _p(d_pk), _p(d_hm), int(rule), _p(d_status), _p(d_norm),
+                                              C.c_void_p(stream)), "frw_falcon_verify_dev")
 
     def falcon_verify(self, logn, sig, pk, hm, rule=RULE_CIRCUIT, strict=True, want_norm=True):
         """Host buffers (frw_falcon_verify): sig, pk, hm uint16[batch, N] -> (status i32[batch], norm u64[batch] or None)."""
@@ -964,13 +949,8 @@ class WitnessEngine:
             raise ValueError("batch mismatch")
         st = np.zeros(batch, dtype=np.int32)
         norm = np.zeros(batch, dtype=np.uint64) if want_norm else None
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_falcon_verify(self._ctx, int(logn), batch, p(sig), p(pk), p(hm), int(rule), p(st), p(norm) if want_norm else None,
-                                         1 if strict else 0)
-        if rc == E_RANGE:
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_falcon_verify", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_falcon_verify")
+        rc = self._lib.frw_falcon_verify(self._ctx, int(logn), batch, _p(sig), _p(pk), _p(hm), int(rule), _p(st), _p(norm), 1 if strict else 0)
+        _check_refusal(rc, "frw_falcon_verify", st, "signature(s)")
         return st, norm
 
     @staticmethod
@@ -981,12 +961,7 @@ class WitnessEngine:
         sig_len = len(sig_bytes[0]) if batch else SIG_LEN[logn]
         if any(len(k) != PK_LEN[logn] for k in pk_bytes) or any(len(x) != sig_len for x in sig_bytes):
             raise ValueError("public keys must be %d bytes and signatures of one common length" % PK_LEN[logn])
-        pkb = np.frombuffer(b"".join(bytes(k) for k in pk_bytes) or b"\0", dtype=np.uint8)
-        sgb = np.frombuffer(b"".join(bytes(x) for x in sig_bytes) or b"\0", dtype=np.uint8)
-        blob = np.frombuffer(b"".join(bytes(m) for m in msgs) or b"\0", dtype=np.uint8)
-        off = np.zeros(batch + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(m) for m in msgs])
-        return batch, sig_len, pkb, sgb, blob, off
+        return (batch, sig_len, *_pack(pk_bytes, sig_bytes, msgs))
 
     def falcon_verify_workspace_bytes(self, logn, batch):
         return int(self._lib.frw_falcon_verify_workspace_bytes(int(logn), int(batch)))
@@ -997,13 +972,9 @@ class WitnessEngine:
         batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
         st = np.zeros(batch, dtype=np.int32)
         norm = np.zeros(batch, dtype=np.uint64) if want_norm else None
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_falcon_verify_from_bytes(self._ctx, int(logn), batch, p(pkb), p(sgb), sig_len, p(blob), p(off), int(rule), p(st),
-                                                    p(norm) if want_norm else None, 1 if strict else 0)
-        if rc == E_RANGE:
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_falcon_verify_from_bytes", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_falcon_verify_from_bytes")
+        rc = self._lib.frw_falcon_verify_from_bytes(self._ctx, int(logn), batch, _p(pkb), _p(sgb), sig_len, _p(blob), _p(off), int(rule),
+                                                    _p(st), _p(norm), 1 if strict else 0)
+        _check_refusal(rc, "frw_falcon_verify_from_bytes", st, "signature(s)")
         return st, norm
 
     def falcon_verify_from_bytes_dev(self, logn, pk_bytes, sig_bytes, msgs, rule=RULE_CIRCUIT, stream=0, workspace=None, sig_len=None):
@@ -1013,25 +984,14 @@ class WitnessEngine:
         (uint8, int64[batch + 1]): nothing is uploaded then.  The uploaded inputs and a workspace made here are torch's and go back
         to its allocator when this method returns, with the four kernels possibly still queued: pass torch's current stream (or 0 while
         that is the default stream), or pass device tensors and a `workspace` of your own and keep them until `stream` has run."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(pk_bytes, torch.Tensor):
-            d_pkb, d_sgb, (d_blob, d_off) = pk_bytes, sig_bytes, msgs
-            batch = d_pkb.numel() // PK_LEN[logn]
-            if sig_len is None:
-                sig_len = d_sgb.numel() // batch if batch else SIG_LEN[logn]
-        else:
-            batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
-            d_pkb, d_sgb, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, sgb, blob))
-            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
-        d_status = torch.empty(batch, dtype=torch.int32, device=dev)
-        d_norm = torch.empty(batch, dtype=torch.int64, device=dev)
-        if workspace is None:
-            workspace = torch.empty(max(self.falcon_verify_workspace_bytes(logn, batch), 16), dtype=torch.uint8, device=dev)
-        check(self._lib.frw_falcon_verify_from_bytes_dev(self._ctx, int(logn), batch, self._ptr(d_pkb), self._ptr(d_sgb), int(sig_len),
-                                                         self._ptr(d_blob), self._ptr(d_off), int(rule), self._ptr(d_status), self._ptr(d_norm),
-                                                         self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
-              "frw_falcon_verify_from_bytes_dev")
+        batch, sig_len, d_pkb, d_sgb, d_blob, d_off = _encoded_dev(self.device, logn, pk_bytes, sig_bytes, msgs, sig_len,
+                                                                   self._falcon_verify_bytes)
+        d_status = _empty(batch, "int32", self.device)
+        d_norm = _empty(batch, "int64", self.device)
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.falcon_verify_workspace_bytes, logn, batch)
+        check(self._lib.frw_falcon_verify_from_bytes_dev(self._ctx, int(logn), batch, _p(d_pkb), _p(d_sgb), int(sig_len), _p(d_blob),
+                                                         _p(d_off), int(rule), _p(d_status), _p(d_norm), _p(ws), ws_bytes,
+                                                         C.c_void_p(stream)), "frw_falcon_verify_from_bytes_dev")
         return d_status, d_norm
 
     # ---- the prover from bytes: encoded signatures in, proofs on the wire out ---------------------------------------------------------
@@ -1047,20 +1007,14 @@ class WitnessEngine:
         or None, status int32[batch], num_unsatisfied uint32[batch]).  A refused slot (status != 0) is all zeros in every output."""
         batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
         rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
-        mode = WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED
         out = {"wire": np.zeros((batch, proof_wire_bytes(compressed)), dtype=np.uint8),
                "proofs": np.zeros((batch, 48), dtype=np.uint64) if want_proofs else None,
                "instance": np.zeros((batch, (2 << logn) + 1, 4), dtype=np.uint64) if want_instance else None,
                "status": np.zeros(batch, dtype=np.int32), "num_unsatisfied": np.zeros(batch, dtype=np.uint32)}
-        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        rc = self._lib.frw_pok_prove_from_bytes(self._ctx, pk, r1cs, int(circuit), int(logn), batch, p(pkb), p(sgb), sig_len, p(blob), p(off),
-                                                p(rs), mode, p(out["wire"]), p(out["proofs"]), p(out["instance"]), p(out["status"]),
-                                                p(out["num_unsatisfied"]), 1 if strict else 0)
-        if rc == E_RANGE:
-            st = out["status"]
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, "frw_pok_prove_from_bytes", "Invalid input: signature(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
-        check(rc, "frw_pok_prove_from_bytes")
+        rc = self._lib.frw_pok_prove_from_bytes(self._ctx, pk, r1cs, int(circuit), int(logn), batch, _p(pkb), _p(sgb), sig_len, _p(blob),
+                                                _p(off), _p(rs), _wire_mode(compressed), _p(out["wire"]), _p(out["proofs"]),
+                                                _p(out["instance"]), _p(out["status"]), _p(out["num_unsatisfied"]), 1 if strict else 0)
+        _check_refusal(rc, "frw_pok_prove_from_bytes", out["status"], "signature(s)")
         return out
 
     def pok_prove_from_bytes_dev(self, pk, r1cs, circuit, logn, pk_bytes, sig_bytes, msgs, rs, compressed=True, in_flight=None, workspace=None,
@@ -1072,37 +1026,26 @@ class WitnessEngine:
         are), or None for one that holds `in_flight` proofs (default: min(batch, 4)).  The call waits on `stream` once, for the number
         of accepted signatures; its results are ordered on `stream` and not synchronised."""
         import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(pk_bytes, torch.Tensor):
-            d_pkb, d_sgb, (d_blob, d_off) = pk_bytes, sig_bytes, msgs
-            batch = d_pkb.numel() // PK_LEN[logn]
-            if sig_len is None:
-                sig_len = d_sgb.numel() // batch if batch else SIG_LEN[logn]
-        else:
-            batch, sig_len, pkb, sgb, blob, off = self._falcon_verify_bytes(logn, pk_bytes, sig_bytes, msgs)
-            d_pkb, d_sgb, d_blob = (torch.from_numpy(a.copy()).to(dev) for a in (pkb, sgb, blob))
-            d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        dev = self.device
+        batch, sig_len, d_pkb, d_sgb, d_blob, d_off = _encoded_dev(dev, logn, pk_bytes, sig_bytes, msgs, sig_len, self._falcon_verify_bytes)
         if isinstance(rs, torch.Tensor):
             d_rs = rs
+        elif batch:
+            d_rs, = _upload((np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4),), dev)
         else:
-            rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
-            d_rs = torch.from_numpy(rs.view(np.int64).copy()).to(dev) if batch else torch.zeros(8, dtype=torch.int64, device=dev)
-        wire_len = proof_wire_bytes(compressed)
+            d_rs = torch.zeros(8, dtype=torch.int64, device=torch.device("cuda", dev))
         rows = max(batch, 1)                    # (an empty tensor has no address: the call refuses null pointers whatever the batch)
-        out = {"wire": torch.empty((rows, wire_len), dtype=torch.uint8, device=dev),
-               "proofs": torch.empty((rows, 48), dtype=torch.int64, device=dev) if want_proofs else None,
-               "instance": torch.empty((rows, (2 << logn) + 1, 4), dtype=torch.int64, device=dev) if want_instance else None,
-               "status": torch.empty(rows, dtype=torch.int32, device=dev),
-               "num_unsatisfied": torch.empty(rows, dtype=torch.int32, device=dev) if want_unsatisfied else None}
-        if workspace is None:
-            k = max(1, min(batch, 4) if in_flight is None else int(in_flight))
-            workspace = torch.empty(max(self.pok_prove_workspace_bytes(pk, r1cs, circuit, logn, batch, k), 256), dtype=torch.uint8, device=dev)
-        P = lambda t: self._ptr(t) if t is not None else None
-        check(self._lib.frw_pok_prove_from_bytes_dev(self._ctx, pk, r1cs, int(circuit), int(logn), batch, self._ptr(d_pkb), self._ptr(d_sgb),
-                                                     int(sig_len), self._ptr(d_blob), self._ptr(d_off), self._ptr(d_rs),
-                                                     WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, P(out["wire"]), P(out["proofs"]),
-                                                     P(out["instance"]), P(out["status"]), P(out["num_unsatisfied"]), self._ptr(workspace),
-                                                     workspace.numel(), C.c_void_p(stream)), "frw_pok_prove_from_bytes_dev")
+        out = {"wire": _empty((rows, proof_wire_bytes(compressed)), "uint8", dev),
+               "proofs": _empty((rows, 48), "int64", dev) if want_proofs else None,
+               "instance": _empty((rows, (2 << logn) + 1, 4), "int64", dev) if want_instance else None,
+               "status": _empty(rows, "int32", dev),
+               "num_unsatisfied": _empty(rows, "int32", dev) if want_unsatisfied else None}
+        k = max(1, min(batch, 4) if in_flight is None else int(in_flight))
+        ws, ws_bytes = _workspace(workspace, dev, 256, self.pok_prove_workspace_bytes, pk, r1cs, circuit, logn, batch, k)
+        check(self._lib.frw_pok_prove_from_bytes_dev(self._ctx, pk, r1cs, int(circuit), int(logn), batch, _p(d_pkb), _p(d_sgb), int(sig_len),
+                                                     _p(d_blob), _p(d_off), _p(d_rs), _wire_mode(compressed), _p(out["wire"]),
+                                                     _p(out["proofs"]), _p(out["instance"]), _p(out["status"]), _p(out["num_unsatisfied"]),
+                                                     _p(ws), ws_bytes, C.c_void_p(stream)), "frw_pok_prove_from_bytes_dev")
         return {k: (v[:batch] if v is not None else None) for k, v in out.items()}
 
     # ---- an aggregate from bytes: triples of mixed parameter sets in statement order -> verdicts, the statement, ONE proof ------------
@@ -1121,23 +1064,13 @@ class WitnessEngine:
             if logn is None or len(second[i]) != (NONCE_LEN if nonces is not None else SIG_LEN[logn]):
                 raise ValueError("statement %d: a key of %d or %d bytes and a signature of %d or %d (a nonce of %d)"
                                  % (i, PK_LEN[9], PK_LEN[10], SIG_LEN[9], SIG_LEN[10], NONCE_LEN))
-        pkb = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
-        sec = np.frombuffer(b"".join(second) or b"\0", dtype=np.uint8)
-        blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8)
-        off = np.zeros(len(keys) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(m) for m in msgs])
-        return len(keys), pkb, sec, blob, off
+        return (len(keys), *_pack(keys, second, msgs))
 
     def _aggregate_count(self, handle, count, where):
         info = self.r1cs_info(handle)
         if int(info.num_statements) != count:
             raise FrwError(-1, where, "%d statements given, the aggregate has %d" % (count, int(info.num_statements)))
         return info
-
-    def _aggregate_upload(self, arrays):
-        import torch
-        dev = torch.device("cuda", self.device)
-        return [torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a).copy()).to(dev) for a in arrays]
 
     def aggregate_screen_workspace_bytes(self, handle):
         return int(self._lib.frw_aggregate_screen_workspace_bytes(handle))
@@ -1149,26 +1082,21 @@ class WitnessEngine:
         self._aggregate_count(handle, count, "frw_aggregate_falcon_verify_from_bytes")
         st = np.zeros(count, dtype=np.int32)
         norm = np.zeros(count, dtype=np.uint64) if want_norm else None
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(self._lib.frw_aggregate_falcon_verify_from_bytes(handle, self._ctx, p(pkb), p(sgb), p(blob), p(off), int(rule), p(st),
-                                                               p(norm) if want_norm else None), "frw_aggregate_falcon_verify_from_bytes")
+        check(self._lib.frw_aggregate_falcon_verify_from_bytes(handle, self._ctx, _p(pkb), _p(sgb), _p(blob), _p(off), int(rule), _p(st),
+                                                               _p(norm)), "frw_aggregate_falcon_verify_from_bytes")
         return st, norm
 
     def aggregate_falcon_verify_from_bytes_dev(self, handle, triples, rule=RULE_CIRCUIT, stream=0, workspace=None):
         """The same on the device (frw_aggregate_falcon_verify_from_bytes_dev) -> (status int32[count], norm int64[count]) device
         tensors, not synchronised.  Capture-safe once the inputs are on the device."""
-        import torch
         count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
         self._aggregate_count(handle, count, "frw_aggregate_falcon_verify_from_bytes_dev")
-        d_pkb, d_sgb, d_blob, d_off = self._aggregate_upload((pkb, sgb, blob, off))
-        dev = d_pkb.device
-        d_status = torch.empty(count, dtype=torch.int32, device=dev)
-        d_norm = torch.empty(count, dtype=torch.int64, device=dev)
-        if workspace is None:
-            workspace = torch.empty(max(self.aggregate_screen_workspace_bytes(handle), 16), dtype=torch.uint8, device=dev)
-        check(self._lib.frw_aggregate_falcon_verify_from_bytes_dev(handle, self._ctx, self._ptr(d_pkb), self._ptr(d_sgb), self._ptr(d_blob),
-                                                                   self._ptr(d_off), int(rule), self._ptr(d_status), self._ptr(d_norm),
-                                                                   self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
+        d_pkb, d_sgb, d_blob, d_off = _upload((pkb, sgb, blob, off), self.device)
+        d_status = _empty(count, "int32", self.device)
+        d_norm = _empty(count, "int64", self.device)
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.aggregate_screen_workspace_bytes, handle)
+        check(self._lib.frw_aggregate_falcon_verify_from_bytes_dev(handle, self._ctx, _p(d_pkb), _p(d_sgb), _p(d_blob), _p(d_off), int(rule),
+                                                                   _p(d_status), _p(d_norm), _p(ws), ws_bytes, C.c_void_p(stream)),
               "frw_aggregate_falcon_verify_from_bytes_dev")
         return d_status, d_norm
 
@@ -1179,26 +1107,21 @@ class WitnessEngine:
         info = self._aggregate_count(handle, count, "frw_aggregate_statement_from_bytes")
         inst = np.zeros((int(info.num_instance), 4), dtype=np.uint64)
         st = np.zeros(count, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(self._lib.frw_aggregate_statement_from_bytes(handle, self._ctx, p(pkb), p(non), p(blob), p(off), int(encoding), p(inst), p(st)),
-              "frw_aggregate_statement_from_bytes")
+        check(self._lib.frw_aggregate_statement_from_bytes(handle, self._ctx, _p(pkb), _p(non), _p(blob), _p(off), int(encoding), _p(inst),
+                                                           _p(st)), "frw_aggregate_statement_from_bytes")
         return inst, st
 
     def aggregate_statement_from_bytes_dev(self, handle, pk_bytes, nonces, msgs, encoding=ENC_MONTGOMERY, stream=0, workspace=None):
         """The same on the device (frw_aggregate_statement_from_bytes_dev) -> (instance int64[I, 4], status int32[count]) device
         tensors, not synchronised."""
-        import torch
         count, pkb, non, blob, off = self._aggregate_bytes(list(zip(pk_bytes, msgs)), nonces)
         info = self._aggregate_count(handle, count, "frw_aggregate_statement_from_bytes_dev")
-        d_pkb, d_non, d_blob, d_off = self._aggregate_upload((pkb, non, blob, off))
-        dev = d_pkb.device
-        d_inst = torch.empty((int(info.num_instance), 4), dtype=torch.int64, device=dev)
-        d_status = torch.empty(count, dtype=torch.int32, device=dev)
-        if workspace is None:
-            workspace = torch.empty(max(self.aggregate_screen_workspace_bytes(handle), 16), dtype=torch.uint8, device=dev)
-        check(self._lib.frw_aggregate_statement_from_bytes_dev(handle, self._ctx, self._ptr(d_pkb), self._ptr(d_non), self._ptr(d_blob),
-                                                               self._ptr(d_off), int(encoding), self._ptr(d_inst), self._ptr(d_status),
-                                                               self._ptr(workspace), workspace.numel(), C.c_void_p(stream)),
+        d_pkb, d_non, d_blob, d_off = _upload((pkb, non, blob, off), self.device)
+        d_inst = _empty((int(info.num_instance), 4), "int64", self.device)
+        d_status = _empty(count, "int32", self.device)
+        ws, ws_bytes = _workspace(workspace, self.device, 16, self.aggregate_screen_workspace_bytes, handle)
+        check(self._lib.frw_aggregate_statement_from_bytes_dev(handle, self._ctx, _p(d_pkb), _p(d_non), _p(d_blob), _p(d_off), int(encoding),
+                                                               _p(d_inst), _p(d_status), _p(ws), ws_bytes, C.c_void_p(stream)),
               "frw_aggregate_statement_from_bytes_dev")
         return d_inst, d_status
 
@@ -1217,18 +1140,15 @@ class WitnessEngine:
         out = {"wire": np.zeros(proof_wire_bytes(compressed), dtype=np.uint8), "proof": np.zeros(48, dtype=np.uint64),
                "instance": np.zeros((int(info.num_instance), 4), dtype=np.uint64), "nonces": np.zeros((count, NONCE_LEN), dtype=np.uint8),
                "status": np.zeros(count, dtype=np.int32), "num_unsatisfied": np.zeros(1, dtype=np.uint32)}
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = self._lib.frw_aggregate_prove_from_bytes(self._ctx, pk, handle, p(pkb), p(sgb), p(blob), p(off), p(rs),
-                                                      WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, p(out["wire"]), p(out["proof"]),
-                                                      p(out["instance"]), p(out["nonces"]), p(out["status"]), p(out["num_unsatisfied"]))
+        rc = self._lib.frw_aggregate_prove_from_bytes(self._ctx, pk, handle, _p(pkb), _p(sgb), _p(blob), _p(off), _p(rs),
+                                                      _wire_mode(compressed), _p(out["wire"]), _p(out["proof"]), _p(out["instance"]),
+                                                      _p(out["nonces"]), _p(out["status"]), _p(out["num_unsatisfied"]))
         return self._aggregate_verdict(rc, out, out["status"], strict, "frw_aggregate_prove_from_bytes")
 
     @staticmethod
     def _aggregate_verdict(rc, out, status, strict, where):
         if rc == E_RANGE and strict:
-            st = np.asarray(status.tolist())
-            bad = np.nonzero(st)[0]
-            raise FrwError(rc, where, "no proof: statement(s) %s refused (status %s)" % (bad[:8], st[bad][:8]))
+            raise FrwError(rc, where, _refusal(status, "statement(s)", head="no proof"))
         if rc != E_RANGE:
             check(rc, where)
         out["rc"] = rc
@@ -1239,25 +1159,22 @@ class WitnessEngine:
         int64[I, 4], nonces uint8[count, 40], status int32[count], num_unsatisfied int32[1]) and rc.  rs: uint64[2, 4] on the host or an
         int64 device tensor.  The call waits on `stream` once, for the number of refused statements."""
         import torch
+        dev = self.device
         count, pkb, sgb, blob, off = self._aggregate_bytes(triples)
         info = self._aggregate_count(handle, count, "frw_aggregate_prove_from_bytes_dev")
-        d_pkb, d_sgb, d_blob, d_off = self._aggregate_upload((pkb, sgb, blob, off))
-        dev = d_pkb.device
-        d_rs = rs if isinstance(rs, torch.Tensor) else self._aggregate_upload((np.ascontiguousarray(rs, dtype=np.uint64).reshape(8),))[0]
-        out = {"wire": torch.empty(proof_wire_bytes(compressed), dtype=torch.uint8, device=dev),
-               "proof": torch.empty(48, dtype=torch.int64, device=dev),
-               "instance": torch.empty((int(info.num_instance), 4), dtype=torch.int64, device=dev),
-               "nonces": torch.empty((count, NONCE_LEN), dtype=torch.uint8, device=dev),
-               "status": torch.empty(count, dtype=torch.int32, device=dev),
-               "num_unsatisfied": torch.empty(1, dtype=torch.int32, device=dev)}
-        if workspace is None:
-            workspace = torch.empty(max(self.aggregate_prove_workspace_bytes(pk, handle), 256), dtype=torch.uint8, device=dev)
-        rc = self._lib.frw_aggregate_prove_from_bytes_dev(self._ctx, pk, handle, self._ptr(d_pkb), self._ptr(d_sgb), self._ptr(d_blob),
-                                                          self._ptr(d_off), self._ptr(d_rs),
-                                                          WIRE_COMPRESSED if compressed else WIRE_UNCOMPRESSED, self._ptr(out["wire"]),
-                                                          self._ptr(out["proof"]), self._ptr(out["instance"]), self._ptr(out["nonces"]),
-                                                          self._ptr(out["status"]), self._ptr(out["num_unsatisfied"]), self._ptr(workspace),
-                                                          workspace.numel(), C.c_void_p(stream))
+        d_pkb, d_sgb, d_blob, d_off = _upload((pkb, sgb, blob, off), dev)
+        d_rs = rs if isinstance(rs, torch.Tensor) else _upload((np.ascontiguousarray(rs, dtype=np.uint64).reshape(8),), dev)[0]
+        out = {"wire": _empty(proof_wire_bytes(compressed), "uint8", dev),
+               "proof": _empty(48, "int64", dev),
+               "instance": _empty((int(info.num_instance), 4), "int64", dev),
+               "nonces": _empty((count, NONCE_LEN), "uint8", dev),
+               "status": _empty(count, "int32", dev),
+               "num_unsatisfied": _empty(1, "int32", dev)}
+        ws, ws_bytes = _workspace(workspace, dev, 256, self.aggregate_prove_workspace_bytes, pk, handle)
+        rc = self._lib.frw_aggregate_prove_from_bytes_dev(self._ctx, pk, handle, _p(d_pkb), _p(d_sgb), _p(d_blob), _p(d_off), _p(d_rs),
+                                                          _wire_mode(compressed), _p(out["wire"]), _p(out["proof"]), _p(out["instance"]),
+                                                          _p(out["nonces"]), _p(out["status"]), _p(out["num_unsatisfied"]), _p(ws),
+                                                          ws_bytes, C.c_void_p(stream))
         return self._aggregate_verdict(rc, out, out["status"], strict, "frw_aggregate_prove_from_bytes_dev")
 
     def groth16_setup_r1cs(self, handle, alpha, beta, gamma, delta, t, mode=KEY_AUTO, rank=0, world=1, want_vk=True):
@@ -1270,21 +1187,17 @@ class WitnessEngine:
         vk = np.zeros(84 + 12 * ni, dtype=np.uint64)
         h = C.c_void_p()
         opts = Groth16KeyOpts(int(mode), int(rank), int(world))
-        check(self._lib.frw_groth16_setup_r1cs_opts(handle, tox.ctypes.data_as(C.c_void_p), C.byref(opts), C.byref(h),
-                                                    vk.ctypes.data_as(C.c_void_p) if want_vk else None), "frw_groth16_setup_r1cs")
-        if not want_vk:
-            return h, None
-        return h, {"alpha_g1": vk[:12], "beta_g2": vk[12:36], "gamma_g2": vk[36:60], "delta_g2": vk[60:84],
-                   "gamma_abc_g1": vk[84:].reshape(-1, 12)}
+        check(self._lib.frw_groth16_setup_r1cs_opts(handle, _p(tox), C.byref(opts), C.byref(h), _p(vk) if want_vk else None),
+              "frw_groth16_setup_r1cs")
+        return h, (_vk_dict(vk) if want_vk else None)
 
     def r1cs_check_dev(self, handle, batch, d_wit, d_inst, d_num_unsatisfied, stream=0):
-        check(self._lib.frw_r1cs_check_dev(handle, batch, self._ptr(d_wit), self._ptr(d_inst),
-                                           self._ptr(d_num_unsatisfied), C.c_void_p(stream)), "frw_r1cs_check_dev")
+        check(self._lib.frw_r1cs_check_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_num_unsatisfied), C.c_void_p(stream)),
+              "frw_r1cs_check_dev")
 
     def r1cs_eval_dev(self, handle, batch, d_wit, d_inst, d_num_unsatisfied, d_abc, stream=0):
         """r1cs_check_dev + A z, B z, C z into d_abc (int64[batch, 3, C, 4], Montgomery)."""
-        check(self._lib.frw_r1cs_eval_dev(handle, batch, self._ptr(d_wit), self._ptr(d_inst),
-                                          self._ptr(d_num_unsatisfied), self._ptr(d_abc), C.c_void_p(stream)),
+        check(self._lib.frw_r1cs_eval_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_num_unsatisfied), _p(d_abc), C.c_void_p(stream)),
               "frw_r1cs_eval_dev")
 
     def r1cs_eval_scratch_bytes(self, handle, batch, with_products):
@@ -1292,10 +1205,8 @@ class WitnessEngine:
 
     def r1cs_eval_scratch_dev(self, handle, batch, d_wit, d_inst, d_num_unsatisfied, d_abc, d_scratch, scratch_bytes, stream=0):
         """frw_r1cs_eval_dev / frw_r1cs_check_dev (d_abc=None) with the caller's scratch: allocates nothing, capture-safe."""
-        check(self._lib.frw_r1cs_eval_scratch_dev(handle, batch, self._ptr(d_wit), self._ptr(d_inst), self._ptr(d_num_unsatisfied),
-                                                  self._ptr(d_abc) if d_abc is not None else None,
-                                                  self._ptr(d_scratch) if d_scratch is not None else None, scratch_bytes,
-                                                  C.c_void_p(stream)), "frw_r1cs_eval_scratch_dev")
+        check(self._lib.frw_r1cs_eval_scratch_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_num_unsatisfied), _p(d_abc), _p(d_scratch),
+                                                  scratch_bytes, C.c_void_p(stream)), "frw_r1cs_eval_scratch_dev")
 
     # ---- multi-scalar multiplication over BLS12-381 G1 (frw_msm.hip) --------------------------------------------------
     def msm_g1_load(self, bases, narrow=False, bare=False, wide=False):
@@ -1306,43 +1217,41 @@ class WitnessEngine:
         bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 12)
         h = C.c_void_p()
         if bare:
-            check(self._lib.frw_msm_g1_load_bare(self.device, bases.shape[0], bases.ctypes.data_as(C.c_void_p), 2 if wide else 1 if narrow else 0, C.byref(h)),
+            check(self._lib.frw_msm_g1_load_bare(self.device, bases.shape[0], _p(bases), 2 if wide else 1 if narrow else 0, C.byref(h)),
                   "frw_msm_g1_load_bare")
             return h
         fn = self._lib.frw_msm_g1_load_narrow if narrow else self._lib.frw_msm_g1_load
-        check(fn(self.device, bases.shape[0], bases.ctypes.data_as(C.c_void_p), C.byref(h)), "frw_msm_g1_load")
+        check(fn(self.device, bases.shape[0], _p(bases), C.byref(h)), "frw_msm_g1_load")
         return h
 
     def g1_fixed_base(self, scalars):
         """k_i G1 on the device: canonical scalars uint64[count, 4] -> uint64[count, 12] (ark-ff's bytes)."""
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros((scalars.shape[0], 12), dtype=np.uint64)
-        check(self._lib.frw_g1_fixed_base(self.device, scalars.shape[0], scalars.ctypes.data_as(C.c_void_p),
-                                          out.ctypes.data_as(C.c_void_p)), "frw_g1_fixed_base")
+        check(self._lib.frw_g1_fixed_base(self.device, scalars.shape[0], _p(scalars), _p(out)), "frw_g1_fixed_base")
         return out
 
     def g2_fixed_base(self, scalars):
         """k_i G2 on the device: canonical scalars uint64[count, 4] -> uint64[count, 24] (ark-ff's bytes)."""
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros((scalars.shape[0], 24), dtype=np.uint64)
-        check(self._lib.frw_g2_fixed_base(self.device, scalars.shape[0], scalars.ctypes.data_as(C.c_void_p),
-                                          out.ctypes.data_as(C.c_void_p)), "frw_g2_fixed_base")
+        check(self._lib.frw_g2_fixed_base(self.device, scalars.shape[0], _p(scalars), _p(out)), "frw_g2_fixed_base")
         return out
 
     def msm_g2_load(self, bases, narrow=False, bare=False, wide=False):
         bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 24)
         h = C.c_void_p()
         if bare:
-            check(self._lib.frw_msm_g2_load_bare(self.device, bases.shape[0], bases.ctypes.data_as(C.c_void_p), 2 if wide else 1 if narrow else 0, C.byref(h)),
+            check(self._lib.frw_msm_g2_load_bare(self.device, bases.shape[0], _p(bases), 2 if wide else 1 if narrow else 0, C.byref(h)),
                   "frw_msm_g2_load_bare")
             return h
         fn = self._lib.frw_msm_g2_load_narrow if narrow else self._lib.frw_msm_g2_load
-        check(fn(self.device, bases.shape[0], bases.ctypes.data_as(C.c_void_p), C.byref(h)), "frw_msm_g2_load")
+        check(fn(self.device, bases.shape[0], _p(bases), C.byref(h)), "frw_msm_g2_load")
         return h
 
     def msm_g2_dev(self, handle, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, stream=0):
-        check(self._lib.frw_msm_g2_dev(handle, batch, self._ptr(d_scalars), scalar_stride, 1 if montgomery else 0, self._ptr(d_out),
-                                       self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_msm_g2_dev")
+        check(self._lib.frw_msm_g2_dev(handle, batch, _p(d_scalars), scalar_stride, 1 if montgomery else 0, _p(d_out), _p(d_workspace),
+                                       workspace_bytes, C.c_void_p(stream)), "frw_msm_g2_dev")
 
     def msm_free(self, handle):
         self._lib.frw_msm_free(handle)
@@ -1354,12 +1263,12 @@ class WitnessEngine:
         return info
 
     def msm_g1_dev(self, handle, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, stream=0):
-        check(self._lib.frw_msm_g1_dev(handle, batch, self._ptr(d_scalars), scalar_stride, 1 if montgomery else 0, self._ptr(d_out),
-                                       self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_msm_g1_dev")
+        check(self._lib.frw_msm_g1_dev(handle, batch, _p(d_scalars), scalar_stride, 1 if montgomery else 0, _p(d_out), _p(d_workspace),
+                                       workspace_bytes, C.c_void_p(stream)), "frw_msm_g1_dev")
 
     def groth16_msm_h_dev(self, handle, batch, d_h, domain_size, d_out, d_workspace, workspace_bytes, stream=0):
-        check(self._lib.frw_groth16_msm_h_dev(handle, batch, self._ptr(d_h), domain_size, self._ptr(d_out), self._ptr(d_workspace),
-                                              workspace_bytes, C.c_void_p(stream)), "frw_groth16_msm_h_dev")
+        check(self._lib.frw_groth16_msm_h_dev(handle, batch, _p(d_h), domain_size, _p(d_out), _p(d_workspace), workspace_bytes,
+                                              C.c_void_p(stream)), "frw_groth16_msm_h_dev")
 
     # ---- a whole Groth16 proof per signature ---------------------------------------------------------------------------
     def groth16_pk_load(self, num_instance, num_witness, domain_size, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, a_query,
@@ -1373,7 +1282,7 @@ class WitnessEngine:
         want = [12, 12, 12, 24, 24, nv * 12, nv * 12, nv * 24, (domain_size - 1) * 12, num_witness * 12]
         if [a.size for a in arrs] != want:
             raise ValueError("proving key: wrong array sizes")
-        d = Groth16PkDesc(num_instance, num_witness, domain_size, *[a.ctypes.data_as(C.c_void_p) for a in arrs])
+        d = Groth16PkDesc(num_instance, num_witness, domain_size, *[_p(a) for a in arrs])
         h = C.c_void_p()
         opts = Groth16KeyOpts(int(mode), int(rank), int(world))
         check(self._lib.frw_groth16_pk_load_opts(self.device, C.byref(d), C.byref(opts), C.byref(h)), "frw_groth16_pk_load")
@@ -1394,24 +1303,19 @@ class WitnessEngine:
         vk = np.zeros(84 + 12 * info["num_instance"], dtype=np.uint64)
         h = C.c_void_p()
         opts = Groth16KeyOpts(int(mode), 0, 1)
-        check(self._lib.frw_groth16_pk_load_wire_dev(self.device, buf.ctypes.data_as(C.c_void_p), buf.size, 0 if compressed else 1,
-                                                     0 if checked else PK_POINTS_ARE_CHECKED, C.byref(opts), C.byref(h),
-                                                     vk.ctypes.data_as(C.c_void_p)), "frw_groth16_pk_load_wire_dev")
-        return h, {"alpha_g1": vk[:12], "beta_g2": vk[12:36], "gamma_g2": vk[36:60], "delta_g2": vk[60:84],
-                   "gamma_abc_g1": vk[84:].reshape(-1, 12)}
+        check(self._lib.frw_groth16_pk_load_wire_dev(self.device, _p(buf), buf.size, _wire_mode(compressed),
+                                                     0 if checked else PK_POINTS_ARE_CHECKED, C.byref(opts), C.byref(h), _p(vk)),
+              "frw_groth16_pk_load_wire_dev")
+        return h, _vk_dict(vk)
 
     def groth16_pk_to_wire(self, pk, vk, compressed=True):
         """The whole proving key behind a handle (table or bare, made by groth16_setup* or loaded) as the bytes ProvingKey::deserialize
         reads.  vk: the verifying key that came with the handle (dict or flat limbs): gamma_g2 and gamma_abc_g1 are taken from it."""
-        vk = _vk_flat(vk)
-        if vk.size < 96 or (vk.size - 84) % 12:
-            raise FrwError(-1, "groth16_pk_to_wire", "verifying key: expected 84 + 12 x num_instance uint64 values")
-        ni = (vk.size - 84) // 12
+        vk, ni = _vk_flat(vk, "groth16_pk_to_wire")
         info = self.groth16_pk_info(pk)
         nv = int(info.z_hi) - int(info.z_lo) - 3
         out = np.zeros(max(groth16_pk_wire_bytes(ni, nv - ni, int(info.h_hi) - int(info.h_lo) + 1, compressed), 1), dtype=np.uint8)
-        check(self._lib.frw_groth16_pk_to_wire_dev(pk, vk.ctypes.data_as(C.c_void_p), ni, 0 if compressed else 1, out.ctypes.data_as(C.c_void_p),
-                                                   out.size), "frw_groth16_pk_to_wire_dev")
+        check(self._lib.frw_groth16_pk_to_wire_dev(pk, _p(vk), ni, _wire_mode(compressed), _p(out), out.size), "frw_groth16_pk_to_wire_dev")
         return out.tobytes()
 
     def groth16_pk_info(self, pk):
@@ -1430,30 +1334,28 @@ class WitnessEngine:
     def groth16_prove_partial_dev(self, pk, r1cs, batch, d_wit, d_inst, rs, d_partial, d_workspace, workspace_bytes, d_num_unsatisfied=None, stream=0):
         """One rank's partial sums of a key in slices: d_partial int64[batch, 72] = A | B1' | L | H | B (ark-ff's affine bytes)."""
         rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
-        check(self._lib.frw_groth16_prove_partial_dev(pk, r1cs, batch, self._ptr(d_wit), self._ptr(d_inst), rs.ctypes.data_as(C.c_void_p),
-                                                      self._ptr(d_partial), self._ptr(d_num_unsatisfied) if d_num_unsatisfied is not None else None,
-                                                      self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_partial_dev")
+        check(self._lib.frw_groth16_prove_partial_dev(pk, r1cs, batch, _p(d_wit), _p(d_inst), _p(rs), _p(d_partial), _p(d_num_unsatisfied),
+                                                      _p(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_partial_dev")
 
     def groth16_prove_combine_dev(self, pk, world, d_partials, rs, d_proof, d_workspace, workspace_bytes, stream=0):
         """All ranks' partial sums (int64[world, 72], rank order) -> the proof int64[48]."""
         rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(2, 4)
-        check(self._lib.frw_groth16_prove_combine_dev(pk, world, self._ptr(d_partials), rs.ctypes.data_as(C.c_void_p), self._ptr(d_proof),
-                                                      self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_combine_dev")
+        check(self._lib.frw_groth16_prove_combine_dev(pk, world, _p(d_partials), _p(rs), _p(d_proof), _p(d_workspace), workspace_bytes,
+                                                      C.c_void_p(stream)), "frw_groth16_prove_combine_dev")
 
     def diag_groth16_side_counts(self, pk, d_z, d_workspace, workspace_bytes, stream=0):
         """(rows of b_g1_query / b_g2_query that hold a point, digits and ones over all rows, digits and ones over those rows): the point
         additions of the witness-side sums of a key of bare handles for the scalars d_z (z ++ [1, r, s] of the key's slice)."""
         out = np.zeros(5, dtype=np.uint64)
-        check(self._lib.frw_diag_groth16_side_counts(pk, self._ptr(d_z), self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream),
-                                                     out.ctypes.data_as(C.c_void_p)), "frw_diag_groth16_side_counts")
+        check(self._lib.frw_diag_groth16_side_counts(pk, _p(d_z), _p(d_workspace), workspace_bytes, C.c_void_p(stream), _p(out)),
+              "frw_diag_groth16_side_counts")
         return [int(v) for v in out]
 
     def diag_poly_eval_dev(self, d_coeffs, n, t):
         """p(t) for the polynomial whose n coefficients (ark-ff's Montgomery form) are in device memory; t, result: Python integers."""
         tt = np.frombuffer(int(t).to_bytes(32, "little"), dtype=np.uint64).copy()
         out = np.zeros(4, dtype=np.uint64)
-        check(self._lib.frw_diag_poly_eval_dev(self.device, n, self._ptr(d_coeffs), tt.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)),
-              "frw_diag_poly_eval_dev")
+        check(self._lib.frw_diag_poly_eval_dev(self.device, n, _p(d_coeffs), _p(tt), _p(out)), "frw_diag_poly_eval_dev")
         return int.from_bytes(out.tobytes(), "little")
 
     def groth16_setup(self, circuit, logn, alpha, beta, gamma, delta, t):
@@ -1462,10 +1364,8 @@ class WitnessEngine:
         L = circuit_layout(circuit, logn)
         vk = np.zeros(84 + 12 * L.num_instance, dtype=np.uint64)
         h = C.c_void_p()
-        check(self._lib.frw_groth16_setup(self.device, circuit, logn, tox.ctypes.data_as(C.c_void_p), C.byref(h),
-                                          vk.ctypes.data_as(C.c_void_p)), "frw_groth16_setup")
-        return h, {"alpha_g1": vk[:12], "beta_g2": vk[12:36], "gamma_g2": vk[36:60], "delta_g2": vk[60:84],
-                   "gamma_abc_g1": vk[84:].reshape(-1, 12)}
+        check(self._lib.frw_groth16_setup(self.device, circuit, logn, _p(tox), C.byref(h), _p(vk)), "frw_groth16_setup")
+        return h, _vk_dict(vk)
 
     def groth16_pk_free(self, handle):
         self._lib.frw_groth16_pk_free(handle)
@@ -1476,15 +1376,13 @@ class WitnessEngine:
     def groth16_prove_dev(self, pk, r1cs, batch, d_wit, d_inst, rs, d_proofs, d_workspace, workspace_bytes, d_num_unsatisfied=None, stream=0):
         """rs: host uint64[batch, 2, 4] (r, s per proof, canonical); d_proofs: int64[batch, 48] = A | B | C in ark-ff's bytes."""
         rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(batch, 2, 4)
-        check(self._lib.frw_groth16_prove_dev(pk, r1cs, batch, self._ptr(d_wit), self._ptr(d_inst), rs.ctypes.data_as(C.c_void_p),
-                                              self._ptr(d_proofs), self._ptr(d_num_unsatisfied) if d_num_unsatisfied is not None else None,
-                                              self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_dev")
+        check(self._lib.frw_groth16_prove_dev(pk, r1cs, batch, _p(d_wit), _p(d_inst), _p(rs), _p(d_proofs), _p(d_num_unsatisfied),
+                                              _p(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_dev")
 
     def groth16_prove_rs_dev(self, pk, r1cs, batch, d_wit, d_inst, d_rs, d_proofs, d_workspace, workspace_bytes, d_num_unsatisfied=None, stream=0):
         """The same with the blinding factors in device memory (d_rs: int64[batch, 2, 4]): stream-ordered throughout, capturable."""
-        check(self._lib.frw_groth16_prove_rs_dev(pk, r1cs, batch, self._ptr(d_wit), self._ptr(d_inst), self._ptr(d_rs),
-                                                 self._ptr(d_proofs), self._ptr(d_num_unsatisfied) if d_num_unsatisfied is not None else None,
-                                                 self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_rs_dev")
+        check(self._lib.frw_groth16_prove_rs_dev(pk, r1cs, batch, _p(d_wit), _p(d_inst), _p(d_rs), _p(d_proofs), _p(d_num_unsatisfied),
+                                                 _p(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_rs_dev")
 
     def qap_info(self, handle):
         """Domain of the QAP witness map for the loaded matrices: (log n, n, C, I, workspace bytes per signature)."""
@@ -1497,17 +1395,13 @@ class WitnessEngine:
                             stream=0):
         """ark-groth16's R1CStoQAP::witness_map for every signature of a resident batch: d_h = int64[batch, n, 4]
         (Montgomery), coefficient k of h(X) = (A B - C)(X) / (X^n - 1) at index k."""
-        check(self._lib.frw_qap_witness_map_dev(handle, batch, self._ptr(d_wit), self._ptr(d_inst), self._ptr(d_h),
-                                                self._ptr(d_num_unsatisfied) if d_num_unsatisfied is not None else None,
-                                                self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)),
-              "frw_qap_witness_map_dev")
+        check(self._lib.frw_qap_witness_map_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_h), _p(d_num_unsatisfied), _p(d_workspace),
+                                                workspace_bytes, C.c_void_p(stream)), "frw_qap_witness_map_dev")
 
     def qap_quotient_dev(self, handle, batch, d_wit, d_inst, d_h, d_workspace, workspace_bytes, d_num_unsatisfied=None, stream=0):
         """h with six transforms instead of seven: equal to qap_witness_map_dev's wherever d_num_unsatisfied is 0."""
-        check(self._lib.frw_qap_quotient_dev(handle, batch, self._ptr(d_wit), self._ptr(d_inst), self._ptr(d_h),
-                                             self._ptr(d_num_unsatisfied) if d_num_unsatisfied is not None else None,
-                                             self._ptr(d_workspace), workspace_bytes, C.c_void_p(stream)),
-              "frw_qap_quotient_dev")
+        check(self._lib.frw_qap_quotient_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_h), _p(d_num_unsatisfied), _p(d_workspace),
+                                             workspace_bytes, C.c_void_p(stream)), "frw_qap_quotient_dev")
 
     def qap_witness_map(self, handle, witness, instance):
         """Host arrays (uint64[batch, W, 4], uint64[batch, I, 4], Montgomery, as witness_ntt_verify returns them) ->
@@ -1518,10 +1412,8 @@ class WitnessEngine:
         n = int(self.qap_info(handle).domain_size)
         h = np.empty((batch, n, 4), dtype=np.uint64)
         bad = np.empty(batch, dtype=np.uint32)
-        check(self._lib.frw_qap_witness_map(handle, batch, witness.ctypes.data_as(C.c_void_p), instance.ctypes.data_as(C.c_void_p),
-                                            h.ctypes.data_as(C.c_void_p), bad.ctypes.data_as(C.c_void_p)), "frw_qap_witness_map")
+        check(self._lib.frw_qap_witness_map(handle, batch, _p(witness), _p(instance), _p(h), _p(bad)), "frw_qap_witness_map")
         return h, bad
 
     def digest_dev(self, d_buf, words_per_item, items, d_out, stream=0):
-        check(self._lib.frw_digest_dev(self._ctx, self._ptr(d_buf), words_per_item, items, self._ptr(d_out),
-                                       C.c_void_p(stream)), "frw_digest_dev")
+        check(self._lib.frw_digest_dev(self._ctx, _p(d_buf), words_per_item, items, _p(d_out), C.c_void_p(stream)), "frw_digest_dev")

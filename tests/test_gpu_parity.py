@@ -327,6 +327,25 @@ def test_genuine_falcon_signatures_end_to_end(engine, oracle):
                                    torch.from_numpy(dinst.view(np.int64)).to(dev)) == 0
 
 
+def test_prepare_inputs_of_no_signature_and_of_one(engine):
+    """prepare_inputs packs its bytes with the packer of the *_from_bytes calls: an empty batch hands the library one-byte
+    placeholders where it used to hand empty arrays (frw_prepare_inputs returns before it reads either), and one genuine
+    signature (tests/golden/falcon_signed.json) still decodes and hashes to the stored (sig, pk, hm)."""
+    import hashlib
+    import json
+    import os
+    sig, pk, hm, st = engine.prepare_inputs(9, [], [], [])
+    for a in (sig, pk, hm):
+        assert a.shape == (0, 512) and a.dtype == np.uint16
+    assert st.shape == (0,) and st.dtype == np.int32
+    cases = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "falcon_signed.json")))["cases"]
+    c = [x for x in cases if x["logn"] == 9][0]
+    sig, pk, hm, st = engine.prepare_inputs(9, [bytes.fromhex(c["pk_bytes"])], [bytes.fromhex(c["msg"])], [bytes.fromhex(c["sig_bytes"])])
+    assert st.tolist() == [0] and sig.shape == pk.shape == hm.shape == (1, 512)
+    for a, name in ((sig, "sig_sha256"), (pk, "pk_sha256"), (hm, "hm_sha256")):
+        assert hashlib.sha256(a[0].tobytes()).hexdigest() == c[name], name
+
+
 @pytest.mark.parametrize("logn", [9, 10])
 @pytest.mark.parametrize("enc", [0, 1])
 def test_dual_witness_matches_oracle(engine, oracle, logn, enc):

@@ -32,6 +32,7 @@
 #include "frw_fq29.h"
 #include "frw_quad.h"
 #include "frw_fr29.h"
+#include "frw_digits.h"
 #include "frw_layout.h"
 #include "frw_rows.h"
 
@@ -134,42 +135,11 @@ __global__ __launch_bounds__(64) void msm_ones_table_kernel(uint32_t n, const ui
     store_row<F>(ones_table + id * Grp<F>::PT_WORDS, pt_to_affine(acc));
 }
 
-// ---- the scalars: canonical integer, sixteen signed 16-bit digits ---------------------------------------------------------------
-// d_j in [-2^15, 2^15] with sum d_j 2^(16 j) = k; the top digit takes the last carry (k < 2^255, so it stays <= 2^15)
-// Returns true (and no digits) for the scalar 1: a Falcon witness is 45 % ones (the boolean elements that are set), which
-// would all land in bucket 0 of window 0 -- they are summed by msm_ones_kernel instead.
-// the scalar as a canonical integer below r
-__device__ __forceinline__ Fr8 scalar_canonical(const uint32_t *src, int montgomery)
-{
-    Fr8 w = fr_load(src);
-    if (montgomery) {
-        // ark-ff's h R (R = 2^256) -> h: one product with 2^5 in R' = 2^261 arithmetic (frw_fr29.h), then the canonical form
-        F29 c;
-#pragma unroll
-        for (int k = 0; k < NL29; k++) c.l[k] = k ? 0u : 32u;
-        w = f29_pack(f29_canonical(f29_mul(f29_unpack(w), c)));
-    } else {
-        // "canonical" is the caller's promise; any 256-bit integer is brought below r here (2^256 < 4 r: two conditional
-        // subtractions), because a top digit above 2^15 would index past the buckets -- and k P = (k mod r) P anyway
-        w = f29_pack(f29_canonical(f29_reduce_4p(f29_unpack(w))));
-    }
-    return w;
-}
-// detect_one == false (a bare handle, below): the scalar one is digit 1 of window 0 like any other value
-__device__ __forceinline__ bool scalar_digits(const uint32_t *src, int montgomery, int (&d)[MSM_W], bool detect_one = true)
-{
-    const Fr8 w = scalar_canonical(src, montgomery);
-    if (detect_one && w.l[0] == 1u && !(w.l[1] | w.l[2] | w.l[3] | w.l[4] | w.l[5] | w.l[6] | w.l[7])) return true;
-    int carry = 0;
-#pragma unroll
-    for (int j = 0; j < MSM_W; j++) {
-        int v = (int)((w.l[j >> 1] >> (16 * (j & 1))) & 0xffffu) + carry;
-        carry = 0;
-        if (j + 1 < MSM_W && v > MSM_BUCKETS) { v -= 1 << MSM_C; carry = 1; }
-        d[j] = v;
-    }
-    return false;
-}
+// ---- the scalars: canonical integer, signed digits, the bucket and the entry of a digit: frw_digits.h ---------------------------------
+// Sixteen 16-bit digits here (32 of 8 bits in the narrow pipeline, 13 of 20 on wide windows).  The scalar 1 gets no digits where it is
+// told apart (the sums over window tables, and the narrow sums of bare handles): a Falcon witness is 45 % ones, which would all land in
+// bucket 0 of window 0 -- they are summed by msm_ones_kernel / nmsm_ones_kernel instead.  To the dense sums of a bare handle the scalar
+// one is digit 1 of window 0 like any other value.
 
 // The counting sort of a signature's 16 n (digit, point) pairs by bucket, without a global atomic: the points are cut into
 // MSM_SLICES slices, a workgroup per (signature, slice) histograms its slice in LDS (32,768 counters = 128 KB of the CU's
@@ -185,43 +155,17 @@ __device__ __forceinline__ bool scalar_digits(const uint32_t *src, int montgomer
 // accumulations, one per 16-bit window, over the SAME rows: grid row y of every kernel below is window y of ONE scalar vector
 // (instead of signature y with all its windows), a row's entries are point indices, and msm_horner_kernel puts the sixteen window
 // sums together (15 x 16 doublings).  The number of bucket additions is the table path's: one per (point, non-zero digit).
-// the digit of window `win` (a register array indexed at run time would live in scratch: sixteen selects)
-__device__ __forceinline__ int msm_digit_of(const int (&d)[MSM_W], uint32_t win)
+
+// The elements [lo, hi) of n that the workgroup's slice (blockIdx.x of gridDim.x) sorts: equal runs, the last ones short or empty (lo may
+// lie past hi: slices x ceil(n / slices) < n + slices, nowhere near 2^32).  round_to: runs of whole tiles -- those slices may begin far
+// past n, so they are clamped, in 64 bits.
+struct SliceRange { uint32_t lo, hi; };
+__device__ __forceinline__ SliceRange slice_range(uint32_t n, uint32_t round_to = 1)
 {
-    int v = 0;
-#pragma unroll
-    for (int j = 0; j < MSM_W; j++) v = (uint32_t)j == win ? d[j] : v;
-    return v;
-}
-__global__ __launch_bounds__(1024) void msm_hist_kernel(uint32_t n, const uint32_t *__restrict__ scalars, size_t sig_stride_words,
-                                                        int montgomery, uint32_t *__restrict__ slice_hist /* [row][slice][buckets] */,
-                                                        uint32_t *__restrict__ ones_count /* [sig] */, uint32_t *__restrict__ ones_list /* [sig][n] */,
-                                                        int bare)
-{
-    __shared__ uint32_t hist[MSM_BUCKETS];
-    const size_t row = blockIdx.y, sig = bare ? 0 : row;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) hist[b] = 0;
-    __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        int d[MSM_W];
-        if (scalar_digits(scalars + sig * sig_stride_words + (size_t)i * 8, montgomery, d, !bare)) {
-            ones_list[sig * n + atomicAdd(&ones_count[sig], 1u)] = i;
-            continue;
-        }
-        if (bare) {
-            const int v = msm_digit_of(d, (uint32_t)row);
-            if (v) atomicAdd(&hist[(v < 0 ? -v : v) - 1], 1u);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < MSM_W; j++)
-            if (d[j]) atomicAdd(&hist[(d[j] < 0 ? -d[j] : d[j]) - 1], 1u);
-    }
-    __syncthreads();
-    uint32_t *out = slice_hist + (row * slices + slice) * MSM_BUCKETS;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) out[b] = hist[b];
+    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = ((n + slices - 1) / slices + round_to - 1) / round_to * round_to;
+    if (round_to == 1) return SliceRange{slice * per, slice * per + per < n ? slice * per + per : n};
+    const uint32_t lo = (uint64_t)slice * per < n ? slice * per : n;
+    return SliceRange{lo, (uint64_t)lo + per < n ? lo + per : n};
 }
 
 // A bare handle's sixteen window rows would each turn the scalars into digits again -- sixteen times the 32-byte reads and the
@@ -233,7 +177,7 @@ __global__ __launch_bounds__(256) void msm_digits_kernel(uint32_t n, const uint3
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int d[MSM_W];
-    (void)scalar_digits(scalars + (size_t)i * 8, montgomery, d, false);
+    signed_digits<MSM_C, MSM_W>(scalar_canonical(scalars + (size_t)i * 8, montgomery), d);
 #pragma unroll
     for (int j = 0; j < MSM_W; j++) digits[(size_t)j * n + i] = (int16_t)(d[j] == (1 << 15) ? -32768 : d[j]);     // (+2^15 does not fit: stored as its negative's code, told apart below)
 }
@@ -243,37 +187,74 @@ __device__ __forceinline__ int msm_digit_load(const int16_t *digits, size_t at)
     const int v = digits[at];
     return v == -32768 ? 1 << 15 : v;
 }
-__global__ __launch_bounds__(1024) void msm_hist_digits_kernel(uint32_t n, const int16_t *__restrict__ digits, uint32_t *__restrict__ slice_hist)
-{
-    __shared__ uint32_t hist[MSM_BUCKETS];
-    const size_t row = blockIdx.y;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) hist[b] = 0;
-    __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        const int v = msm_digit_load(digits, row * n + i);
-        if (v) atomicAdd(&hist[(v < 0 ? -v : v) - 1], 1u);
+
+// Where the digits of a flat sort come from.  A source says how many buckets a grid row has (BUCKETS), how many entries an element can
+// leave in it (PER_ROW: a row's entries are [row][PER_ROW n]), and hands each() the non-zero digits of element i of a row, each with the
+// id its entry carries; the histogram's pass (`first`) is also the one that records a scalar equal to one.
+// Window tables: grid row = signature, every window of the scalar, entry id = the table row j n + i of window j.  A scalar that is one
+// goes to the signature's list -- or, MASKED and asked for, into its bit mask (zeroed by the caller; the first n / 32 words of the list).
+template <int C, int W, bool MASKED> struct TableDigits {
+    static constexpr int BUCKETS = 1 << (C - 1), PER_ROW = W;
+    const uint32_t *scalars;
+    size_t sig_stride_words;
+    int montgomery;
+    uint32_t *ones_count /* [sig] */, *ones_list /* [sig][n] */;
+    int ones_as_mask;
+    template <class Fn> __device__ __forceinline__ void each(size_t sig, uint32_t n, uint32_t i, bool first, Fn fn) const
+    {
+        const Fr8 k = scalar_canonical(scalars + sig * sig_stride_words + (size_t)i * 8, montgomery);
+        if (scalar_is_one(k)) {
+            if (!first) return;
+            if (MASKED && ones_as_mask) atomicOr(&ones_list[sig * n + (i >> 5)], 1u << (i & 31));
+            else ones_list[sig * n + atomicAdd(&ones_count[sig], 1u)] = i;
+            return;
+        }
+        int d[W];
+        signed_digits<C, W>(k, d);
+#pragma unroll
+        for (int j = 0; j < W; j++)
+            if (d[j]) fn(d[j], (uint32_t)j * n + i);
     }
+};
+typedef TableDigits<MSM_C, MSM_W, false> DenseTableDigits;
+typedef TableDigits<NMSM_C, NMSM_W, true> NarrowTableDigits;
+// A dense bare handle: grid row = window, its stored digit of scalar i, entry id = the point i.  No scalar is told apart as one.
+struct StoredDigits {
+    static constexpr int BUCKETS = MSM_BUCKETS, PER_ROW = 1;
+    const int16_t *digits;
+    template <class Fn> __device__ __forceinline__ void each(size_t row, uint32_t n, uint32_t i, bool, Fn fn) const
+    {
+        const int v = msm_digit_load(digits, row * n + i);
+        if (v) fn(v, i);
+    }
+};
+template <class Src>
+__global__ __launch_bounds__(1024) void msm_sort_hist_kernel(uint32_t n, const Src src, uint32_t *__restrict__ slice_hist /* [row][slice][buckets] */)
+{
+    __shared__ uint32_t hist[Src::BUCKETS];
+    const size_t row = blockIdx.y;
+    const SliceRange s = slice_range(n);
+    for (int b = threadIdx.x; b < Src::BUCKETS; b += 1024) hist[b] = 0;
     __syncthreads();
-    uint32_t *out = slice_hist + (row * slices + slice) * MSM_BUCKETS;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) out[b] = hist[b];
+    for (uint32_t i = s.lo + threadIdx.x; i < s.hi; i += 1024)
+        src.each(row, n, i, true, [&](int v, uint32_t) { atomicAdd(&hist[digit_bucket(v)], 1u); });
+    __syncthreads();
+    uint32_t *out = slice_hist + (row * gridDim.x + blockIdx.x) * Src::BUCKETS;
+    for (int b = threadIdx.x; b < Src::BUCKETS; b += 1024) out[b] = hist[b];
 }
-__global__ __launch_bounds__(1024) void msm_scatter_digits_kernel(uint32_t n, const int16_t *__restrict__ digits, const uint32_t *__restrict__ offsets,
-                                                                  const uint32_t *__restrict__ slice_hist, uint32_t *__restrict__ entries)
+template <class Src>
+__global__ __launch_bounds__(1024) void msm_sort_scatter_kernel(uint32_t n, const Src src, const uint32_t *__restrict__ offsets,
+                                                                const uint32_t *__restrict__ slice_hist, uint32_t *__restrict__ entries)
 {
-    __shared__ uint32_t cursor[MSM_BUCKETS];
+    __shared__ uint32_t cursor[Src::BUCKETS];
     const size_t row = blockIdx.y;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    const uint32_t *first = slice_hist + (row * slices + slice) * MSM_BUCKETS, *off = offsets + row * MSM_BUCKETS;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) cursor[b] = off[b] + first[b];
+    const SliceRange s = slice_range(n);
+    const uint32_t *first = slice_hist + (row * gridDim.x + blockIdx.x) * Src::BUCKETS, *off = offsets + row * Src::BUCKETS;
+    for (int b = threadIdx.x; b < Src::BUCKETS; b += 1024) cursor[b] = off[b] + first[b];
     __syncthreads();
-    uint32_t *ent = entries + row * (size_t)n;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        const int v = msm_digit_load(digits, row * n + i);
-        if (v) ent[atomicAdd(&cursor[(uint32_t)(v < 0 ? -v : v) - 1u], 1u)] = i | (v < 0 ? 0x80000000u : 0u);
-    }
+    uint32_t *ent = entries + row * (size_t)Src::PER_ROW * n;
+    for (uint32_t i = s.lo + threadIdx.x; i < s.hi; i += 1024)
+        src.each(row, n, i, false, [&](int v, uint32_t id) { ent[atomicAdd(&cursor[digit_bucket(v)], 1u)] = digit_entry(id, v); });
 }
 
 // ---- WIDE windows for the largest bare sums (round 5) -------------------------------------------------------------------------------
@@ -286,21 +267,6 @@ __global__ __launch_bounds__(1024) void msm_scatter_digits_kernel(uint32_t n, co
 // S0 = sum B_lo; a window is sum_hi S1_hi + 2^15 sum_hi hi S0_hi (msm_wide_window_kernel), the windows join by Horner's rule with 20
 // doublings each.  The folds of 13 x 2^19 buckets are a fixed 14 ms, three windows' additions 0.18 ns a point: handles of 2^26 points and
 // more take wide windows by themselves (MSM_WIDE_FROM_DEFAULT), smaller ones when loaded so.
-// signed 20-bit digits, d_j in [-2^19 + 1, 2^19], sum d_j 2^(20 j) = k; the top window (bits 240 ..) takes the last carry
-__device__ __forceinline__ void scalar_digits_wide(const uint32_t *src, int montgomery, int (&d)[WIDE_W])
-{
-    const Fr8 w = scalar_canonical(src, montgomery);
-    int carry = 0;
-#pragma unroll
-    for (int j = 0; j < WIDE_W; j++) {
-        const int bit = WIDE_C * j, k = bit >> 5, sh = bit & 31;
-        const uint64_t two = (uint64_t)w.l[k] | (k + 1 < 8 ? (uint64_t)w.l[k + 1] << 32 : 0ull);
-        int v = (int)((two >> sh) & ((1u << WIDE_C) - 1u)) + carry;
-        carry = 0;
-        if (j + 1 < WIDE_W && v > (1 << (WIDE_C - 1))) { v -= 1 << WIDE_C; carry = 1; }
-        d[j] = v;
-    }
-}
 // The sort, every pass writing RUNS (the first version of it scattered 4-byte entries into 208 x 32,768 open cache lines: each such write a
 // read-modify-write of a line in HBM, 76 ms for 1.7 x 10^9 of them -- all that three windows' additions saved):
 //   digits     int32[13][n], written once
@@ -315,7 +281,7 @@ __global__ __launch_bounds__(256) void msm_wide_digits_kernel(uint32_t n, const 
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int d[WIDE_W];
-    scalar_digits_wide(scalars + (size_t)i * 8, montgomery, d);
+    signed_digits<WIDE_C, WIDE_W>(scalar_canonical(scalars + (size_t)i * 8, montgomery), d);     // (the top window: bits 240 ..)
 #pragma unroll
     for (int j = 0; j < WIDE_W; j++) digits[(size_t)j * n + i] = d[j];
 }
@@ -323,16 +289,15 @@ __global__ __launch_bounds__(1024) void msm_wide_bin_hist_kernel(uint32_t n, con
 {
     __shared__ uint32_t hist[WIDE_BINS];
     const size_t j = blockIdx.y;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = ((n + slices - 1) / slices + WIDE_TILE - 1) / WIDE_TILE * WIDE_TILE;
-    const uint32_t lo = (uint64_t)slice * per < n ? slice * per : n, hi = (uint64_t)lo + per < n ? lo + per : n;
+    const SliceRange s = slice_range(n, WIDE_TILE);
     if (threadIdx.x < WIDE_BINS) hist[threadIdx.x] = 0;
     __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
+    for (uint32_t i = s.lo + threadIdx.x; i < s.hi; i += 1024) {
         const int v = digits[j * n + i];
-        if (v) atomicAdd(&hist[((uint32_t)(v < 0 ? -v : v) - 1u) >> 10], 1u);
+        if (v) atomicAdd(&hist[digit_bucket(v) >> 10], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < WIDE_BINS) slice_hist[(j * slices + slice) * WIDE_BINS + threadIdx.x] = hist[threadIdx.x];
+    if (threadIdx.x < WIDE_BINS) slice_hist[(j * gridDim.x + blockIdx.x) * WIDE_BINS + threadIdx.x] = hist[threadIdx.x];
 }
 // every slice's first position inside its bins; the bins' sizes and starts; the rows' (one workgroup)
 __global__ __launch_bounds__(1024) void msm_wide_bin_offsets_kernel(uint32_t slices, uint32_t *__restrict__ slice_hist, uint32_t *__restrict__ bin_count,
@@ -374,10 +339,10 @@ __global__ __launch_bounds__(1024) void msm_wide_bin_scatter_kernel(uint32_t n, 
     __shared__ unsigned long long gpos[WIDE_BINS];
     const size_t j = blockIdx.y;
     const uint32_t t = threadIdx.x;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = ((n + slices - 1) / slices + WIDE_TILE - 1) / WIDE_TILE * WIDE_TILE;
-    const uint32_t lo = (uint64_t)slice * per < n ? slice * per : n, hi = (uint64_t)lo + per < n ? lo + per : n;
-    if (t < WIDE_BINS) gpos[t] = bin_start[j * WIDE_BINS + t] + slice_hist[(j * slices + slice) * WIDE_BINS + t];
-    for (uint32_t tile0 = lo; tile0 < hi; tile0 += WIDE_TILE) {
+    const SliceRange s = slice_range(n, WIDE_TILE);
+    const uint32_t hi = s.hi;
+    if (t < WIDE_BINS) gpos[t] = bin_start[j * WIDE_BINS + t] + slice_hist[(j * gridDim.x + blockIdx.x) * WIDE_BINS + t];
+    for (uint32_t tile0 = s.lo; tile0 < hi; tile0 += WIDE_TILE) {
         if (t < WIDE_BINS) { tcount[t] = 0; tfill[t] = 0; }
         __syncthreads();
         int dv[WIDE_TILE / 1024];
@@ -385,7 +350,7 @@ __global__ __launch_bounds__(1024) void msm_wide_bin_scatter_kernel(uint32_t n, 
         for (int k = 0; k < WIDE_TILE / 1024; k++) {
             const uint32_t i = tile0 + t + 1024u * k;
             dv[k] = i < hi ? digits[j * n + i] : 0;
-            if (dv[k]) atomicAdd(&tcount[((uint32_t)(dv[k] < 0 ? -dv[k] : dv[k]) - 1u) >> 10], 1u);
+            if (dv[k]) atomicAdd(&tcount[digit_bucket(dv[k]) >> 10], 1u);
         }
         __syncthreads();
         // exclusive prefix sums of the 512 counts: within each of the first eight wavefronts by shuffles, their totals through LDS (two
@@ -410,9 +375,9 @@ __global__ __launch_bounds__(1024) void msm_wide_bin_scatter_kernel(uint32_t n, 
 #pragma unroll
         for (int k = 0; k < WIDE_TILE / 1024; k++) {
             if (!dv[k]) continue;
-            const uint32_t i = tile0 + t + 1024u * k, m = (uint32_t)(dv[k] < 0 ? -dv[k] : dv[k]) - 1u, bin = m >> 10;
+            const uint32_t i = tile0 + t + 1024u * k, m = digit_bucket(dv[k]), bin = m >> 10;
             const uint32_t pos = tstart[bin] + atomicAdd(&tfill[bin], 1u);
-            stage[pos] = make_uint2(i | (dv[k] < 0 ? 0x80000000u : 0u), m & (WIDE_BIN_BUCKETS - 1));
+            stage[pos] = make_uint2(digit_entry(i, dv[k]), m & (WIDE_BIN_BUCKETS - 1));
             sbin[pos] = (uint16_t)bin;
         }
         __syncthreads();
@@ -554,35 +519,6 @@ __global__ __launch_bounds__(1024) void msm_scan_kernel(const uint32_t *__restri
     for (int k = 0; k < PER; k++) offsets[sig * MSM_BUCKETS + t * PER + k] = base + local[k];
 }
 
-__global__ __launch_bounds__(1024) void msm_scatter_kernel(uint32_t n, const uint32_t *__restrict__ scalars, size_t sig_stride_words,
-                                                           int montgomery, const uint32_t *__restrict__ offsets,
-                                                           const uint32_t *__restrict__ slice_hist, uint32_t *__restrict__ entries, int bare)
-{
-    __shared__ uint32_t cursor[MSM_BUCKETS];
-    const size_t row = blockIdx.y, sig = bare ? 0 : row;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    const uint32_t *first = slice_hist + (row * slices + slice) * MSM_BUCKETS, *off = offsets + row * MSM_BUCKETS;
-    for (int b = threadIdx.x; b < MSM_BUCKETS; b += 1024) cursor[b] = off[b] + first[b];
-    __syncthreads();
-    uint32_t *ent = entries + row * (bare ? (size_t)n : (size_t)MSM_W * n);      // a bare row: one window, entries = point indices
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        int d[MSM_W];
-        if (scalar_digits(scalars + sig * sig_stride_words + (size_t)i * 8, montgomery, d, !bare)) continue;
-        if (bare) {
-            const int v = msm_digit_of(d, (uint32_t)row);
-            if (v) ent[atomicAdd(&cursor[(uint32_t)(v < 0 ? -v : v) - 1u], 1u)] = i | (v < 0 ? 0x80000000u : 0u);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < MSM_W; j++) {
-            if (!d[j]) continue;
-            const uint32_t b = (uint32_t)(d[j] < 0 ? -d[j] : d[j]) - 1u;
-            ent[atomicAdd(&cursor[b], 1u)] = ((uint32_t)j * n + i) | (d[j] < 0 ? 0x80000000u : 0u);
-        }
-    }
-}
-
 // Work items.  A bucket is added up by one thread, so a bucket far above the mean is a serial chain the whole call waits for:
 // a Falcon witness as scalars leaves 35,000 pairs in all, 775 of them in the bucket of digit +-1 (carries of the recoding),
 // and a lone wavefront needs ~18 us per addition.  Buckets are therefore cut into ITEMS of at most `split` entries, equal
@@ -606,6 +542,12 @@ __device__ __forceinline__ uint32_t msm_split_of(uint32_t total, uint32_t finer)
     const uint32_t s = (uint32_t)(((uint64_t)total * 3 + 2 * MSM_BUCKETS - 1) / (2 * MSM_BUCKETS)) / finer;
     return s < 32u ? 32u : s;
 }
+// a row's entries in all (the last bucket's start and size), and how many items a bucket of c entries becomes: equal parts of at most `split`
+__device__ __forceinline__ uint32_t row_total(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ counts, size_t row, int buckets)
+{
+    return offsets[row * buckets + buckets - 1] + counts[row * buckets + buckets - 1];
+}
+__device__ __forceinline__ uint32_t items_of(uint32_t c, uint32_t split) { return c <= split ? 1u : (c + split - 1) / split; }
 __global__ __launch_bounds__(1024) void msm_order_kernel(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ offsets,
                                                          uint32_t *__restrict__ order, uint32_t *__restrict__ item_first /* [sig][buckets] */,
                                                          uint32_t *__restrict__ items /* [sig][max_items][2]: bucket, part */,
@@ -638,13 +580,13 @@ __global__ __launch_bounds__(1024) void msm_order_kernel(const uint32_t *__restr
     __threadfence_block();
     __syncthreads();
     // items: rank by rank, ceil(c / split) each (an empty bucket keeps one: its thread stores the identity)
-    const uint32_t total = offsets[sig * MSM_BUCKETS + MSM_BUCKETS - 1] + cnt[MSM_BUCKETS - 1], split = msm_split_of(total, finer);
+    const uint32_t split = msm_split_of(row_total(offsets, counts, sig, MSM_BUCKETS), finer);
     constexpr int PER = MSM_BUCKETS / 1024;
     uint32_t k[PER], local = 0;
 #pragma unroll
     for (int j = 0; j < PER; j++) {
         const uint32_t c = cnt[ord[t * PER + j]];
-        k[j] = c <= split ? 1u : (c + split - 1) / split;
+        k[j] = items_of(c, split);
         local += k[j];
     }
     hist[t] = local;
@@ -687,8 +629,7 @@ __global__ __launch_bounds__(64, 2) void msm_bucket_kernel(MsmDev m, const uint3
     const uint2 item = *(const uint2 *)(items + (sig * (size_t)max_items + it) * 2);
     const uint32_t b = item.x, chunk = item.y;
     const uint32_t c = counts[sig * MSM_BUCKETS + b];
-    const uint32_t total = offsets[sig * MSM_BUCKETS + MSM_BUCKETS - 1] + counts[sig * MSM_BUCKETS + MSM_BUCKETS - 1], split = msm_split_of(total, finer);
-    const uint32_t k = c <= split ? 1u : (c + split - 1) / split;
+    const uint32_t k = items_of(c, msm_split_of(row_total(offsets, counts, sig, MSM_BUCKETS), finer));
     const uint32_t lo = (uint32_t)((uint64_t)c * chunk / k), cnt = (uint32_t)((uint64_t)c * (chunk + 1) / k) - lo;     // equal parts
     const uint32_t *ent = entries + (row_base ? (size_t)row_base[sig] : sig * ent_stride) + offsets[sig * MSM_BUCKETS + b] + lo;
     XyzzT<F> acc = pt_identity<F>();
@@ -785,8 +726,7 @@ __global__ __launch_bounds__(64, 2) void msm_combine_kernel(const uint32_t *__re
     const size_t sig = blockIdx.y;
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     const uint32_t c = counts[sig * MSM_BUCKETS + b];
-    const uint32_t total = offsets[sig * MSM_BUCKETS + MSM_BUCKETS - 1] + counts[sig * MSM_BUCKETS + MSM_BUCKETS - 1], split = msm_split_of(total, finer);
-    const uint32_t k = c <= split ? 1u : (c + split - 1) / split;
+    const uint32_t k = items_of(c, msm_split_of(row_total(offsets, counts, sig, MSM_BUCKETS), finer));
     const uint32_t *src = partial_items + (sig * (size_t)max_items + item_first[sig * MSM_BUCKETS + b]) * (size_t)BW;
     XyzzT<F> acc = load_bucket<F>(src);
     for (uint32_t j = 1; j < k; j++) acc = pt_add(acc, load_bucket<F>(src + (size_t)j * BW));
@@ -879,21 +819,8 @@ __global__ __launch_bounds__(MSM_FOLD_THREADS) void msm_fold2_kernel(const uint3
 // per signature, cut into ~2,048 equal work items, and the fold is one workgroup: a suffix scan and a tree over 128 points.
 // slices of the counting sort (a workgroup of 1,024 threads each): 16 per signature, 128 beyond 2^18 scalars (an aggregate statement is
 // one "signature": 16 workgroups for 2.5 M scalars were 1.2 ms at the head of every other kernel of its proof)
-// (1,024 slices for the 2^27-scalar sums were tried: the histogram no faster -- it waited for ONE global counter, see wave_append -- and the
-// scatter three times slower: a slice's run inside a bucket is a 1,024th of it, and the entry array's lines left the L2 half written)
-// list[(*count)++] = value for the lanes of a wavefront that ask for it: ONE atomic per wavefront (the scalars equal to one are 55 % of a
-// witness: 65 M increments of one address in the 1,024-statement proof, 20 ms of a histogram pass that computes for two)
-__device__ __forceinline__ void wave_append(bool want, uint32_t *__restrict__ count, uint32_t *__restrict__ list, uint32_t value)
-{
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
-    if (!mask) return;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));   // wanting lanes below this one
-    const int leader = __builtin_ctzll(mask);
-    uint32_t base = 0;
-    if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader, 64);
-    if (want) list[base + lane] = value;
-}
+// (1,024 slices for the 2^27-scalar sums were tried: the histogram no faster -- it waited for ONE global counter, that of the list of
+// ones: see nmsm_hist_bare_kernel -- and the scatter three times slower: a slice's run inside a bucket is a 1,024th of it, and the entry array's lines left the L2 half written)
 // Work items per signature: 2,048 for the per-signature circuits (n < 2^18 points), n / 128 rounded up to a multiple of 2,048 beyond
 // (an aggregate statement is ONE "signature" with sixteen times the points: 2,048 items would be 32 wavefronts on 1,024 SIMDs, each
 // a chain of 550 additions); items <= buckets + total / split <= 128 + target, rounded up to whole wavefronts.
@@ -901,50 +828,10 @@ __device__ __forceinline__ void wave_append(bool want, uint32_t *__restrict__ co
 // the fold); with more than 2^18 points up to 65,536 threads, whose <= 1,024 partial sums a small kernel brings down to 64 first
 // threads of the one-workgroup fold: 128 for the buckets + 256 (G1) / 128 (G2: four waves = one per SIMD, the whole register file
 // for an addition that needs 300 live registers) for the ones' partial sums
-__device__ __forceinline__ bool scalar_digits8(const uint32_t *src, int montgomery, int (&d)[NMSM_W])
-{
-    const Fr8 w = scalar_canonical(src, montgomery);
-    if (w.l[0] == 1u && !(w.l[1] | w.l[2] | w.l[3] | w.l[4] | w.l[5] | w.l[6] | w.l[7])) return true;
-    int carry = 0;
-#pragma unroll
-    for (int j = 0; j < NMSM_W; j++) {
-        int v = (int)((w.l[j >> 2] >> (8 * (j & 3))) & 0xffu) + carry;        // the top byte of a value below r is <= 0x73: no carry out
-        carry = 0;
-        if (j + 1 < NMSM_W && v > NMSM_BUCKETS) { v -= 1 << NMSM_C; carry = 1; }
-        d[j] = v;
-    }
-    return false;
-}
 __device__ __forceinline__ uint32_t nmsm_split_of(uint32_t total, uint32_t target)
 {
     const uint32_t s = (total + target - 1) / target;
     return s < 32u ? 32u : s;
-}
-__global__ __launch_bounds__(1024) void nmsm_hist_kernel(uint32_t n, const uint32_t *__restrict__ scalars, size_t sig_stride_words, int montgomery,
-                                                         uint32_t *__restrict__ slice_hist /* [sig][slice][128] */,
-                                                         uint32_t *__restrict__ ones_count /* [sig] */, uint32_t *__restrict__ ones_list /* [sig][n] */,
-                                                         int ones_as_mask)
-{
-    __shared__ uint32_t hist[NMSM_BUCKETS];
-    const size_t sig = blockIdx.y;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    if (threadIdx.x < NMSM_BUCKETS) hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        int d[NMSM_W];
-        if (scalar_digits8(scalars + sig * sig_stride_words + (size_t)i * 8, montgomery, d)) {
-            // the scalar is one: a bit of the signature's mask (zeroed by the caller; the first n / 32 words of its list), or an entry of its list
-            if (ones_as_mask) atomicOr(&ones_list[sig * n + (i >> 5)], 1u << (i & 31));
-            else ones_list[sig * n + atomicAdd(&ones_count[sig], 1u)] = i;
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < NMSM_W; j++)
-            if (d[j]) atomicAdd(&hist[(d[j] < 0 ? -d[j] : d[j]) - 1], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < NMSM_BUCKETS) slice_hist[(sig * slices + slice) * NMSM_BUCKETS + threadIdx.x] = hist[threadIdx.x];
 }
 // one workgroup of 128 threads per signature: bucket sizes and starts, every slice's first position inside its buckets, the
 // work items (bucket | part << 8: equal parts of at most `split` entries)
@@ -982,34 +869,11 @@ __global__ __launch_bounds__(NMSM_BUCKETS) void nmsm_plan_kernel(uint32_t *__res
     __syncthreads();
     counts[sig * NMSM_BUCKETS + b] = c;
     offsets[sig * NMSM_BUCKETS + b] = incl - c;
-    const uint32_t k = c <= split ? 1u : (c + split - 1) / split;
+    const uint32_t k = items_of(c, split);
     const uint32_t kincl = inclusive_scan(k), first = kincl - k;
     item_first[sig * NMSM_BUCKETS + b] = first;
     if (b == NMSM_BUCKETS - 1) item_count[sig] = kincl;
     for (uint32_t part = 0; part < k; part++) items[sig * (size_t)max_items + first + part] = (uint32_t)b | (part << 8);
-}
-__global__ __launch_bounds__(1024) void nmsm_scatter_kernel(uint32_t n, const uint32_t *__restrict__ scalars, size_t sig_stride_words, int montgomery,
-                                                            const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ slice_hist,
-                                                            uint32_t *__restrict__ entries /* [sig][32 n] */)
-{
-    __shared__ uint32_t cursor[NMSM_BUCKETS];
-    const size_t sig = blockIdx.y;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
-    if (threadIdx.x < NMSM_BUCKETS)
-        cursor[threadIdx.x] = offsets[sig * NMSM_BUCKETS + threadIdx.x] + slice_hist[(sig * slices + slice) * NMSM_BUCKETS + threadIdx.x];
-    __syncthreads();
-    uint32_t *ent = entries + sig * (size_t)NMSM_W * n;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += 1024) {
-        int d[NMSM_W];
-        if (scalar_digits8(scalars + sig * sig_stride_words + (size_t)i * 8, montgomery, d)) continue;
-#pragma unroll
-        for (int j = 0; j < NMSM_W; j++) {
-            if (!d[j]) continue;
-            const uint32_t b = (uint32_t)(d[j] < 0 ? -d[j] : d[j]) - 1u;
-            ent[atomicAdd(&cursor[b], 1u)] = ((uint32_t)j * n + i) | (d[j] < 0 ? 0x80000000u : 0u);
-        }
-    }
 }
 // ---- the narrow sums of a BARE handle (round 5: a key whose window tables would not fit; the points only) ------------------------------
 // One scalar vector, thirty-two 8-bit windows: the counting sort is over (window, digit) -- 4,096 counters in 16 KB of LDS, ONE pass over
@@ -1034,8 +898,9 @@ __global__ __launch_bounds__(1024) void nmsm_hist_bare_kernel(uint32_t n, const 
     __shared__ uint32_t hist[NMSM_W * NMSM_BUCKETS];
     __shared__ uint32_t ones_buf[ONES_CAP];
     __shared__ uint32_t ones_fill, ones_base;
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
+    const uint32_t slices = gridDim.x, slice = blockIdx.x;
+    const SliceRange s = slice_range(n);
+    const uint32_t hi = s.hi;
     for (int b = threadIdx.x; b < NMSM_W * NMSM_BUCKETS; b += 1024) hist[b] = 0;
     if (threadIdx.x == 0) ones_fill = 0;
     __syncthreads();
@@ -1047,19 +912,21 @@ __global__ __launch_bounds__(1024) void nmsm_hist_bare_kernel(uint32_t n, const 
         if (threadIdx.x == 0) ones_fill = 0;
         __syncthreads();
     };
-    for (uint32_t k0 = lo; k0 < hi; k0 += 1024) {                      // (the same number of rounds for every thread: barriers inside)
+    for (uint32_t k0 = s.lo; k0 < hi; k0 += 1024) {                    // (the same number of rounds for every thread: barriers inside)
         const uint32_t k = k0 + threadIdx.x;
         bool one = false;
         if (k < hi) {
             const uint32_t i = index ? index[k] : k;
-            int d[NMSM_W];
-            one = scalar_digits8(scalars + (size_t)i * 8, montgomery, d);
+            const Fr8 sc = scalar_canonical(scalars + (size_t)i * 8, montgomery);
+            one = scalar_is_one(sc);
             if (one) {
                 ones_buf[atomicAdd(&ones_fill, 1u)] = i;               // (at most 1,024 a round, and a round starts with 3,072 free)
             } else {
+                int d[NMSM_W];
+                signed_digits<NMSM_C, NMSM_W>(sc, d);
 #pragma unroll
                 for (int j = 0; j < NMSM_W; j++)
-                    if (d[j]) atomicAdd(&hist[j * NMSM_BUCKETS + (d[j] < 0 ? -d[j] : d[j]) - 1], 1u);
+                    if (d[j]) atomicAdd(&hist[j * NMSM_BUCKETS + digit_bucket(d[j])], 1u);
             }
         }
         __syncthreads();
@@ -1091,22 +958,21 @@ __global__ __launch_bounds__(1024) void nmsm_scatter_bare_kernel(uint32_t n, con
 {
     __shared__ uint32_t cursor[NMSM_W * NMSM_BUCKETS];
     __shared__ unsigned long long base[NMSM_W];
-    const uint32_t slices = gridDim.x, slice = blockIdx.x, per = (n + slices - 1) / slices;
-    const uint32_t lo = slice * per, hi = lo + per < n ? lo + per : n;
+    const uint32_t slices = gridDim.x, slice = blockIdx.x;
+    const SliceRange s = slice_range(n);
     for (int b = threadIdx.x; b < NMSM_W * NMSM_BUCKETS; b += 1024)
         cursor[b] = offsets[b] + slice_hist[((size_t)(b / NMSM_BUCKETS) * slices + slice) * NMSM_BUCKETS + (b % NMSM_BUCKETS)];
     if (threadIdx.x < NMSM_W) base[threadIdx.x] = entry_base[threadIdx.x];
     __syncthreads();
-    for (uint32_t k = lo + threadIdx.x; k < hi; k += 1024) {
+    for (uint32_t k = s.lo + threadIdx.x; k < s.hi; k += 1024) {
         const uint32_t i = index ? index[k] : k;
+        const Fr8 sc = scalar_canonical(scalars + (size_t)i * 8, montgomery);
+        if (scalar_is_one(sc)) continue;
         int d[NMSM_W];
-        if (scalar_digits8(scalars + (size_t)i * 8, montgomery, d)) continue;
+        signed_digits<NMSM_C, NMSM_W>(sc, d);
 #pragma unroll
-        for (int j = 0; j < NMSM_W; j++) {
-            if (!d[j]) continue;
-            const uint32_t b = (uint32_t)(d[j] < 0 ? -d[j] : d[j]) - 1u;
-            entries[base[j] + atomicAdd(&cursor[j * NMSM_BUCKETS + b], 1u)] = i | (d[j] < 0 ? 0x80000000u : 0u);
-        }
+        for (int j = 0; j < NMSM_W; j++)
+            if (d[j]) entries[base[j] + atomicAdd(&cursor[j * NMSM_BUCKETS + digit_bucket(d[j])], 1u)] = digit_entry(i, d[j]);
     }
 }
 // one thread per (signature, item): the sum of the item's table rows
@@ -1126,8 +992,7 @@ __global__ __launch_bounds__(64, F::LANES > 1 ? 1 : 2) void nmsm_bucket_kernel(N
     if (it >= item_count[sig]) return;
     const uint32_t item = items[sig * (size_t)max_items + it], b = item & (NMSM_BUCKETS - 1), part = item >> 8;
     const uint32_t c = counts[sig * NMSM_BUCKETS + b];
-    const uint32_t total = offsets[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1] + counts[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1], split = nmsm_split_of(total, target);
-    const uint32_t k = c <= split ? 1u : (c + split - 1) / split;
+    const uint32_t k = items_of(c, nmsm_split_of(row_total(offsets, counts, sig, NMSM_BUCKETS), target));
     const uint32_t lo = (uint32_t)((uint64_t)c * part / k), cnt = (uint32_t)((uint64_t)c * (part + 1) / k) - lo;     // equal parts
     const uint32_t *ent = entries + (entry_base ? (size_t)entry_base[sig] : sig * (size_t)NMSM_W * m.n) + offsets[sig * NMSM_BUCKETS + b] + lo;
     XyzzT<F> acc = pt_identity<F>();
@@ -1230,8 +1095,7 @@ __global__ __launch_bounds__(64, F::LANES > 1 ? 1 : 2) void nmsm_combine_kernel(
     const size_t slot = blockIdx.y, sig = slot % sigs;
     const uint32_t b = blockIdx.x, lane = threadIdx.x / F::LANES;
     const uint32_t c = counts[sig * NMSM_BUCKETS + b];
-    const uint32_t total = offsets[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1] + counts[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1], split = nmsm_split_of(total, target);
-    const uint32_t k = c <= split ? 1u : (c + split - 1) / split;
+    const uint32_t k = items_of(c, nmsm_split_of(row_total(offsets, counts, sig, NMSM_BUCKETS), target));
     const uint32_t *src = partial_items + (slot * (size_t)max_items + item_first[sig * NMSM_BUCKETS + b]) * (size_t)BW;
     XyzzT<F> acc = pt_identity<F>();
     for (uint32_t j = lane; j < k; j += PER) acc = pt_add(acc, load_bucket<F>(src + (size_t)j * BW));
@@ -1286,8 +1150,7 @@ __global__ __launch_bounds__(64) void nmsm_finish_kernel(const uint32_t *__restr
             mine[k] = 1;
         } else {
             const uint32_t c = counts[sig * NMSM_BUCKETS + b];
-            const uint32_t total = offsets[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1] + counts[sig * NMSM_BUCKETS + NMSM_BUCKETS - 1], split = nmsm_split_of(total, target);
-            mine[k] = c <= split ? 1u : (c + split - 1) / split;
+            mine[k] = items_of(c, nmsm_split_of(row_total(offsets, counts, sig, NMSM_BUCKETS), target));
             src[k] = partial_items + (slot * (size_t)max_items + item_first[sig * NMSM_BUCKETS + b]) * (size_t)BW;
             atomicMax(&longest[k], mine[k]);
         }
@@ -1578,11 +1441,14 @@ hipError_t msm_rows(const frw_msm *m, size_t rows, const uint32_t *sc, size_t st
     const dim3 sgrid((unsigned)slices, (unsigned)rows);
     hipError_t e = hipMemsetAsync(b.ones_count, 0, rows * 16, st);
     if (e != hipSuccess) return e;
+    // where the sort's digits come from: a bare handle's are stored once, window-major, and its grid rows read their own window's
+    const frw::DenseTableDigits from_scalars{sc, stride_words, montgomery, b.ones_count, b.ones_list, 0};
+    const frw::StoredDigits from_digits{(const int16_t *)b.digits};
     if (bare) {
         hipLaunchKernelGGL(frw::msm_digits_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, sc, montgomery, b.digits);
-        hipLaunchKernelGGL(frw::msm_hist_digits_kernel, sgrid, dim3(1024), 0, st, n, (const int16_t *)b.digits, slice_hist);
+        hipLaunchKernelGGL(frw::msm_sort_hist_kernel<frw::StoredDigits>, sgrid, dim3(1024), 0, st, n, from_digits, slice_hist);
     } else {
-        hipLaunchKernelGGL(frw::msm_hist_kernel, sgrid, dim3(1024), 0, st, n, sc, stride_words, montgomery, slice_hist, b.ones_count, b.ones_list, 0);
+        hipLaunchKernelGGL(frw::msm_sort_hist_kernel<frw::DenseTableDigits>, sgrid, dim3(1024), 0, st, n, from_scalars, slice_hist);
     }
     hipLaunchKernelGGL(frw::msm_slice_offsets_kernel, dim3(frw::MSM_BUCKETS / 256, (unsigned)rows), dim3(256), 0, st, slice_hist, b.counts, slices);
     hipLaunchKernelGGL(frw::msm_scan_kernel, dim3((unsigned)rows), dim3(1024), 0, st, b.counts, b.offsets);
@@ -1593,8 +1459,8 @@ hipError_t msm_rows(const frw_msm *m, size_t rows, const uint32_t *sc, size_t st
     const uint32_t finer = bare ? 1u : rows <= 2 ? (n > (1u << 18) ? 24u : 4u) : 1u;
     hipLaunchKernelGGL(frw::msm_order_kernel, dim3((unsigned)rows), dim3(1024), 0, st, b.counts, b.offsets, b.order, b.item_first, b.items, b.item_count, finer,
                        b.max_items);
-    if (bare) hipLaunchKernelGGL(frw::msm_scatter_digits_kernel, sgrid, dim3(1024), 0, st, n, (const int16_t *)b.digits, b.offsets, slice_hist, b.entries);
-    else hipLaunchKernelGGL(frw::msm_scatter_kernel, sgrid, dim3(1024), 0, st, n, sc, stride_words, montgomery, b.offsets, slice_hist, b.entries, 0);
+    if (bare) hipLaunchKernelGGL(frw::msm_sort_scatter_kernel<frw::StoredDigits>, sgrid, dim3(1024), 0, st, n, from_digits, b.offsets, slice_hist, b.entries);
+    else hipLaunchKernelGGL(frw::msm_sort_scatter_kernel<frw::DenseTableDigits>, sgrid, dim3(1024), 0, st, n, from_scalars, b.offsets, slice_hist, b.entries);
     hipLaunchKernelGGL((frw::msm_bucket_kernel<F, PREFETCH>), dim3(b.max_items / 64, (unsigned)rows), dim3(64), 0, st, m->dev, b.offsets,
                        b.counts, b.items, b.item_count, b.entries, b.partial_items, finer, b.max_items, b.ent_stride, (const unsigned long long *)nullptr);
     hipLaunchKernelGGL(frw::msm_combine_kernel<F>, dim3(frw::MSM_BUCKETS / 64, (unsigned)rows), dim3(64), 0, st, b.offsets, b.counts, b.item_first,
@@ -1709,11 +1575,11 @@ hipError_t nmsm_sort(const NmsmBufs &b, uint32_t n, size_t cnt, const uint32_t *
     hipError_t e = hipMemsetAsync(b.ones_count, 0, cnt * 4, st);
     if (e == hipSuccess && ones_as_mask) e = hipMemsetAsync(b.ones_list, 0, cnt * (size_t)n * 4, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(frw::nmsm_hist_kernel, sgrid, dim3(1024), 0, st, n, sc, stride_words, montgomery, b.slice_hist, b.ones_count, b.ones_list,
-                       ones_as_mask ? 1 : 0);
+    const frw::NarrowTableDigits from_scalars{sc, stride_words, montgomery, b.ones_count, b.ones_list, ones_as_mask ? 1 : 0};
+    hipLaunchKernelGGL(frw::msm_sort_hist_kernel<frw::NarrowTableDigits>, sgrid, dim3(1024), 0, st, n, from_scalars, b.slice_hist);
     hipLaunchKernelGGL(frw::nmsm_plan_kernel, dim3((unsigned)cnt), dim3(frw::NMSM_BUCKETS), 0, st, b.slice_hist, b.counts, b.offsets, b.item_first, b.items,
                        b.item_count, b.target, b.max_items, slices);
-    hipLaunchKernelGGL(frw::nmsm_scatter_kernel, sgrid, dim3(1024), 0, st, n, sc, stride_words, montgomery, b.offsets, b.slice_hist, b.entries);
+    hipLaunchKernelGGL(frw::msm_sort_scatter_kernel<frw::NarrowTableDigits>, sgrid, dim3(1024), 0, st, n, from_scalars, b.offsets, b.slice_hist, b.entries);
     return hipGetLastError();
 }
 // ... of ONE scalar vector for bare handles: all thirty-two windows in one pass (`b` from frw::nmsm_layout_bare)
@@ -1731,6 +1597,50 @@ hipError_t nmsm_sort_bare(const NmsmBufs &b, uint32_t n, const uint32_t *sc, int
                        index);
     return hipGetLastError();
 }
+// ---- what both forms of the narrow sums share ----
+// the tables of one launch side by side (NmsmTables); with_ones_tables: the sort left a mask of the ones, not a list
+frw::NmsmTables nmsm_tables(const frw_msm *const *ms, int tables, uint32_t n, uint32_t sigs, bool with_ones_tables)
+{
+    frw::NmsmTables dev;
+    dev.n = n; dev.sigs = sigs;
+    for (int t = 0; t < 3; t++) {
+        const frw_msm *m = ms[t < tables ? t : 0];
+        dev.table[t] = m->dev.table;
+        dev.ones_table[t] = with_ones_tables ? m->dev.ones_table : nullptr;
+    }
+    return dev;
+}
+// two lanes per point (G2): WITHOUT the prefetch of the next row the bucket kernel is 249 registers = two waves per SIMD; with it 256 + 26
+// AGPRs = one (round 4 ran it that way).  FRW_G2_PREFETCH in the environment brings the prefetch back (the A/B of profiles/r05_g2_*).
+bool g2_prefetch()
+{
+    static const bool v = std::getenv("FRW_G2_PREFETCH") != nullptr;
+    return v;
+}
+// the work items' sums of `rows` grid rows; entry_base: a bare handle's windows, else null
+template <class FB, bool PREFETCH>
+void nmsm_launch_bucket(const frw::NmsmTables &dev, unsigned rows, const NmsmBufs &sorted, uint32_t *partial_items, const unsigned long long *entry_base, hipStream_t st)
+{
+    const dim3 grid((sorted.max_items * FB::LANES + 63) / 64, rows);
+    if (PREFETCH || (FB::LANES > 1 && g2_prefetch()))
+        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, true>), grid, dim3(64), 0, st, dev, sorted.offsets, sorted.counts, sorted.items, sorted.item_count,
+                           sorted.entries, partial_items, sorted.target, sorted.max_items, entry_base);
+    else
+        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, false>), grid, dim3(64), 0, st, dev, sorted.offsets, sorted.counts, sorted.items, sorted.item_count,
+                           sorted.entries, partial_items, sorted.target, sorted.max_items, entry_base);
+}
+// The sums of the scalars that are one, `threads` threads for each of `rows` grid rows (row y reads the tables' row y row_step): one partial
+// sum per 64 threads, and more than 64 of those brought down to 64 by a second kernel.  Returns what the fold is to read.
+struct OnesSums { const uint32_t *sums; uint32_t groups, stride; };
+template <class FB>
+OnesSums nmsm_launch_ones(const frw::NmsmTables &dev, uint32_t threads, unsigned rows, uint32_t row_step, const NmsmBufs &sorted, const NmsmBufs &own, hipStream_t st)
+{
+    hipLaunchKernelGGL(frw::nmsm_ones_kernel<FB>, dim3(threads / 64, rows), dim3(64), 0, st, dev, sorted.ones_count, sorted.ones_list, own.partial_ones,
+                       own.ones_stride, row_step);
+    if (threads / 64 <= 64) return OnesSums{own.partial_ones, threads / 64, own.ones_stride};
+    hipLaunchKernelGGL(frw::nmsm_ones_fold_kernel<FB>, dim3(64, rows), dim3(64), 0, st, own.partial_ones, threads / 64, own.ones_stride, own.folded_ones);
+    return OnesSums{own.folded_ones, 64, 64};
+}
 // `sorted`: whose sort arrays to read; `own`: where the tables' partial sums go -- carved for `tables * cnt` signatures when there is
 // more than one table (the same carve as `sorted` for a sum on its own); d_out: [tables][cnt] results.  Every kernel here is a grid of
 // single wavefronts: none of them can be kept waiting by a kernel that fills the chip.
@@ -1744,43 +1654,18 @@ hipError_t nmsm_accumulate(const frw_msm *const *ms, int tables, const NmsmBufs 
 {
     if (!ones_elsewhere) ones_stream = st;                          // (a caller's stream may be the null stream: the flag says whether it was given)
     const uint32_t n = ms[0]->dev.n;
-    frw::NmsmTables dev;
-    dev.n = n; dev.sigs = (uint32_t)cnt;
-    for (int t = 0; t < 3; t++) {
-        const frw_msm *m = ms[t < tables ? t : 0];
-        dev.table[t] = m->dev.table;
-        dev.ones_table[t] = ones_as_mask ? m->dev.ones_table : nullptr;   // not as a mask: the sort left a list of the ones
-    }
+    const frw::NmsmTables dev = nmsm_tables(ms, tables, n, (uint32_t)cnt, ones_as_mask);
     const unsigned rows = (unsigned)(cnt * (size_t)tables);
     typedef typename frw::BulkPolicy<F>::type FB;
-    // two lanes per point (G2): WITHOUT the prefetch of the next row the bucket kernel is 249 registers = two waves per SIMD; with it 256 + 26
-    // AGPRs = one (round 4 ran it that way).  FRW_G2_PREFETCH in the environment brings the prefetch back (the A/B of profiles/r05_g2_*).
-    static const bool g2_prefetch = std::getenv("FRW_G2_PREFETCH") != nullptr;
     // the ones' partial sums: enough threads to occupy the chip (~2^16 over the batch), between 256 and 4,096 per signature
-    int ones_threads = 256;
-    while (ones_threads < (int)frw::nmsm_ones_max(n) && (size_t)ones_threads * rows < 65536) ones_threads <<= 1;
-    hipLaunchKernelGGL(frw::nmsm_ones_kernel<FB>, dim3((unsigned)ones_threads / 64, rows), dim3(64), 0, ones_stream, dev, sorted.ones_count, sorted.ones_list,
-                       own.partial_ones, own.ones_stride, 1u);
-    const uint32_t *ones_for_finish = own.partial_ones;
-    uint32_t ones_groups = (uint32_t)ones_threads / 64, ones_finish_stride = own.ones_stride;
-    if (ones_groups > 64) {
-        hipLaunchKernelGGL(frw::nmsm_ones_fold_kernel<FB>, dim3(64, rows), dim3(64), 0, ones_stream, own.partial_ones, ones_groups, own.ones_stride, own.folded_ones);
-        ones_for_finish = own.folded_ones;
-        ones_groups = 64;
-        ones_finish_stride = 64;
-    }
+    uint32_t ones_threads = 256;
+    while (ones_threads < frw::nmsm_ones_max(n) && (size_t)ones_threads * rows < 65536) ones_threads <<= 1;
+    const OnesSums ones = nmsm_launch_ones<FB>(dev, ones_threads, rows, 1u, sorted, own, ones_stream);
     if (ones_elsewhere) {
         const hipError_t e = hipEventRecord(ones_done, ones_stream);
         if (e != hipSuccess) return e;
     }
-    if (PREFETCH || (FB::LANES > 1 && g2_prefetch))
-        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, true>), dim3((sorted.max_items * FB::LANES + 63) / 64, rows), dim3(64), 0, st, dev,
-                           sorted.offsets, sorted.counts, sorted.items, sorted.item_count, sorted.entries, own.partial_items, sorted.target, sorted.max_items,
-                           (const unsigned long long *)nullptr);
-    else
-        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, false>), dim3((sorted.max_items * FB::LANES + 63) / 64, rows), dim3(64), 0, st, dev,
-                           sorted.offsets, sorted.counts, sorted.items, sorted.item_count, sorted.entries, own.partial_items, sorted.target, sorted.max_items,
-                           (const unsigned long long *)nullptr);
+    nmsm_launch_bucket<FB, PREFETCH>(dev, rows, sorted, own.partial_items, nullptr, st);
     // the items of a bucket: added up by a workgroup per bucket where latency counts (a lone proof: 12 ms -> 8.6), by the fold's own
     // thread where throughput does (the combine is nine times the wave-level additions: 3 % of a 64-proof call)
     const bool combine = cnt <= 16;
@@ -1792,7 +1677,7 @@ hipError_t nmsm_accumulate(const frw_msm *const *ms, int tables, const NmsmBufs 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(frw::nmsm_finish_kernel<FB>, dim3(rows), dim3(64), 0, st, sorted.counts, sorted.offsets, sorted.item_first, own.partial_items,
-                       combine ? own.bucket_sums : (uint32_t *)nullptr, ones_for_finish, (int)ones_groups, ones_finish_stride, sorted.target, sorted.max_items,
+                       combine ? own.bucket_sums : (uint32_t *)nullptr, ones.sums, (int)ones.groups, ones.stride, sorted.target, sorted.max_items,
                        d_out, xyzz_out ? 1 : 0, (uint32_t)cnt, 0);
     return hipGetLastError();
 }
@@ -1804,37 +1689,17 @@ hipError_t nmsm_accumulate(const frw_msm *const *ms, int tables, const NmsmBufs 
 template <class F, bool PREFETCH>
 hipError_t nmsm_accumulate_bare(const frw_msm *const *ms, int tables, const NmsmBufs &b, uint32_t *d_out, hipStream_t st, bool xyzz_out, uint32_t out_step = 1)
 {
-    const uint32_t n = b.n;                                          // (the sort's: the tables' rows, or those an index names)
-    frw::NmsmTables dev;
-    dev.n = n; dev.sigs = frw::NMSM_W;
-    for (int t = 0; t < 3; t++) {
-        dev.table[t] = ms[t < tables ? t : 0]->dev.table;
-        dev.ones_table[t] = nullptr;
-    }
+    // (b.n is the sort's: the tables' rows, or those an index names)
+    const frw::NmsmTables dev = nmsm_tables(ms, tables, b.n, frw::NMSM_W, false);
     const unsigned rows = (unsigned)tables * frw::NMSM_W;
     typedef typename frw::BulkPolicy<F>::type FB;
-    static const bool g2_prefetch = std::getenv("FRW_G2_PREFETCH") != nullptr;       // (see nmsm_accumulate)
-    const uint32_t ones_threads = frw::nmsm_ones_max(n);             // 4,096, or 65,536 beyond 2^18 points
-    hipLaunchKernelGGL(frw::nmsm_ones_kernel<FB>, dim3(ones_threads / 64, (unsigned)tables), dim3(64), 0, st, dev, b.ones_count, b.ones_list, b.partial_ones,
-                       b.ones_stride, (uint32_t)frw::NMSM_W);
-    const uint32_t *ones_for_finish = b.partial_ones;
-    uint32_t ones_groups = ones_threads / 64, ones_finish_stride = b.ones_stride;
-    if (ones_groups > 64) {
-        hipLaunchKernelGGL(frw::nmsm_ones_fold_kernel<FB>, dim3(64, (unsigned)tables), dim3(64), 0, st, b.partial_ones, ones_groups, b.ones_stride, b.folded_ones);
-        ones_for_finish = b.folded_ones;
-        ones_groups = 64;
-        ones_finish_stride = 64;
-    }
-    if (PREFETCH || (FB::LANES > 1 && g2_prefetch))
-        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, true>), dim3((b.max_items * FB::LANES + 63) / 64, rows), dim3(64), 0, st, dev,
-                           b.offsets, b.counts, b.items, b.item_count, b.entries, b.partial_items, b.target, b.max_items, (const unsigned long long *)b.entry_base);
-    else
-        hipLaunchKernelGGL((frw::nmsm_bucket_kernel<FB, false>), dim3((b.max_items * FB::LANES + 63) / 64, rows), dim3(64), 0, st, dev,
-                           b.offsets, b.counts, b.items, b.item_count, b.entries, b.partial_items, b.target, b.max_items, (const unsigned long long *)b.entry_base);
+    // the ones: 4,096 threads per table, or 65,536 beyond 2^18 points; grid row y is (table y, window 0), the only window with ones
+    const OnesSums ones = nmsm_launch_ones<FB>(dev, frw::nmsm_ones_max(b.n), (unsigned)tables, (uint32_t)frw::NMSM_W, b, b, st);
+    nmsm_launch_bucket<FB, PREFETCH>(dev, rows, b, b.partial_items, (const unsigned long long *)b.entry_base, st);
     hipLaunchKernelGGL(frw::nmsm_combine_kernel<FB>, dim3(frw::NMSM_BUCKETS, rows), dim3(64), 0, st, b.counts, b.offsets, b.item_first,
                        b.partial_items, b.bucket_sums, b.target, b.max_items, (uint32_t)frw::NMSM_W);
     hipLaunchKernelGGL(frw::nmsm_finish_kernel<FB>, dim3(rows), dim3(64), 0, st, b.counts, b.offsets, b.item_first, b.partial_items,
-                       b.bucket_sums, ones_for_finish, (int)ones_groups, ones_finish_stride, b.target, b.max_items,
+                       b.bucket_sums, ones.sums, (int)ones.groups, ones.stride, b.target, b.max_items,
                        b.window_sums, 1, (uint32_t)frw::NMSM_W, 1);
     hipLaunchKernelGGL(frw::msm_horner_kernel<FB>, dim3((unsigned)tables), dim3(64), 0, st, b.window_sums, frw::NMSM_W, frw::NMSM_C, d_out, xyzz_out ? 1 : 0,
                        out_step);
@@ -1931,21 +1796,25 @@ extern "C" int frw_msm_info(const frw_msm *m, frw_msm_info_t *out)
     return FRW_OK;
 }
 
+// the sums of one group's handle: PREFETCH is G1's (G2 has no registers to spare for the next row)
+template <class F, bool PREFETCH>
+static int msm_dev(int group, const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, int montgomery, uint64_t *d_out,
+                   void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (!m || m->group != group || (batch && (!d_scalars || !d_out || !d_workspace)) || scalar_stride < m->dev.n) return FRW_E_INVALID_ARG;
+    if (batch == 0) return FRW_OK;
+    if (m->window_bits == 8) return nmsm_run<F, PREFETCH>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return msm_run<F, PREFETCH>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" int frw_msm_g1_dev(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, int montgomery,
                               uint64_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (!m || m->group != 1 || (batch && (!d_scalars || !d_out || !d_workspace)) || scalar_stride < m->dev.n) return FRW_E_INVALID_ARG;
-    if (batch == 0) return FRW_OK;
-    if (m->window_bits == 8) return nmsm_run<FqField, true>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
-    return msm_run<FqField, true>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return msm_dev<FqField, true>(1, m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, stream);
 }
 extern "C" int frw_msm_g2_dev(const frw_msm *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, int montgomery,
                               uint64_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (!m || m->group != 2 || (batch && (!d_scalars || !d_out || !d_workspace)) || scalar_stride < m->dev.n) return FRW_E_INVALID_ARG;
-    if (batch == 0) return FRW_OK;
-    if (m->window_bits == 8) return nmsm_run<Fq2Field, false>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
-    return msm_run<Fq2Field, false>(m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return msm_dev<Fq2Field, false>(2, m, batch, d_scalars, scalar_stride, montgomery, d_out, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int frw_groth16_msm_h_dev(const frw_msm *m, size_t batch, const uint64_t *d_h, size_t domain_size, uint64_t *d_out,

@@ -239,7 +239,7 @@ def test_witness_map_on_the_other_domains(engine, oracle, tmp_path, logns):
 
 
 def _digits8(v):
-    """non-zero signed 8-bit digits of a scalar that is not one (frw_msm.hip scalar_digits8: a byte above 128 borrows from the next)"""
+    """non-zero signed 8-bit digits of a scalar that is not one (frw_digits.h signed_digits<8, 32>: a byte above 128 borrows from the next)"""
     cnt = carry = 0
     for j in range(32):
         d = ((v >> (8 * j)) & 0xff) + carry

@@ -127,6 +127,38 @@ def test_a_workspace_of_exactly_the_reported_size(engine, oracle, narrow, bare):
         engine.msm_free(handle)
 
 
+_TINY = {}
+
+
+def _tiny(oracle, n):
+    """n bases, four scalar vectors (random, all ones, all r - 1, all zero) and the oracle's sums, made once per n"""
+    if n not in _TINY:
+        rng = random.Random(4100 + n)
+        bases = oracle.g1_fixed_base(T.ints_to_limbs([rng.randrange(1, E.R) for _ in range(n)]))
+        vectors = [[rng.randrange(E.R) for _ in range(n)], [1] * n, [E.R - 1] * n, [0] * n]
+        canon = np.stack([T.ints_to_limbs(v) for v in vectors])
+        mont = np.stack([T.ints_to_limbs([x * FR_R % E.R for x in v]) for v in vectors])
+        want = [oracle.g1_msm(bases, T.ints_to_limbs(v), 5).tolist() for v in vectors]
+        _TINY[n] = (bases, canon, mont, want)
+    return _TINY[n]
+
+
+@pytest.mark.parametrize("n", [1, 5, 33])
+@pytest.mark.parametrize("narrow,bare", HANDLES, ids=HANDLE_IDS)
+def test_fewer_points_than_slices_of_the_sort(engine, oracle, narrow, bare, n):
+    """Every counting sort cuts the n scalars into 16 to 224 slices (the wide windows': rounded up to whole tiles of 4,096 and clamped): with
+    1, 5 and 33 points most slices are empty and begin past the end.  Calls of three signatures, canonical and Montgomery scalars."""
+    bases, canon, mont, want = _tiny(oracle, n)
+    handle = engine.msm_g1_load(bases, narrow=narrow, bare=bool(bare), wide=bare == "wide")
+    try:
+        assert want[3] == [0] * 12
+        for sc, montgomery in ((canon, 0), (mont, 1)):
+            for first in (0, 1):                                   # vectors 0 1 2, then 1 2 3
+                assert [g.tolist() for g in _run(engine, handle, sc[first:first + 3], montgomery)] == want[first:first + 3], (montgomery, first)
+    finally:
+        engine.msm_free(handle)
+
+
 def _h_query(oracle, n, toxic):
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_msm

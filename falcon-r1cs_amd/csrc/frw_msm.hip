@@ -33,6 +33,7 @@
 #include "frw_quad.h"
 #include "frw_fr29.h"
 #include "frw_digits.h"
+#include "frw_drbg.h"
 #include "frw_layout.h"
 #include "frw_rows.h"
 
@@ -2517,11 +2518,12 @@ namespace {
 // d_proofs: [batch][48] (a whole key), or d_partial: [batch][72] (a slice: the five partial sums, frw.h FRW_GROTH16_PARTIAL_WORDS).
 int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
                        const uint64_t *rs_host, const uint64_t *rs_dev, uint64_t *d_proofs, uint64_t *d_partial, uint32_t *d_num_unsatisfied,
-                       void *d_workspace, size_t workspace_bytes, void *stream)
+                       void *d_workspace, size_t workspace_bytes, void *stream, bool args_only = false)
 {
     const Groth16Parts parts = groth16_parts(pk, r1cs);
     const frw::Groth16BareBufs g = frw::groth16_layout_bare(d_workspace, parts.qap, parts.msm[0], parts.domain, parts.nv, parts.nz, parts.b_rows);     // (every statement's)
     if (workspace_bytes < g.bytes || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
+    if (args_only) return FRW_OK;
     uint64_t *const h = g.h, *const zext = g.zext, *const pB2 = g.pts.B2, *const d_rs = g.pts.rs, *const d_split = g.pts.split;
     uint32_t *const pA = g.pts.A, *const pH = g.pts.H, *const pSA = g.pts.SA, *const pRB1 = g.pts.RB1;      // [A | B1' | L] [H] [s A | r B1']
     const NmsmBufs &g1 = g.sides.g1, &gb = g.sides.gb, &g2 = g.sides.g2;
@@ -2598,10 +2600,11 @@ int groth16_prove_bare(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t ba
     }
     return FRW_OK;
 }
-// rs_host: the blinding factors in host memory (uploaded, and waited for: the array may be short-lived); rs_dev: in device memory
+// rs_host: the blinding factors in host memory (uploaded, and waited for: the array may be short-lived); rs_dev: in device memory;
+// args_only: the refusals alone, nothing enqueued (what frw_groth16_prove_seeded_dev asks before it draws)
 int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
                   const uint64_t *rs_host, const uint64_t *rs_dev, uint64_t *d_proofs, uint32_t *d_num_unsatisfied, void *d_workspace,
-                  size_t workspace_bytes, void *stream)
+                  size_t workspace_bytes, void *stream, bool args_only = false)
 {
     const uint64_t *rs = rs_host ? rs_host : rs_dev;
     if (!pk || !r1cs || (batch && (!d_witness || !d_instance || !rs || !d_proofs || !d_workspace))) return FRW_E_INVALID_ARG;
@@ -2610,11 +2613,13 @@ int groth16_prove(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, 
     if (frw_qap_info(r1cs, &q) != FRW_OK || q.domain_size != pk->domain_size || q.num_instance != pk->num_instance) return FRW_E_INVALID_ARG;
     if (pk->bare) {
         if (pk->world > 1) return FRW_E_INVALID_ARG;                        // a slice makes partial sums: frw_groth16_prove_partial_dev
-        return groth16_prove_bare(pk, r1cs, batch, d_witness, d_instance, rs_host, rs_dev, d_proofs, nullptr, d_num_unsatisfied, d_workspace, workspace_bytes, stream);
+        return groth16_prove_bare(pk, r1cs, batch, d_witness, d_instance, rs_host, rs_dev, d_proofs, nullptr, d_num_unsatisfied, d_workspace, workspace_bytes, stream,
+                                  args_only);
     }
     const Groth16Parts parts = groth16_parts(pk, r1cs);
     const size_t chunk = std::min<size_t>(workspace_bytes / frw::groth16_layout(nullptr, 1, parts.qap, parts.domain, parts.nv, parts.msm).bytes, 4096);
     if (chunk == 0 || ((uintptr_t)d_workspace & 255)) return FRW_E_INVALID_ARG;
+    if (args_only) return FRW_OK;
     const size_t I = (size_t)pk->num_instance, W = (size_t)pk->num_witness, nv = I + W, n = (size_t)pk->domain_size, stride = nv + 3;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(pk->device);
@@ -2728,6 +2733,23 @@ extern "C" int frw_groth16_prove_rs_dev(const frw_groth16_pk *pk, const frw_r1cs
 {
     if (!d_rs && batch) return FRW_E_INVALID_ARG;
     return groth16_prove(pk, r1cs, batch, d_witness, d_instance, nullptr, d_rs, d_proofs, d_num_unsatisfied, d_workspace, workspace_bytes, stream);
+}
+// The same with the blinding factors DRAWN on the device (frw_drbg.h): the refusals of the call above, ONE draw of 2 batch scalars into the
+// caller's d_rs, the call as it stands, the counter's step -- the draw and the step on `stream`.  A refused call has drawn nothing and
+// leaves the counter alone.
+extern "C" int frw_groth16_prove_seeded_dev(const frw_groth16_pk *pk, const frw_r1cs *r1cs, size_t batch, const uint64_t *d_witness,
+                                            const uint64_t *d_instance, const uint8_t *d_seed, uint64_t *d_counter, uint64_t *d_rs,
+                                            uint64_t *d_proofs, uint32_t *d_num_unsatisfied, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch == 0) return FRW_OK;
+    if (!d_seed || !d_counter || !d_rs) return FRW_E_INVALID_ARG;
+    int rc = groth16_prove(pk, r1cs, batch, d_witness, d_instance, nullptr, d_rs, d_proofs, d_num_unsatisfied, d_workspace, workspace_bytes, stream, true);
+    if (rc != FRW_OK) return rc;
+    const hipError_t e = hipSetDevice(pk->device);
+    if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
+    rc = frw::drbg::draw_launch(d_seed, d_counter, FRW_DRAW_BLINDING, 2 * batch, d_rs, stream);
+    if (rc == FRW_OK) rc = groth16_prove(pk, r1cs, batch, d_witness, d_instance, nullptr, d_rs, d_proofs, d_num_unsatisfied, d_workspace, workspace_bytes, stream);
+    return rc == FRW_OK ? frw::drbg::advance_launch(d_counter, stream) : rc;
 }
 
 // ---- a key in slices: the partial sums of one rank, and their combination ---------------------------------------------------------------

@@ -24,6 +24,7 @@
 
 #include "../../include/frw.h"
 #include "frw_device.h"
+#include "frw_drbg.h"
 #include "frw_layout.h"
 #include "frw_rerand.h"
 #include "frw_verify.h"
@@ -224,8 +225,9 @@ extern "C" size_t frw_groth16_rerandomize_workspace_bytes(const frw_groth16_vk *
     return frw::rerand_layout(nullptr, batch_in_flight, wire_mode != -1).bytes;
 }
 
-extern "C" int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint64_t *d_factors, int flags,
-                                           uint64_t *d_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
+// The two device calls; args_only: the refusals alone, nothing enqueued (what the seeded calls ask before they draw)
+static int rerandomize_limbs(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint64_t *d_factors, int flags, uint64_t *d_out,
+                             int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream, bool args_only)
 {
     if (batch == 0) return FRW_OK;
     if (!vk || !d_proofs || !d_factors || !d_out || !d_status || !d_workspace || ((uintptr_t)d_workspace & 15) ||
@@ -235,6 +237,7 @@ extern "C" int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batc
     if (!vk->d_delta) return FRW_E_INVALID_ARG;
     const size_t chunk = frw::proofs_in_flight(batch, workspace_bytes, [](size_t k) { return frw::rerand_layout(nullptr, k, false).bytes; });
     if (chunk == 0) return FRW_E_INVALID_ARG;
+    if (args_only) return FRW_OK;
     const hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
     const frw::RerandBufs b = frw::rerand_layout(d_workspace, chunk, false);
@@ -246,9 +249,14 @@ extern "C" int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batc
     return FRW_OK;
 }
 
-extern "C" int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint64_t *d_factors,
-                                                int flags, uint8_t *d_wire_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes,
-                                                void *stream)
+extern "C" int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint64_t *d_factors, int flags,
+                                           uint64_t *d_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return rerandomize_limbs(vk, batch, d_proofs, d_factors, flags, d_out, d_status, d_workspace, workspace_bytes, stream, false);
+}
+
+static int rerandomize_wire(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint64_t *d_factors, int flags,
+                            uint8_t *d_wire_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream, bool args_only)
 {
     if (batch == 0) return FRW_OK;
     if (!vk || !d_wire_in || !d_factors || !d_wire_out || !d_status || !d_workspace || ((uintptr_t)d_workspace & 15) || !mode_ok(mode) ||
@@ -258,6 +266,7 @@ extern "C" int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t
     if (!vk->d_delta) return FRW_E_INVALID_ARG;
     const size_t chunk = frw::proofs_in_flight(batch, workspace_bytes, [](size_t k) { return frw::rerand_layout(nullptr, k, true).bytes; });
     if (chunk == 0) return FRW_E_INVALID_ARG;
+    if (args_only) return FRW_OK;
     const hipError_t e = hipSetDevice(vk->device);
     if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
     const hipStream_t st = (hipStream_t)stream;
@@ -275,4 +284,45 @@ extern "C" int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t
         if (le != hipSuccess) return frw::record_hip_error(le, "frw_groth16_rerandomize_wire_dev");
     }
     return FRW_OK;
+}
+
+extern "C" int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint64_t *d_factors,
+                                                int flags, uint8_t *d_wire_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                                                void *stream)
+{
+    return rerandomize_wire(vk, batch, d_wire_in, mode, d_factors, flags, d_wire_out, d_status, d_workspace, workspace_bytes, stream, false);
+}
+
+// ---- the same with the factors drawn on the device (frw_drbg.h): the wrapped call's refusals, ONE draw of 2 batch scalars into the caller's
+// d_factors, the call as it stands, the counter's step -- all on `stream`.  A refused call has drawn nothing and leaves the counter alone.
+template <class Call> static int seeded(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_seed, uint64_t *d_counter, uint64_t *d_factors, void *stream,
+                                        Call call)
+{
+    if (batch == 0) return FRW_OK;
+    if (!d_seed || !d_counter) return FRW_E_INVALID_ARG;
+    int rc = call(true);
+    if (rc != FRW_OK) return rc;
+    const hipError_t e = hipSetDevice(vk->device);
+    if (e != hipSuccess) return frw::record_hip_error(e, "hipSetDevice");
+    rc = frw::drbg::draw_launch(d_seed, d_counter, FRW_DRAW_RERANDOMIZE, 2 * batch, d_factors, stream);
+    if (rc == FRW_OK) rc = call(false);
+    return rc == FRW_OK ? frw::drbg::advance_launch(d_counter, stream) : rc;
+}
+
+extern "C" int frw_groth16_rerandomize_seeded_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint8_t *d_seed,
+                                                  uint64_t *d_counter, uint64_t *d_factors, int flags, uint64_t *d_out, int32_t *d_status,
+                                                  void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return seeded(vk, batch, d_seed, d_counter, d_factors, stream, [&](bool args_only) {
+        return rerandomize_limbs(vk, batch, d_proofs, d_factors, flags, d_out, d_status, d_workspace, workspace_bytes, stream, args_only);
+    });
+}
+
+extern "C" int frw_groth16_rerandomize_wire_seeded_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint8_t *d_seed,
+                                                       uint64_t *d_counter, uint64_t *d_factors, int flags, uint8_t *d_wire_out, int32_t *d_status,
+                                                       void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return seeded(vk, batch, d_seed, d_counter, d_factors, stream, [&](bool args_only) {
+        return rerandomize_wire(vk, batch, d_wire_in, mode, d_factors, flags, d_wire_out, d_status, d_workspace, workspace_bytes, stream, args_only);
+    });
 }

@@ -281,6 +281,31 @@ VK_POINTS_ARE_CHECKED = 1
 KEY_AUTO, KEY_TABLES, KEY_BARE = 0, 1, 2           # frw.h FRW_KEY_*: window tables, or the points only (keys that would not fit)
 GROTH16_PARTIAL_WORDS = 72
 GROTH16_COMBINE_WORKSPACE = 4096
+DRAW_BLINDING, DRAW_RERANDOMIZE = 1, 2             # frw.h FRW_DRAW_*: the tags of (r, s) and of (r1, r2)
+
+
+def fr_draw(seed, counter, tag, count):
+    """`count` scalars of BLS12-381's Fr for (seed, counter, tag) on the host (frw_fr_draw): element j is the first 64 bytes of
+    SHAKE256("FRW-FR-DRAW-001" || tag || seed || le64(counter) || le64(j)) modulo the group order.  seed: 32 bytes; counter below
+    2^64; tag 0 .. 255 (DRAW_BLINDING, DRAW_RERANDOMIZE, or a caller's own).  Returns uint64[count, 4], canonical.  What fr_draw_dev
+    and the *_seeded_dev calls draw, bit for bit: the seed is a secret, and a (seed, counter) pair is used once."""
+    seed = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if seed.size != 32:
+        raise FrwError(-1, "frw_fr_draw", "seed: 32 bytes")
+    out = np.zeros((int(count), 4), dtype=np.uint64)
+    check(load_library().frw_fr_draw(_p(seed), C.c_uint64(int(counter)), int(tag), int(count), _p(out)), "frw_fr_draw")
+    return out
+
+
+def fr_draw_dev(d_seed, d_counter, tag, count, out=None, stream=0):
+    """fr_draw on the device of `d_seed` (frw_fr_draw_dev): d_seed a device uint8 tensor of 32 bytes, d_counter a device int64 tensor
+    of one element, read by the draw and then advanced by one (modulo 2^64).  Returns int64[count, 4] (`out`, or a fresh tensor),
+    ordered on `stream`; with `out` given the call allocates nothing and is capture-safe: every replay draws with the counter it finds."""
+    if out is None:
+        out = _empty((int(count), 4), "int64", d_seed.device)
+    check(load_library().frw_fr_draw_dev(d_seed.device.index or 0, _p(d_seed), _p(d_counter), int(tag), int(count), _p(out),
+                                         C.c_void_p(stream)), "frw_fr_draw_dev")
+    return out
 
 
 class Groth16Verifier:
@@ -467,6 +492,39 @@ class Groth16Verifier:
         check(self._lib.frw_groth16_rerandomize_wire_dev(self._h, batch, _p(d_wire), mode, _p(d_factors), int(flags), _p(out), _p(status),
                                                          _p(ws), ws_bytes, C.c_void_p(stream)), "frw_groth16_rerandomize_wire_dev")
         return out, status
+
+    def rerandomize_seeded_dev(self, d_proofs, d_seed, d_counter, d_factors=None, flags=0, out=None, stream=0, workspace=None):
+        """rerandomize_dev with the factors drawn on the device (frw_groth16_rerandomize_seeded_dev): one draw of 2 x batch scalars
+        for (d_seed, d_counter, DRAW_RERANDOMIZE) into d_factors (int64[batch, 2, 4]; None: a fresh tensor), the re-randomisation,
+        and the counter advanced by one.  Returns (proofs, status, d_factors).  Capture-safe when d_factors, out and workspace are
+        given: every replay is a fresh re-randomisation."""
+        batch = d_proofs.shape[0]
+        if d_factors is None:
+            d_factors = _empty((batch, 2, 4), "int64", d_proofs.device)
+        if out is None:
+            out = _empty((batch, 48), "int64", d_proofs.device)
+        status = _empty(batch, "int32", d_proofs.device)
+        ws, ws_bytes = _workspace(workspace, d_proofs.device, 16, self.rerandomize_workspace_bytes, batch)
+        check(self._lib.frw_groth16_rerandomize_seeded_dev(self._h, batch, _p(d_proofs), _p(d_seed), _p(d_counter), _p(d_factors), int(flags),
+                                                           _p(out), _p(status), _p(ws), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_rerandomize_seeded_dev")
+        return out, status, d_factors
+
+    def rerandomize_wire_seeded_dev(self, d_wire, d_seed, d_counter, d_factors=None, compressed=True, flags=0, out=None, stream=0, workspace=None):
+        """rerandomize_wire_dev with the factors drawn on the device (frw_groth16_rerandomize_wire_seeded_dev), as
+        rerandomize_seeded_dev.  Returns (bytes, status, d_factors)."""
+        mode = _wire_mode(compressed)
+        batch = _wire_batch(d_wire, compressed, "rerandomize_wire_seeded_dev")
+        if d_factors is None:
+            d_factors = _empty((batch, 2, 4), "int64", d_wire.device)
+        if out is None:
+            out = _empty((batch, proof_wire_bytes(compressed)), "uint8", d_wire.device)
+        status = _empty(batch, "int32", d_wire.device)
+        ws, ws_bytes = _workspace(workspace, d_wire.device, 16, self.rerandomize_workspace_bytes, batch, mode)
+        check(self._lib.frw_groth16_rerandomize_wire_seeded_dev(self._h, batch, _p(d_wire), mode, _p(d_seed), _p(d_counter), _p(d_factors),
+                                                                int(flags), _p(out), _p(status), _p(ws), ws_bytes, C.c_void_p(stream)),
+              "frw_groth16_rerandomize_wire_seeded_dev")
+        return out, status, d_factors
 
     def close(self):
         if self._h:
@@ -1383,6 +1441,15 @@ class WitnessEngine:
         """The same with the blinding factors in device memory (d_rs: int64[batch, 2, 4]): stream-ordered throughout, capturable."""
         check(self._lib.frw_groth16_prove_rs_dev(pk, r1cs, batch, _p(d_wit), _p(d_inst), _p(d_rs), _p(d_proofs), _p(d_num_unsatisfied),
                                                  _p(d_workspace), workspace_bytes, C.c_void_p(stream)), "frw_groth16_prove_rs_dev")
+
+    def groth16_prove_seeded_dev(self, pk, r1cs, batch, d_wit, d_inst, d_seed, d_counter, d_rs, d_proofs, d_workspace, workspace_bytes,
+                                 d_num_unsatisfied=None, stream=0):
+        """groth16_prove_rs_dev with the blinding factors drawn on the device (frw_groth16_prove_seeded_dev): one draw of 2 x batch
+        scalars for (d_seed uint8[32], d_counter int64[1], DRAW_BLINDING) into d_rs (int64[batch, 2, 4], the caller's: it holds what
+        was used), the proofs, and the counter advanced by one.  Capturable as groth16_prove_rs_dev is: every replay is a fresh proof."""
+        check(self._lib.frw_groth16_prove_seeded_dev(pk, r1cs, batch, _p(d_wit), _p(d_inst), _p(d_seed), _p(d_counter), _p(d_rs), _p(d_proofs),
+                                                     _p(d_num_unsatisfied), _p(d_workspace), workspace_bytes, C.c_void_p(stream)),
+              "frw_groth16_prove_seeded_dev")
 
     def qap_info(self, handle):
         """Domain of the QAP witness map for the loaded matrices: (log n, n, C, I, workspace bytes per signature)."""

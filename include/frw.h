@@ -633,7 +633,8 @@ int frw_groth16_prove_dev(const frw_groth16_pk *pk, const frw_r1cs *r, size_t ba
  * order; their split by the curve's endomorphism, done on the host for the call above until round 4, happens on the device for
  * both).  Nothing waits on the host: the call is ordered on `stream` throughout and MAY be captured into a HIP graph and replayed
  * (one capture = one chunk: give it the workspace of the whole batch; the key's streams join the capture through its events and
- * leave it before the call returns).  A replay reads the factors that are in d_rs THEN: refresh them between replays. */
+ * leave it before the call returns).  A replay reads the factors that are in d_rs THEN: refresh them between replays -- or capture
+ * frw_groth16_prove_seeded_dev (below, "drawing the factors on the device"), which draws them inside the graph. */
 int frw_groth16_prove_rs_dev(const frw_groth16_pk *pk, const frw_r1cs *r, size_t batch, const uint64_t *d_witness,
                              const uint64_t *d_instance, const uint64_t *d_rs, uint64_t *d_proofs, uint32_t *d_num_unsatisfied,
                              void *d_workspace, size_t workspace_bytes, void *stream);
@@ -871,7 +872,8 @@ int frw_diag_pairing_dev(int device, size_t count, const uint64_t *g1, const uin
  * A proof of the same statement that looks new: whoever holds (vk, proof) -- no signature, no witness, no proving key -- can present it
  * again, or forward it, without the 192 bytes being a stable identifier.  ark draws r1, r2 itself; here the CALLER supplies them, as with
  * the blinding factors of frw_groth16_prove_rs_dev: the new proof is unlinkable to the old one only if the pair is uniform, secret and
- * FRESH -- the same proof with the same pair gives the same bytes.
+ * FRESH -- the same proof with the same pair gives the same bytes.  frw_groth16_rerandomize_seeded_dev / _wire_seeded_dev (below, "drawing
+ * the factors on the device") draw the pair themselves, as ark does, from a seed and a counter in device memory.
  *     proofs      uint64_t[batch][48]: A | B | C as frw_groth16_prove_dev writes them.  Each of the three may be the point at infinity
  *                 (all zero): the formulas are defined for it, and so may each result be (written as all zero)
  *     factors     uint64_t[batch][2][4]: r1, r2 of every proof, ANY 256-bit values, taken modulo the group order r
@@ -909,6 +911,52 @@ int frw_groth16_rerandomize_dev(const frw_groth16_vk *vk, size_t batch, const ui
                                 uint64_t *d_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
 int frw_groth16_rerandomize_wire_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint64_t *d_factors,
                                      int flags, uint8_t *d_wire_out, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- drawing the factors on the device (frw_drbg.h, frw_drbg.hip): the calls of ark-groth16 0.3.0 that take an `rng` ------------------------
+ * create_random_proof draws (r, s) and rerandomize_proof draws (r1, r2); the calls above take them from the caller.  These derive them
+ * from a 32-byte SEED and a 64-bit COUNTER, one exactly specified function for host and device:
+ *     msg  = "FRW-FR-DRAW-001" (15 ASCII bytes) || tag (1 byte) || seed (32) || le64(counter) || le64(j)          64 bytes
+ *     x_j  = int_le(first 64 bytes of SHAKE256(msg)) mod r        r: BLS12-381's group order; canonical, four little-endian uint64_t
+ * for element j = 0 .. count - 1 of a call.  512 bits modulo r are within 2^-257 of uniform (256 bits "taken modulo r" are not: 2^256 is
+ * some 2.2 r, and some residues would be 1.5 times as likely as others); there is no rejection loop.  tag separates the uses:
+ * FRW_DRAW_BLINDING for (r, s), FRW_DRAW_RERANDOMIZE for (r1, r2), any value 0 .. 255 for a caller's own (else FRW_E_INVALID_ARG).
+ *     frw_fr_draw      HOST code, no device: out = uint64_t[count][4].  The reference for the device calls, bit for bit, and the way to
+ *                      audit or reproduce what a device call used.
+ *     frw_fr_draw_dev  the same for (d_seed, *d_counter) in device memory (d_seed: 32 bytes, any alignment; d_counter: one uint64_t) into
+ *                      d_out = uint64_t[count][4], then *d_counter += 1, modulo 2^64.  Two launches on `stream` ALONE -- one lane per
+ *                      scalar, then one thread that steps the counter once every lane has read it -- nothing allocated, copied or
+ *                      synchronised: capture-safe, no parallel branches, and a replayed graph draws with the counter it finds THEN.
+ * count = 0 (batch = 0 below) is a no-op that returns FRW_OK before anything else is looked at and does NOT advance the counter.  A null
+ * pointer -> FRW_E_INVALID_ARG; no device -> FRW_E_NO_DEVICE (no host fallback for the _dev forms).
+ * The three composed calls are ONE draw followed by the existing call, unchanged: frw_groth16_prove_seeded_dev is
+ * frw_groth16_prove_rs_dev, frw_groth16_rerandomize_seeded_dev / _wire_seeded_dev are frw_groth16_rerandomize_dev / _wire_dev, with
+ * 2 x batch scalars drawn into the CALLER'S d_rs / d_factors (uint64_t[batch][2][4]: slot i gets j = 2 i and j = 2 i + 1) under
+ * FRW_DRAW_BLINDING / FRW_DRAW_RERANDOMIZE -- the buffer stays the caller's, who can read back what was used.  Every other argument, the
+ * workspace and every result are the wrapped call's.  The wrapped call's refusals come FIRST, and a refused call draws nothing and
+ * leaves the counter alone; an accepted one advances it by exactly one, whatever the batch and however many chunks the workspace makes
+ * of it.  A zero factor (probability 2^-255) is FRW_RERAND_ZERO_FACTOR for its slot, as above.  Captured into a HIP graph, each replay
+ * gives fresh proofs with the host out of the loop (frw_groth16_prove_seeded_dev's capture is frw_groth16_prove_rs_dev's: one chunk).
+ * frw_pok_prove_from_bytes_dev, frw_aggregate_prove_from_bytes_dev and frw_groth16_prove_partial_dev have no seeded form: fill their d_rs /
+ * rs with frw_fr_draw_dev / frw_fr_draw first.  A key in SLICES needs the same factors on every rank: the same seed, counter and tag.
+ * What stays the caller's:
+ *   - the seed is SECRET and comes from the operating system's generator; whoever knows (seed, counter) knows every factor drawn from them
+ *   - a pair (seed, counter) must NEVER recur under one tag -- not after 2^64 calls, and not after a restart of the process: persist the
+ *     counter ahead of its use, or take a new seed on every start
+ *   - the draw's reduction and the factors' arithmetic behind it are NOT constant-time (the caveat of the re-randomisation section):
+ *     where an observer of timing is part of the threat, draw and call where that observer is not */
+#define FRW_DRAW_BLINDING     1   /* (r, s) of create_random_proof */
+#define FRW_DRAW_RERANDOMIZE  2   /* (r1, r2) of rerandomize_proof */
+int frw_fr_draw(const uint8_t seed[32], uint64_t counter, int tag, size_t count, uint64_t *out);
+int frw_fr_draw_dev(int device, const uint8_t *d_seed, uint64_t *d_counter, int tag, size_t count, uint64_t *d_out, void *stream);
+int frw_groth16_prove_seeded_dev(const frw_groth16_pk *pk, const frw_r1cs *r, size_t batch, const uint64_t *d_witness,
+                                 const uint64_t *d_instance, const uint8_t *d_seed, uint64_t *d_counter, uint64_t *d_rs,
+                                 uint64_t *d_proofs, uint32_t *d_num_unsatisfied, void *d_workspace, size_t workspace_bytes, void *stream);
+int frw_groth16_rerandomize_seeded_dev(const frw_groth16_vk *vk, size_t batch, const uint64_t *d_proofs, const uint8_t *d_seed,
+                                       uint64_t *d_counter, uint64_t *d_factors, int flags, uint64_t *d_out, int32_t *d_status,
+                                       void *d_workspace, size_t workspace_bytes, void *stream);
+int frw_groth16_rerandomize_wire_seeded_dev(const frw_groth16_vk *vk, size_t batch, const uint8_t *d_wire_in, int mode, const uint8_t *d_seed,
+                                            uint64_t *d_counter, uint64_t *d_factors, int flags, uint8_t *d_wire_out, int32_t *d_status,
+                                            void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- input preparation (what the reference does with falcon-rust before any gadget runs) ---------------------
  * falcon_ntt.rs:27-28,44: sig_poly = Polynomial::from(&sig), pk_poly = Polynomial::from(&pk),

@@ -154,6 +154,8 @@ pub const FRW_VERIFY_BATCHED: c_int = 2;
 pub const FRW_WIRE_COMPRESSED: c_int = 0;
 pub const FRW_WIRE_UNCOMPRESSED: c_int = 1;
 pub const FRW_RERAND_ZERO_FACTOR: c_int = -2;
+pub const FRW_DRAW_BLINDING: c_int = 1;
+pub const FRW_DRAW_RERANDOMIZE: c_int = 2;
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct frw_groth16_pk_desc_t {
@@ -383,6 +385,22 @@ extern "C" {
     pub fn frw_groth16_rerandomize_wire_dev(vk: *const frw_groth16_vk, batch: usize, d_wire_in: *const u8, mode: c_int, d_factors: *const u64,
                                             flags: c_int, d_wire_out: *mut u8, d_status: *mut i32, d_workspace: *mut c_void,
                                             workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    // drawing the factors on the device (frw.h: seed secret, (seed, counter) never reused)
+    pub fn frw_fr_draw(seed: *const u8, counter: u64, tag: c_int, count: usize, out: *mut u64) -> c_int;
+    pub fn frw_fr_draw_dev(device: c_int, d_seed: *const u8, d_counter: *mut u64, tag: c_int, count: usize, d_out: *mut u64,
+                           stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_prove_seeded_dev(pk: *const frw_groth16_pk, r: *const frw_r1cs, batch: usize, d_witness: *const u64,
+                                        d_instance: *const u64, d_seed: *const u8, d_counter: *mut u64, d_rs: *mut u64,
+                                        d_proofs: *mut u64, d_num_unsatisfied: *mut u32, d_workspace: *mut c_void,
+                                        workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_rerandomize_seeded_dev(vk: *const frw_groth16_vk, batch: usize, d_proofs: *const u64, d_seed: *const u8,
+                                              d_counter: *mut u64, d_factors: *mut u64, flags: c_int, d_out: *mut u64,
+                                              d_status: *mut i32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                              stream: *mut c_void) -> c_int;
+    pub fn frw_groth16_rerandomize_wire_seeded_dev(vk: *const frw_groth16_vk, batch: usize, d_wire_in: *const u8, mode: c_int,
+                                                   d_seed: *const u8, d_counter: *mut u64, d_factors: *mut u64, flags: c_int,
+                                                   d_wire_out: *mut u8, d_status: *mut i32, d_workspace: *mut c_void,
+                                                   workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_diag_pairing_dev(device: c_int, count: usize, g1: *const u64, g2: *const u64, out: *mut u64) -> c_int;
     pub fn frw_hash_to_point_dev(ctx: *mut frw_ctx, logn: c_int, batch: usize, d_nonces: *const u8, d_msgs: *const u8,
                                  d_msg_off: *const u64, d_hm: *mut u16, stream: *mut c_void) -> c_int;

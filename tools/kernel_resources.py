@@ -17,7 +17,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "falcon-r1cs_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FILES = ("frw_kernels.hip", "frw_prepare.hip", "frw_r1cs_check.hip", "frw_qap.hip", "frw_qap_small.hip", "frw_setup.hip", "frw_msm.hip")
+FILES = ("frw_kernels.hip", "frw_prepare.hip", "frw_r1cs_check.hip", "frw_qap.hip", "frw_qap_small.hip", "frw_setup.hip", "frw_msm.hip", "frw_drbg.hip")
 
 # (probe source, [(explicit instantiation, scratch allowed, waves per SIMD at least)])
 QAP_PASSES = [("PASS_FIRST", 6, "LOAD_PLAIN", "STORE_FACTOR"), ("PASS_FIRST", 6, "LOAD_PRODUCTS_AB", "STORE_FACTOR"),

@@ -84,6 +84,11 @@ class R1csInfoStruct(C.Structure):
                 ("log_domain_size", C.c_int32), ("witness_map_on_device", C.c_int32)]
 
 
+class R1csfInfoStruct(C.Structure):
+    _fields_ = [("modulus", C.c_uint64 * 4), ("num_instance", C.c_uint64), ("num_witness", C.c_uint64), ("num_constraints", C.c_uint64),
+                ("nnz", C.c_uint64 * 3), ("scratch_bytes_per_statement", C.c_uint64 * 2)]
+
+
 class QapInfoStruct(C.Structure):
     _fields_ = [("log_domain_size", C.c_int32), ("domain_size", C.c_uint64), ("num_constraints", C.c_uint64),
                 ("num_instance", C.c_uint64), ("workspace_bytes_per_signature", C.c_uint64)]
@@ -214,6 +219,16 @@ PROTOTYPES = {
     "frw_r1cs_load_csr": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "frw_r1cs_load_file": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_free": (None, [C.c_void_p]),
+    "frw_r1cs_export_field": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p]),
+    "frw_r1csf_load": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "frw_r1csf_load_csr": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "frw_r1csf_load_file": (C.c_int, [C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "frw_r1csf_free": (None, [C.c_void_p]),
+    "frw_r1csf_info": (C.c_int, [C.c_void_p, C.POINTER(R1csfInfoStruct)]),
+    "frw_r1csf_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int]),
+    "frw_r1csf_check_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
     "frw_r1cs_load_aggregate": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_info": (C.c_int, [C.c_void_p, C.POINTER(R1csInfoStruct)]),
     "frw_aggregate_assign_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

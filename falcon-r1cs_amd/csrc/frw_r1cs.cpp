@@ -23,6 +23,7 @@
 #include "frw_arena.h"
 #include "frw_device.h"
 #include "frw_r1cs_file.h"
+#include "frw_r1cs_field.h"
 #include "frw_stage.h"
 #include "host/frw_host.hpp"
 
@@ -40,6 +41,8 @@ frw::host::ConstraintMatrices build_matrices(int circuit, int logn)
     return cs->to_matrices();
 }
 }  // namespace
+
+frw::host::ConstraintMatrices frw::r1cs_build_matrices(int circuit, int logn) { return build_matrices(circuit, logn); }
 
 // Device-resident matrices for frw_r1cs_check_dev
 struct frw_r1cs {

@@ -246,6 +246,36 @@ def _limbs4(x):
     return (C.c_uint64 * 4)(*[(int(x) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)])
 
 
+def _modulus(p, where):
+    """A modulus as the four limbs the C ABI takes; one that does not fit them is refused here, as field_info refuses it."""
+    if p < 0 or p >> 256:
+        raise FrwError(-1, where, "the modulus does not fit four limbs")
+    return _limbs4(p)
+
+
+def _csr_arrays(num_instance, num_witness, matrices):
+    """A, B, C as three (row_ptr, col, val) -> the counts, the three pointer arrays frw_r1cs_load_csr / frw_r1csf_load_csr take, and the
+    numpy arrays those point into (the caller holds them for the duration of the call)."""
+    if len(matrices) != 3:
+        raise ValueError("three matrices: A, B, C")
+    ptr = [np.ascontiguousarray(m[0], dtype=np.uint64) for m in matrices]
+    col = [np.ascontiguousarray(m[1], dtype=np.uint32) for m in matrices]
+    val = [np.ascontiguousarray(m[2], dtype=np.uint64).reshape(-1, 4) for m in matrices]
+    if any(len(c) != len(v) for c, v in zip(col, val)) or any(len(p) != len(ptr[0]) or len(p) == 0 for p in ptr):
+        raise ValueError("col and val of a matrix have one entry per term; the three row_ptr have C + 1 entries")
+    counts = (C.c_uint64 * 6)(num_instance, num_witness, len(ptr[0]) - 1, len(col[0]), len(col[1]), len(col[2]))
+    three = [(C.c_void_p * 3)(*map(_p, arrs)) for arrs in (ptr, col, val)]
+    return counts, three, (ptr, col, val)
+
+
+def r1cs_export_field(circuit, logn, p, path):
+    """frw_r1cs_export_field (no device): the circuit's matrices over the modulus p as an FRWR1CS1 file -> the six header counts."""
+    counts = (C.c_uint64 * 6)()
+    check(load_library().frw_r1cs_export_field(int(circuit), int(logn), _modulus(p, "frw_r1cs_export_field"), os.fsencode(str(path)), counts),
+          "frw_r1cs_export_field")
+    return list(counts)
+
+
 def field_info(p) -> FieldInfo:
     """frw_field_info: the Montgomery constants of an odd modulus 2^160 < p < 2^255 (no device needed)."""
     if p < 0 or p >> 256:
@@ -881,15 +911,7 @@ class WitnessEngine:
         """A handle for ANY constraint system: matrices = three (row_ptr uint64[C + 1], col uint32[nnz], val uint64[nnz][4] canonical)
         for A, B, C -- the arrays of the FRWR1CS1 file (column 0 the constant one, 1 .. I - 1 the public inputs, I + k witness k).  The
         handle goes wherever an r1cs_load handle goes but into the calls that start from Falcon signatures; free with r1cs_free."""
-        if len(matrices) != 3:
-            raise ValueError("three matrices: A, B, C")
-        ptr = [np.ascontiguousarray(m[0], dtype=np.uint64) for m in matrices]
-        col = [np.ascontiguousarray(m[1], dtype=np.uint32) for m in matrices]
-        val = [np.ascontiguousarray(m[2], dtype=np.uint64).reshape(-1, 4) for m in matrices]
-        if any(len(c) != len(v) for c, v in zip(col, val)) or any(len(p) != len(ptr[0]) or len(p) == 0 for p in ptr):
-            raise ValueError("col and val of a matrix have one entry per term; the three row_ptr have C + 1 entries")
-        counts = (C.c_uint64 * 6)(num_instance, num_witness, len(ptr[0]) - 1, len(col[0]), len(col[1]), len(col[2]))
-        three = [(C.c_void_p * 3)(*map(_p, arrs)) for arrs in (ptr, col, val)]
+        counts, three, _arrays = _csr_arrays(num_instance, num_witness, matrices)
         h = C.c_void_p()
         check(self._lib.frw_r1cs_load_csr(self.device, counts, *three, C.byref(h)), "frw_r1cs_load_csr")
         return h
@@ -902,6 +924,47 @@ class WitnessEngine:
 
     def r1cs_free(self, handle):
         self._lib.frw_r1cs_free(handle)
+
+    # ---- the check and the products over any four-limb field (frw_r1csf_*): a handle made for a modulus ----
+    def r1csf_load(self, circuit, logn, p):
+        """The matrices of circuit 0 / 1 / 2 carried over to the modulus p (their centred lift, reduced), on the device; free with
+        r1csf_free.  The handle goes into r1csf_check_dev only."""
+        h = C.c_void_p()
+        check(self._lib.frw_r1csf_load(self.device, circuit, logn, _modulus(p, "frw_r1csf_load"), C.byref(h)), "frw_r1csf_load")
+        return h
+
+    def r1csf_load_csr(self, p, num_instance, num_witness, matrices):
+        """r1cs_load_csr over the modulus p: the values canonical mod p."""
+        counts, three, _arrays = _csr_arrays(num_instance, num_witness, matrices)
+        h = C.c_void_p()
+        check(self._lib.frw_r1csf_load_csr(self.device, _modulus(p, "frw_r1csf_load_csr"), counts, *three, C.byref(h)), "frw_r1csf_load_csr")
+        return h
+
+    def r1csf_load_file(self, p, path):
+        """The same from an FRWR1CS1 file (what r1cs_export_field writes; the file does not record the modulus)."""
+        h = C.c_void_p()
+        check(self._lib.frw_r1csf_load_file(self.device, _modulus(p, "frw_r1csf_load_file"), os.fsencode(str(path)), C.byref(h)),
+              "frw_r1csf_load_file")
+        return h
+
+    def r1csf_free(self, handle):
+        self._lib.frw_r1csf_free(handle)
+
+    def r1csf_info(self, handle):
+        from ._lib import R1csfInfoStruct
+        q = R1csfInfoStruct()
+        check(self._lib.frw_r1csf_info(handle, C.byref(q)), "frw_r1csf_info")
+        return q
+
+    def r1csf_scratch_bytes(self, handle, batch, with_products):
+        return int(self._lib.frw_r1csf_scratch_bytes(handle, batch, 1 if with_products else 0))
+
+    def r1csf_check_dev(self, handle, batch, d_wit, d_inst, d_num_unsatisfied, d_first_unsatisfied=None, d_abc=None, d_scratch=None,
+                        scratch_bytes=0, stream=0):
+        """is_satisfied() / which_is_unsatisfied() of every statement over the handle's field, and (d_abc: int64[batch, 3, C, 4]) A z, B z,
+        C z in Montgomery form over it.  Allocates nothing: d_scratch holds r1csf_scratch_bytes(handle, batch, d_abc is not None)."""
+        check(self._lib.frw_r1csf_check_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_num_unsatisfied), _p(d_first_unsatisfied), _p(d_abc),
+                                            _p(d_scratch), scratch_bytes, C.c_void_p(stream)), "frw_r1csf_check_dev")
 
     def r1cs_load_aggregate(self, logns):
         """The constraint system of an aggregate statement: FalconNTTVerificationCircuit once per entry of `logns` (9 / 10, in

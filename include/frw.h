@@ -28,9 +28,9 @@
  *     what arkworks keeps in witness_assignment; FRW_ENC_CANONICAL stores x itself.  The reference is generic
  *     over F: PrimeField; every witness value is an integer below 2^160, so FRW_ENC_CANONICAL and FRW_ENC_COMPACT
  *     are field-agnostic, and a field encoding (FRW_ENC_FIELD_BASE + i, frw_ctx_field_encoding) stores x*2^256 mod p
- *     for any odd p with 2^160 < p < 2^255 in the witness, ntt, gadget and statement calls.  Everything downstream
- *     that takes buffers rather than an encoding -- the R1CS check, the QAP map, the MSMs, proving and verifying --
- *     is BLS12-381 only.
+ *     for any odd p with 2^160 < p < 2^255 in the witness, ntt, gadget and statement calls.  The R1CS satisfaction check
+ *     and the products A z, B z, C z follow the field too (frw_r1csf_*, a handle made for a modulus).  What stays
+ *     BLS12-381 only is everything after them: the QAP map, the MSMs, proving, verifying and the aggregates.
  *   - witness:  uint64_t[batch][W][4] in arkworks allocation order (layout: frw_layout()).
  *     instance: uint64_t[batch][I][4], I = 2N+1: [1, pk_ntt[0..N), hm_ntt[0..N)]
  *     (falcon_ntt.rs:63,67; public-input order as in examples/pok_sig.rs:38-45).
@@ -352,6 +352,56 @@ int frw_r1cs_eval_scratch_dev(const frw_r1cs *r, size_t batch, const uint64_t *d
 int frw_r1cs_load_csr(int device, const uint64_t counts[6], const uint64_t *const row_ptr[3], const uint32_t *const col[3],
                       const uint64_t *const val[3], frw_r1cs **out);
 int frw_r1cs_load_file(int device, const char *path, frw_r1cs **out);
+
+/* ---- the check and the products over ANY four-limb field: a handle made for a modulus given at run time ---------------------
+ * The reference's circuits are `impl<F: PrimeField> ConstraintSynthesizer<F>`; a field encoding (frw_ctx_field_encoding) makes the
+ * witness over any odd p with 2^160 < p < 2^255, and these calls say whether it satisfies the circuit -- cs.is_satisfied() and
+ * which_is_unsatisfied() over that field -- and give A z, B z, C z, the three vectors a foreign-field prover's witness_map starts
+ * from.  The modulus follows frw_field_info's rule (anything else: FRW_E_INVALID_ARG); BLS12-381's own group order is admissible.
+ * A `frw_r1csf *` goes into these calls only: the QAP map, the keys and the provers take a `frw_r1cs *`, BLS12-381.
+ *
+ * frw_r1cs_export_field / frw_r1csf_load: the matrices the host mirror emits (frw_r1cs_export), carried over to p.  Every
+ * coefficient of the three Falcon circuits is an integer (+-1, powers of two, +-q, twiddle products, ladder offsets -- the inverses
+ * of the dual and schoolbook circuits are witness values), so the matrices over p are the centred lift of the matrices over the group
+ * order r (v > r / 2 ? v - r : v) reduced mod p.  A coefficient whose lift reaches 2^200 (the largest a circuit holds is 160 bits)
+ * breaks that premise: FRW_E_INVALID_ARG, frw_last_error() naming the matrix and the row.  The file is the FRWR1CS1 layout with values
+ * canonical mod `modulus`; it does not record the modulus.  `circuit` is any of FRW_CIRCUIT_*.
+ * frw_r1csf_load_csr / frw_r1csf_load_file: matrices that come from anywhere, canonical mod `modulus`; accepted and refused as
+ * frw_r1cs_load_csr lists above, "a value >= the group order" reading "a value >= modulus".  Validation comes first, then the device:
+ * without a GPU a malformed system is FRW_E_INVALID_ARG and a well-formed one FRW_E_NO_DEVICE.
+ *
+ * frw_r1csf_check_dev: d_witness uint64_t[batch][W][4] and d_instance uint64_t[batch][I][4] in ark-ff's bytes over that modulus
+ * (x 2^256 mod p: what a field encoding writes, what Fp256<P> holds), every element canonical (limbs < p; an element >= p gives an
+ * unspecified count, the call stays memory-safe).
+ *     d_num_unsatisfied[i]    the rows statement i violates
+ *     d_first_unsatisfied[i]  optional: the lowest violated row, 0xffffffff if none (ark's which_is_unsatisfied, as an index)
+ *     d_abc                   optional: uint64_t[batch][3][C][4] = A z, B z, C z, Montgomery form over p, rows in constraint order
+ *                             (the layout of frw_r1cs_eval_dev); NULL: check only
+ * A statement whose instance[0] is not 2^256 mod p -- a refused, zero-filled slot of the witness calls; a buffer in another
+ * encoding -- is reported with num = C, first = 0 and zeros in its d_abc slot, and none of its rows is evaluated: a zero assignment
+ * satisfies a system whose constant is read from it, and must not pass as "0 violated rows".
+ * d_scratch: at least frw_r1csf_scratch_bytes(r, batch, d_abc != NULL) bytes, 16-byte aligned; may be NULL where that is 0 (a system
+ * without rows of 64 terms or more).  It holds the plain values of the variables the long rows read and, check only, those rows' products.
+ * Nothing is allocated and nothing synchronises: everything is ordered on `stream` alone, one kernel after the other, so the call
+ * may be captured and the captured graph has no parallel branches.  batch = 0 returns FRW_OK before anything else is looked at. */
+typedef struct frw_r1csf frw_r1csf;
+typedef struct {
+    uint64_t modulus[4];
+    uint64_t num_instance, num_witness, num_constraints, nnz[3];
+    uint64_t scratch_bytes_per_statement[2];  /* check only, with products */
+} frw_r1csf_info_t;
+int frw_r1cs_export_field(int circuit, int logn, const uint64_t modulus[4], const char *path, uint64_t *counts);
+int frw_r1csf_load(int device, int circuit, int logn, const uint64_t modulus[4], frw_r1csf **out);
+int frw_r1csf_load_csr(int device, const uint64_t modulus[4], const uint64_t counts[6],
+                       const uint64_t *const row_ptr[3], const uint32_t *const col[3],
+                       const uint64_t *const val[3], frw_r1csf **out);
+int frw_r1csf_load_file(int device, const uint64_t modulus[4], const char *path, frw_r1csf **out);
+void frw_r1csf_free(frw_r1csf *r);
+int frw_r1csf_info(const frw_r1csf *r, frw_r1csf_info_t *out);
+size_t frw_r1csf_scratch_bytes(const frw_r1csf *r, size_t batch, int with_products);
+int frw_r1csf_check_dev(const frw_r1csf *r, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
+                        uint32_t *d_num_unsatisfied, uint32_t *d_first_unsatisfied /* may be NULL */,
+                        uint64_t *d_abc /* may be NULL: check only */, void *d_scratch, size_t scratch_bytes, void *stream);
 
 /* ---- QAP witness map (the step after the hot path in a Groth16 prover) ------------------------------------------
  * examples/pok_sig.rs:30-47 hands the circuit to Groth16::<Bls12_381>::prove; after generate_constraints the prover's

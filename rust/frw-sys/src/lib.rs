@@ -121,6 +121,17 @@ pub struct frw_r1cs_info_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct frw_r1csf_info_t {
+    pub modulus: [u64; 4],
+    pub num_instance: u64,
+    pub num_witness: u64,
+    pub num_constraints: u64,
+    pub nnz: [u64; 3],
+    pub scratch_bytes_per_statement: [u64; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct frw_qap_info_t {
     pub log_domain_size: i32,
     pub domain_size: u64,
@@ -135,6 +146,10 @@ pub struct frw_ctx {
 }
 #[repr(C)]
 pub struct frw_r1cs {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct frw_r1csf {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -268,6 +283,17 @@ extern "C" {
     pub fn frw_r1cs_load_csr(device: c_int, counts: *const u64, row_ptr: *const *const u64, col: *const *const u32, val: *const *const u64, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_load_file(device: c_int, path: *const c_char, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_free(r: *mut frw_r1cs);
+    pub fn frw_r1cs_export_field(circuit: c_int, logn: c_int, modulus: *const u64, path: *const c_char, counts: *mut u64) -> c_int;
+    pub fn frw_r1csf_load(device: c_int, circuit: c_int, logn: c_int, modulus: *const u64, out: *mut *mut frw_r1csf) -> c_int;
+    pub fn frw_r1csf_load_csr(device: c_int, modulus: *const u64, counts: *const u64, row_ptr: *const *const u64, col: *const *const u32,
+                              val: *const *const u64, out: *mut *mut frw_r1csf) -> c_int;
+    pub fn frw_r1csf_load_file(device: c_int, modulus: *const u64, path: *const c_char, out: *mut *mut frw_r1csf) -> c_int;
+    pub fn frw_r1csf_free(r: *mut frw_r1csf);
+    pub fn frw_r1csf_info(r: *const frw_r1csf, out: *mut frw_r1csf_info_t) -> c_int;
+    pub fn frw_r1csf_scratch_bytes(r: *const frw_r1csf, batch: usize, with_products: c_int) -> usize;
+    pub fn frw_r1csf_check_dev(r: *const frw_r1csf, batch: usize, d_witness: *const u64, d_instance: *const u64,
+                               d_num_unsatisfied: *mut u32, d_first_unsatisfied: *mut u32, d_abc: *mut u64, d_scratch: *mut c_void,
+                               scratch_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_r1cs_load_aggregate(device: c_int, count: usize, logn: *const i32, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_info(r: *const frw_r1cs, out: *mut frw_r1cs_info_t) -> c_int;
     pub fn frw_aggregate_assign_dev(aggregate: *const frw_r1cs, d_witness_512: *const u64, d_instance_512: *const u64,

@@ -17,7 +17,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "falcon-r1cs_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FILES = ("frw_kernels.hip", "frw_prepare.hip", "frw_r1cs_check.hip", "frw_qap.hip", "frw_qap_small.hip", "frw_setup.hip", "frw_msm.hip", "frw_drbg.hip")
+FILES = ("frw_kernels.hip", "frw_prepare.hip", "frw_r1cs_check.hip", "frw_r1cs_field.hip", "frw_qap.hip", "frw_qap_small.hip", "frw_setup.hip", "frw_msm.hip", "frw_drbg.hip")
 
 # (probe source, [(explicit instantiation, scratch allowed, waves per SIMD at least)])
 QAP_PASSES = [("PASS_FIRST", 6, "LOAD_PLAIN", "STORE_FACTOR"), ("PASS_FIRST", 6, "LOAD_PRODUCTS_AB", "STORE_FACTOR"),
@@ -38,7 +38,11 @@ HOT_WHOLE = {"frw_kernels.hip": {"frw::witness_ntt_verify_kernel<10, 1>": (0, 1)
                                  "frw::ntt_modq_kernel<9, 1>": (0, 1)},
              # (the flattened rows' kernel wants 131 registers and is written for FOUR waves per SIMD, 128 each: three of them live in scratch
              # memory -- a latency-bound kernel, the fourth wave is worth more than the twelve bytes; more than that is a regression)
-             "frw_r1cs_check.hip": {"frw::r1cs_eval_flat_kernel<true>": (12, 4), "frw::r1cs_long_rows_small_kernel": (0, 2)}}
+             "frw_r1cs_check.hip": {"frw::r1cs_eval_flat_kernel<true>": (12, 4), "frw::r1cs_long_rows_small_kernel": (0, 2)},
+             # the check over a run-time modulus: eight CIOS rounds with the modulus in scalar registers, no scratch; the long rows' kernel
+             # holds four ten-limb sums and a field product (130 VGPRs: three waves per SIMD)
+             "frw_r1cs_field.hip": {"frw::r1csf_eval_kernel<true>": (0, 4), "frw::r1csf_eval_kernel<false>": (0, 4),
+                                    "frw::r1csf_long_rows_kernel": (0, 3), "frw::r1csf_zsmall_kernel": (0, 8), "frw::r1csf_init_kernel": (0, 8)}}
 
 FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
           ("LDS Size [bytes/block]", "lds"))

@@ -55,6 +55,13 @@ ASAN_OPTIONS=detect_leaks=0 /tmp/frw_rerand_host_asan | tail -1
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" \
     -o /tmp/frw_stage_host_asan "$ROOT/tests/cpp/test_stage_host.cpp" -L"$ROOT/falcon-r1cs_amd" -lfrw -Wl,-rpath,"$ROOT/falcon-r1cs_amd"
 ASAN_OPTIONS=detect_leaks=0 /tmp/frw_stage_host_asan | tail -1
+# the host side of a constraint system over a run-time modulus (frw_r1cs_field.h: the Montgomery arithmetic, the centred lift and its
+# 2^200 guard, the parser) against 256-bit arithmetic the program carries itself: a program of its own
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -Werror -Wno-unknown-pragmas \
+    -I "$ROOT/tests/cpp/hip_host" -I "$ROOT/falcon-r1cs_amd/csrc" -o /tmp/frw_r1cs_field_host_asan "$ROOT/tests/cpp/test_r1cs_field_host.cpp"
+R1CSF_DIR=$(mktemp -d /tmp/frw_r1cs_field.XXXXXX)
+/tmp/frw_r1cs_field_host_asan "$R1CSF_DIR" | tail -1
+rm -rf "$R1CSF_DIR"
 # the host side of the launchers (frw_launch.h: the variant dispatcher, the residency tables, the grid arithmetic): a program of its own
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -Werror -I "$ROOT/falcon-r1cs_amd/csrc" \
     -o /tmp/frw_launch_host_asan "$ROOT/tests/cpp/test_launch_host.cpp"

@@ -835,6 +835,24 @@ class WitnessEngine:
                                            _p(out[0]), _p(out[1]), _p(out[2]), _p(st)), "frw_prepare_inputs")
         return out[0], out[1], out[2], st
 
+    # the three steps of prepare_inputs one by one, on device buffers (torch tensors or raw pointers); not synchronised
+    def decode_signatures_dev(self, logn, batch, d_sig_bytes, sig_len, d_sig, d_nonce_out, d_status, stream=0):
+        """frw_decode_signatures_dev: d_sig_bytes uint8[batch, sig_len] -> d_sig uint16[batch, N], d_nonce_out uint8[batch, 40] (or None),
+        d_status int32[batch]: FRW_ST_OK or FRW_ST_DECODE.  The row of a refused signature is unspecified."""
+        check(self._lib.frw_decode_signatures_dev(self._ctx, int(logn), batch, _p(d_sig_bytes), int(sig_len), _p(d_sig), _p(d_nonce_out),
+                                                  _p(d_status), C.c_void_p(stream)), "frw_decode_signatures_dev")
+
+    def decode_public_keys_dev(self, logn, batch, d_pk_bytes, d_pk, d_status, stream=0):
+        """frw_decode_public_keys_dev: d_pk_bytes uint8[batch, PK_LEN[logn]] -> d_pk uint16[batch, N], d_status int32[batch]."""
+        check(self._lib.frw_decode_public_keys_dev(self._ctx, int(logn), batch, _p(d_pk_bytes), _p(d_pk), _p(d_status), C.c_void_p(stream)),
+              "frw_decode_public_keys_dev")
+
+    def hash_to_point_dev(self, logn, batch, d_nonces, d_msgs, d_msg_off, d_hm, stream=0):
+        """frw_hash_to_point_dev: d_nonces uint8[batch, 40], the messages as one blob d_msgs and its int64[batch + 1] non-decreasing offsets
+        d_msg_off -> d_hm uint16[batch, N]."""
+        check(self._lib.frw_hash_to_point_dev(self._ctx, int(logn), batch, _p(d_nonces), _p(d_msgs), _p(d_msg_off), _p(d_hm), C.c_void_p(stream)),
+              "frw_hash_to_point_dev")
+
     def gadget(self, kind, a, b=None, encoding=ENC_MONTGOMERY):
         """Stand-alone gadget blocks (frw_gadget): a = python ints; returns (blocks u64[count, BLK, 4], status)."""
         blk = self._lib.frw_gadget_block_len(kind)

@@ -6,6 +6,7 @@
 #define __device__
 #define __host__
 #define __global__
+#define __constant__
 #define __forceinline__ inline
 struct uint2 { uint32_t x, y; };
 struct uint4 { uint32_t x, y, z, w; };

@@ -89,6 +89,22 @@ class R1csfInfoStruct(C.Structure):
                 ("nnz", C.c_uint64 * 3), ("scratch_bytes_per_statement", C.c_uint64 * 2)]
 
 
+class FftFieldInfoStruct(C.Structure):
+    _fields_ = [("modulus", C.c_uint64 * 4), ("generator", C.c_uint64 * 4), ("two_adicity", C.c_uint32), ("reserved", C.c_uint32),
+                ("two_adic_root", C.c_uint64 * 4), ("two_adic_root_mont", C.c_uint64 * 4)]
+
+
+class QapfDomainStruct(C.Structure):
+    _fields_ = [("log_size", C.c_uint32), ("reserved", C.c_uint32), ("size", C.c_uint64), ("group_gen", C.c_uint64 * 4),
+                ("group_gen_inv", C.c_uint64 * 4), ("size_inv", C.c_uint64 * 4), ("generator_inv", C.c_uint64 * 4),
+                ("vanishing_inv", C.c_uint64 * 4)]
+
+
+class QapfInfoStruct(C.Structure):
+    _fields_ = [("domain", QapfDomainStruct), ("num_constraints", C.c_uint64), ("num_instance", C.c_uint64), ("num_passes", C.c_uint32),
+                ("reserved", C.c_uint32), ("workspace_bytes_per_statement", C.c_uint64)]
+
+
 class QapInfoStruct(C.Structure):
     _fields_ = [("log_domain_size", C.c_int32), ("domain_size", C.c_uint64), ("num_constraints", C.c_uint64),
                 ("num_instance", C.c_uint64), ("workspace_bytes_per_signature", C.c_uint64)]
@@ -229,6 +245,13 @@ PROTOTYPES = {
     "frw_r1csf_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t, C.c_int]),
     "frw_r1csf_check_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    "frw_fft_field_info": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FftFieldInfoStruct)]),
+    "frw_qapf_domain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(QapfDomainStruct)]),
+    "frw_qapf_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "frw_qapf_free": (None, [C.c_void_p]),
+    "frw_qapf_info": (C.c_int, [C.c_void_p, C.POINTER(QapfInfoStruct)]),
+    "frw_qapf_witness_map_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
     "frw_r1cs_load_aggregate": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_info": (C.c_int, [C.c_void_p, C.POINTER(R1csInfoStruct)]),
     "frw_aggregate_assign_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -277,3 +277,19 @@ inline bool r1csf_write(const FieldMatrices &m, const char *path)
 host::ConstraintMatrices r1cs_build_matrices(int circuit, int logn);
 
 }  // namespace frw
+
+// ---- the handle and the launch sequence, for the units that stand on them (frw_r1cs_field.hip, frw_qap_field.hip) --------------------
+#ifdef __HIPCC__
+struct frw_r1csf {
+    int device = 0;
+    frw::FieldDerived field{};
+    frw::R1csfDev dev{};
+    uint64_t nnz[3] = {0, 0, 0};
+    std::vector<void *> allocs;
+};
+namespace frw {
+// batch <= 32768.  Everything on `st`, nothing allocated, no synchronisation; first / abc may be null.
+hipError_t launch_r1csf_check(const R1csfDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance, uint32_t *num_unsatisfied,
+                              uint32_t *first_unsatisfied, uint64_t *abc, void *scratch, hipStream_t st);
+}  // namespace frw
+#endif

@@ -265,8 +265,8 @@ __global__ __launch_bounds__(BLOCK, FRW_R1CSF_WAVES) void r1csf_eval_kernel(R1cs
     }
 }
 
-// batch <= 32768.  Everything on `st`, nothing allocated, no synchronisation; first / abc may be null.
-static hipError_t launch_r1csf_check(const R1csfDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance, uint32_t *num_unsatisfied,
+// (declared in frw_r1cs_field.h: frw_qap_field.hip runs the same sequence)
+hipError_t launch_r1csf_check(const R1csfDev &r, size_t batch, const uint64_t *witness, const uint64_t *instance, uint32_t *num_unsatisfied,
                               uint32_t *first_unsatisfied, uint64_t *abc, void *scratch, hipStream_t st)
 {
     if (batch == 0) return hipSuccess;
@@ -294,14 +294,7 @@ static hipError_t launch_r1csf_check(const R1csfDev &r, size_t batch, const uint
 }  // namespace frw
 
 // ---- the handle ------------------------------------------------------------------------------------------------------------------
-struct frw_r1csf {
-    int device = 0;
-    frw::FieldDerived field{};
-    frw::R1csfDev dev{};
-    uint64_t nnz[3] = {0, 0, 0};
-    std::vector<void *> allocs;
-};
-
+// (struct frw_r1csf: frw_r1cs_field.h)
 extern "C" void frw_r1csf_free(frw_r1csf *r)
 {
     if (!r) return;

@@ -286,6 +286,54 @@ def field_info(p) -> FieldInfo:
     return FieldInfo(val(s.modulus), val(s.one), val(s.r2), int(s.ninv32), int(s.bits))
 
 
+def _val4(l):
+    return sum(int(v) << (64 * i) for i, v in enumerate(l))
+
+
+@dataclass(frozen=True)
+class FftFieldInfo:
+    modulus: int
+    generator: int
+    two_adicity: int         # s of p - 1 = 2^s t, t odd
+    two_adic_root: int       # generator^t
+    two_adic_root_mont: int  # ... x 2^256 mod p
+
+
+@dataclass(frozen=True)
+class QapfDomain:
+    log_size: int
+    size: int
+    group_gen: int
+    group_gen_inv: int
+    size_inv: int
+    generator_inv: int
+    vanishing_inv: int       # (generator^size - 1)^-1
+
+
+def _qapf_domain_of(s):
+    return QapfDomain(int(s.log_size), int(s.size), _val4(s.group_gen), _val4(s.group_gen_inv), _val4(s.size_inv), _val4(s.generator_inv),
+                      _val4(s.vanishing_inv))
+
+
+def fft_field_info(p, generator) -> FftFieldInfo:
+    """frw_fft_field_info (no device): the two-adicity of p and the root generator^t, what ark-ff's FftParameters lists; the generator
+    is the caller's (ark-bn254: 5, ark-bls12-381: 7, ark-bls12-377: 22, Pallas / Vesta: 5)."""
+    from ._lib import FftFieldInfoStruct
+    s = FftFieldInfoStruct()
+    check(load_library().frw_fft_field_info(_modulus(p, "frw_fft_field_info"), _modulus(generator, "frw_fft_field_info"), C.byref(s)),
+          "frw_fft_field_info")
+    return FftFieldInfo(_val4(s.modulus), _val4(s.generator), int(s.two_adicity), _val4(s.two_adic_root), _val4(s.two_adic_root_mont))
+
+
+def qapf_domain(p, generator, num_constraints, num_instance) -> QapfDomain:
+    """frw_qapf_domain (no device): ark-poly's Radix2EvaluationDomain::new(C + I) over p and the constants of the coset by the generator."""
+    from ._lib import QapfDomainStruct
+    s = QapfDomainStruct()
+    check(load_library().frw_qapf_domain(_modulus(p, "frw_qapf_domain"), _modulus(generator, "frw_qapf_domain"), num_constraints, num_instance,
+                                         C.byref(s)), "frw_qapf_domain")
+    return _qapf_domain_of(s)
+
+
 def expand_field_host(p, logn, compact):
     """frw_expand_field_host (no device): compact u8[batch, bytes_per_signature] -> (witness u64[batch, W, 4], instance
     u64[batch, I, 4]) with every element in Montgomery form over the modulus p."""
@@ -983,6 +1031,31 @@ class WitnessEngine:
         C z in Montgomery form over it.  Allocates nothing: d_scratch holds r1csf_scratch_bytes(handle, batch, d_abc is not None)."""
         check(self._lib.frw_r1csf_check_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_num_unsatisfied), _p(d_first_unsatisfied), _p(d_abc),
                                             _p(d_scratch), scratch_bytes, C.c_void_p(stream)), "frw_r1csf_check_dev")
+
+    # ---- the QAP witness map over the handle's field (frw_qapf_*) ----
+    def qapf_create(self, r1csf_handle, generator):
+        """The witness map of an r1csf_load* handle over its field's radix-2 domain, the coset by `generator`; the r1csf handle must
+        outlive this one.  Free with qapf_free."""
+        h = C.c_void_p()
+        check(self._lib.frw_qapf_create(r1csf_handle, _modulus(generator, "frw_qapf_create"), C.byref(h)), "frw_qapf_create")
+        return h
+
+    def qapf_free(self, handle):
+        self._lib.frw_qapf_free(handle)
+
+    def qapf_info(self, handle):
+        """-> the QapfInfoStruct: .domain (limbs; qapf_domain gives integers), num_constraints, num_instance, num_passes,
+        workspace_bytes_per_statement"""
+        from ._lib import QapfInfoStruct
+        q = QapfInfoStruct()
+        check(self._lib.frw_qapf_info(handle, C.byref(q)), "frw_qapf_info")
+        return q
+
+    def qapf_witness_map_dev(self, handle, batch, d_wit, d_inst, d_h, d_workspace, workspace_bytes, d_num_unsatisfied=None, stream=0):
+        """h = (A B - C) / (X^n - 1) of every statement over the handle's field: d_h int64[batch, n, 4], Montgomery form over p.
+        Allocates nothing; the batch goes through d_workspace in chunks of as many statements as it holds."""
+        check(self._lib.frw_qapf_witness_map_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_h), _p(d_num_unsatisfied), _p(d_workspace),
+                                                 workspace_bytes, C.c_void_p(stream)), "frw_qapf_witness_map_dev")
 
     def r1cs_load_aggregate(self, logns):
         """The constraint system of an aggregate statement: FalconNTTVerificationCircuit once per entry of `logns` (9 / 10, in

@@ -11,5 +11,5 @@ from .engine import (G_ADD_MOD, G_L2_ELEM, G_LESS_THAN_Q, G_MOD_Q, G_NORM_BOUND_
                      KEY_AUTO, KEY_TABLES, KEY_BARE, GROTH16_PARTIAL_WORDS, GROTH16_COMBINE_WORKSPACE, WitnessEngine, diag_pairing, diag_pairing_dev, compact_layout, layout, layout_dual, layout_schoolbook, circuit_layout, LayoutSchoolbook, CIRCUIT_NTT, CIRCUIT_DUAL_NTT, CIRCUIT_SCHOOLBOOK, RULE_CIRCUIT, RULE_SPEC, synth_triples,
                      WIRE_COMPRESSED, WIRE_UNCOMPRESSED, proof_wire_bytes, proofs_from_wire, proofs_from_wire_dev, proofs_to_wire, proofs_to_wire_dev, vk_to_wire,
                      PK_POINTS_ARE_CHECKED, groth16_pk_wire_bytes, groth16_pk_wire_info,
-                     ENC_FIELD_BASE, MAX_FIELDS, FieldInfo, field_info, expand_field_host, r1cs_export_field,
+                     ENC_FIELD_BASE, MAX_FIELDS, FieldInfo, field_info, expand_field_host, r1cs_export_field, FftFieldInfo, QapfDomain, fft_field_info, qapf_domain,
                      DRAW_BLINDING, DRAW_RERANDOMIZE, fr_draw, fr_draw_dev)

@@ -358,7 +358,8 @@ int frw_r1cs_load_file(int device, const char *path, frw_r1cs **out);
  * witness over any odd p with 2^160 < p < 2^255, and these calls say whether it satisfies the circuit -- cs.is_satisfied() and
  * which_is_unsatisfied() over that field -- and give A z, B z, C z, the three vectors a foreign-field prover's witness_map starts
  * from.  The modulus follows frw_field_info's rule (anything else: FRW_E_INVALID_ARG); BLS12-381's own group order is admissible.
- * A `frw_r1csf *` goes into these calls only: the QAP map, the keys and the provers take a `frw_r1cs *`, BLS12-381.
+ * A `frw_r1csf *` goes into these calls and into frw_qapf_create (the QAP witness map over that field, below) only: the hard-wired
+ * QAP map, the keys and the provers take a `frw_r1cs *`, BLS12-381.
  *
  * frw_r1cs_export_field / frw_r1csf_load: the matrices the host mirror emits (frw_r1cs_export), carried over to p.  Every
  * coefficient of the three Falcon circuits is an integer (+-1, powers of two, +-q, twiddle products, ladder offsets -- the inverses
@@ -402,6 +403,69 @@ size_t frw_r1csf_scratch_bytes(const frw_r1csf *r, size_t batch, int with_produc
 int frw_r1csf_check_dev(const frw_r1csf *r, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
                         uint32_t *d_num_unsatisfied, uint32_t *d_first_unsatisfied /* may be NULL */,
                         uint64_t *d_abc /* may be NULL: check only */, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* ---- the QAP witness map over ANY four-limb field with a radix-2 domain ------------------------------------------------------
+ * The step after A z, B z, C z in Groth16::prove over a field other than BLS12-381's: R1CStoQAP::witness_map,
+ * h(X) = (A(X) B(X) - C(X)) / (X^n - 1) over ark-poly's Radix2EvaluationDomain::new(C + I) of that field (the QAP map section below
+ * restates it).  A foreign-field MSM, key or prover is a curve port and is not here.
+ *
+ * frw_fft_field_info (no device): with p - 1 = 2^s t, t odd, two_adicity = s and two_adic_root = generator^t -- what ark-ff's
+ * FftParameters lists.  The multiplicative generator is the caller's (ark-bn254: 5, ark-bls12-381: 7, ark-bls12-377: 22, Pallas and
+ * Vesta: 5); the library hard-wires none.  FRW_E_INVALID_ARG, frw_last_error() naming the rule: a modulus outside frw_field_info's
+ * rule; a generator that is 0 or >= p; generator^(p - 1) != 1 (a failed Fermat test -- the inverses below are Fermat inverses, so this
+ * much primality is the library's business); root^(2^(s - 1)) != -1 (the generator is a square: the root has no order 2^s).
+ * frw_qapf_domain (no device): Radix2EvaluationDomain::new(C + I), every value canonical.  Refused: log_size > s (ark's
+ * PolynomialDegreeTooLarge), log_size > 22, generator^n = 1 (the coset is the domain itself and the division has no inverse).
+ *
+ * frw_qapf_create borrows `r` (r must outlive the handle) and makes the domain's tables on r's device; frw_qapf_witness_map_dev has the
+ * semantics of frw_qap_witness_map_dev:
+ *     d_h                uint64_t[batch][n][4], Montgomery form over p, canonical, coefficient k of h at index k
+ *     d_num_unsatisfied  optional uint32_t[batch]: the rows statement i violates (frw_r1csf_check_dev's count)
+ *     d_workspace        16-byte aligned, at least workspace_bytes_per_statement bytes (less: FRW_E_INVALID_ARG); the batch is processed
+ *                        in chunks of as many statements as it holds
+ * ark-groth16's seven transforms as written, for EVERY statement -- a = A z ++ instance, b = B z, c = C z; ifft; coset_fft by the
+ * generator; a o b - c; x vanishing_inv; coset_ifft -- so an unsatisfied witness gets ark's interpolant like a satisfied one (there is
+ * no six-transform quotient and no list mode over a foreign field).  A statement whose instance[0] is not 2^256 mod p reports
+ * num = C, as the check does, and its h slot is all zero.  Domains 2^1 .. 2^min(s, 22): up to 2^12 a workgroup keeps an array in LDS
+ * for a whole transform (num_passes = 1); 2^13 .. 2^16 take two passes over HBM, 2^17 .. 2^22 three.  Over p = BLS12-381's r with
+ * generator 7 the result is byte for byte frw_qap_witness_map_dev's.  Nothing is allocated and nothing synchronises: everything runs on
+ * `stream` as one chain without parallel branches, so the call may be captured.  batch = 0 returns FRW_OK before anything else is
+ * looked at.  Same canonical-limbs precondition as frw_r1csf_check_dev. */
+typedef struct {
+    uint64_t modulus[4];
+    uint64_t generator[4];
+    uint32_t two_adicity;              /* s */
+    uint32_t reserved;
+    uint64_t two_adic_root[4];         /* generator^t, canonical */
+    uint64_t two_adic_root_mont[4];    /* ... x 2^256 mod p: what ark-ff stores */
+} frw_fft_field_info_t;
+typedef struct {
+    uint32_t log_size;
+    uint32_t reserved;
+    uint64_t size;                     /* n = next_power_of_two(C + I) */
+    uint64_t group_gen[4];             /* the root squared s - log_size times */
+    uint64_t group_gen_inv[4];
+    uint64_t size_inv[4];
+    uint64_t generator_inv[4];
+    uint64_t vanishing_inv[4];         /* (generator^n - 1)^-1 */
+} frw_qapf_domain_t;
+typedef struct {
+    frw_qapf_domain_t domain;
+    uint64_t num_constraints, num_instance;    /* C, I */
+    uint32_t num_passes;               /* HBM passes one transform takes at this size */
+    uint32_t reserved;
+    uint64_t workspace_bytes_per_statement;
+} frw_qapf_info_t;
+typedef struct frw_qapf frw_qapf;
+int frw_fft_field_info(const uint64_t modulus[4], const uint64_t generator[4], frw_fft_field_info_t *out);
+int frw_qapf_domain(const uint64_t modulus[4], const uint64_t generator[4], uint64_t num_constraints, uint64_t num_instance,
+                    frw_qapf_domain_t *out);
+int frw_qapf_create(const frw_r1csf *r, const uint64_t generator[4], frw_qapf **out);
+void frw_qapf_free(frw_qapf *q);
+int frw_qapf_info(const frw_qapf *q, frw_qapf_info_t *out);
+int frw_qapf_witness_map_dev(const frw_qapf *q, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
+                             uint64_t *d_h, uint32_t *d_num_unsatisfied /* may be NULL */, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* ---- QAP witness map (the step after the hot path in a Groth16 prover) ------------------------------------------
  * examples/pok_sig.rs:30-47 hands the circuit to Groth16::<Bls12_381>::prove; after generate_constraints the prover's

@@ -132,6 +132,41 @@ pub struct frw_r1csf_info_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct frw_fft_field_info_t {
+    pub modulus: [u64; 4],
+    pub generator: [u64; 4],
+    pub two_adicity: u32,
+    pub reserved: u32,
+    pub two_adic_root: [u64; 4],
+    pub two_adic_root_mont: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_qapf_domain_t {
+    pub log_size: u32,
+    pub reserved: u32,
+    pub size: u64,
+    pub group_gen: [u64; 4],
+    pub group_gen_inv: [u64; 4],
+    pub size_inv: [u64; 4],
+    pub generator_inv: [u64; 4],
+    pub vanishing_inv: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_qapf_info_t {
+    pub domain: frw_qapf_domain_t,
+    pub num_constraints: u64,
+    pub num_instance: u64,
+    pub num_passes: u32,
+    pub reserved: u32,
+    pub workspace_bytes_per_statement: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct frw_qap_info_t {
     pub log_domain_size: i32,
     pub domain_size: u64,
@@ -150,6 +185,10 @@ pub struct frw_r1cs {
 }
 #[repr(C)]
 pub struct frw_r1csf {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct frw_qapf {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -294,6 +333,15 @@ extern "C" {
     pub fn frw_r1csf_check_dev(r: *const frw_r1csf, batch: usize, d_witness: *const u64, d_instance: *const u64,
                                d_num_unsatisfied: *mut u32, d_first_unsatisfied: *mut u32, d_abc: *mut u64, d_scratch: *mut c_void,
                                scratch_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_fft_field_info(modulus: *const u64, generator: *const u64, out: *mut frw_fft_field_info_t) -> c_int;
+    pub fn frw_qapf_domain(modulus: *const u64, generator: *const u64, num_constraints: u64, num_instance: u64,
+                           out: *mut frw_qapf_domain_t) -> c_int;
+    pub fn frw_qapf_create(r: *const frw_r1csf, generator: *const u64, out: *mut *mut frw_qapf) -> c_int;
+    pub fn frw_qapf_free(q: *mut frw_qapf);
+    pub fn frw_qapf_info(q: *const frw_qapf, out: *mut frw_qapf_info_t) -> c_int;
+    pub fn frw_qapf_witness_map_dev(q: *const frw_qapf, batch: usize, d_witness: *const u64, d_instance: *const u64, d_h: *mut u64,
+                                    d_num_unsatisfied: *mut u32, d_workspace: *mut c_void, workspace_bytes: usize,
+                                    stream: *mut c_void) -> c_int;
     pub fn frw_r1cs_load_aggregate(device: c_int, count: usize, logn: *const i32, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_info(r: *const frw_r1cs, out: *mut frw_r1cs_info_t) -> c_int;
     pub fn frw_aggregate_assign_dev(aggregate: *const frw_r1cs, d_witness_512: *const u64, d_instance_512: *const u64,

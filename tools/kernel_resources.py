@@ -42,7 +42,10 @@ HOT_WHOLE = {"frw_kernels.hip": {"frw::witness_ntt_verify_kernel<10, 1>": (0, 1)
              # the check over a run-time modulus: eight CIOS rounds with the modulus in scalar registers, no scratch; the long rows' kernel
              # holds four ten-limb sums and a field product (130 VGPRs: three waves per SIMD)
              "frw_r1cs_field.hip": {"frw::r1csf_eval_kernel<true>": (0, 4), "frw::r1csf_eval_kernel<false>": (0, 4),
-                                    "frw::r1csf_long_rows_kernel": (0, 3), "frw::r1csf_zsmall_kernel": (0, 8), "frw::r1csf_init_kernel": (0, 8)}}
+                                    "frw::r1csf_long_rows_kernel": (0, 3), "frw::r1csf_zsmall_kernel": (0, 8), "frw::r1csf_init_kernel": (0, 8)},
+             # the witness map over a run-time modulus: one pass kernel, eight wavefronts a workgroup; LDS sets the occupancy -- two 64 KiB
+             # tiles a CU (four waves per SIMD, 98 VGPRs), one 128 KiB array at 2^12 (two)
+             "frw_qap_field.hip": {"frw::qapf_pass_kernel<11>": (0, 4), "frw::qapf_pass_kernel<12>": (0, 2)}}
 
 FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
           ("LDS Size [bytes/block]", "lds"))

@@ -105,6 +105,20 @@ class QapfInfoStruct(C.Structure):
                 ("reserved", C.c_uint32), ("workspace_bytes_per_statement", C.c_uint64)]
 
 
+class CurveStruct(C.Structure):
+    _fields_ = [("base_modulus", C.c_uint64 * 4), ("scalar_modulus", C.c_uint64 * 4), ("b", C.c_uint64 * 4)]
+
+
+class CurveInfoStruct(C.Structure):
+    _fields_ = [("base_bits", C.c_uint32), ("scalar_bits", C.c_uint32), ("b_mont", C.c_uint64 * 4), ("one_mont", C.c_uint64 * 4),
+                ("scalar_one_mont", C.c_uint64 * 4)]
+
+
+class MsmfInfoStruct(C.Structure):
+    _fields_ = [("num_points", C.c_uint64), ("window_bits", C.c_uint32), ("num_windows", C.c_uint32), ("reserved", C.c_uint64),
+                ("bases_bytes", C.c_uint64), ("workspace_bytes_per_statement", C.c_uint64)]
+
+
 class QapInfoStruct(C.Structure):
     _fields_ = [("log_domain_size", C.c_int32), ("domain_size", C.c_uint64), ("num_constraints", C.c_uint64),
                 ("num_instance", C.c_uint64), ("workspace_bytes_per_signature", C.c_uint64)]
@@ -252,6 +266,15 @@ PROTOTYPES = {
     "frw_qapf_info": (C.c_int, [C.c_void_p, C.POINTER(QapfInfoStruct)]),
     "frw_qapf_witness_map_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    "frw_curve_info": (C.c_int, [C.POINTER(CurveStruct), C.POINTER(CurveInfoStruct)]),
+    "frw_curve_check_points": (C.c_int, [C.POINTER(CurveStruct), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64)]),
+    "frw_curve_scalar_mul": (C.c_int, [C.POINTER(CurveStruct), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_msmf_load": (C.c_int, [C.c_int, C.POINTER(CurveStruct), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_msmf_free": (None, [C.c_void_p]),
+    "frw_msmf_info": (C.c_int, [C.c_void_p, C.POINTER(MsmfInfoStruct)]),
+    "frw_msmf_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "frw_msmf_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                               C.c_void_p]),
     "frw_r1cs_load_aggregate": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_info": (C.c_int, [C.c_void_p, C.POINTER(R1csInfoStruct)]),
     "frw_aggregate_assign_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -500,6 +500,37 @@ inline AggregateProveBufs aggregate_prove_layout(void *ws, size_t count9, size_t
     b.bytes = c.off;
     return b;
 }
+// ---- the sum over a run-time curve (frw_msm_field.hip): a chunk of statements, W windows of 2^(C - 1) buckets each ------------------
+// keys = W 2^(C - 1) (window, bucket) pairs a statement; a fold level brings MSMF_FOLD (weighted, plain) pairs down to one.
+constexpr int MSMF_FOLD_LOG = 3, MSMF_FOLD = 1 << MSMF_FOLD_LOG;
+constexpr int MSMF_XYZZ_WORDS = 32;
+struct MsmfBufs {
+    uint32_t *counts;       // [statements][keys]        entries of a key          (zeroed at the head of a chunk)
+    uint32_t *offsets;      // [statements][keys]        where they start in the statement's entries
+    uint32_t *cursor;       // [statements][keys]        the scatter's next free place
+    uint32_t *entries;      // [statements][W n]         point index | sign << 31
+    int16_t *digits;        // [statements][W][n]
+    uint32_t *buckets;      // [statements][keys][32]    XYZZ
+    uint32_t *fold[2];      // [statements][keys / 8][2][32], [statements][keys / 64][2][32]: the levels alternate
+    size_t bytes;
+};
+inline MsmfBufs msmf_layout(void *ws, size_t statements, size_t n, int window_bits, int windows)
+{
+    MsmfBufs b{};
+    Carve c(ws);
+    const size_t keys = (size_t)windows << (window_bits - 1);
+    b.counts = c.take<uint32_t>(statements * keys * 4);
+    b.offsets = c.take<uint32_t>(statements * keys * 4);
+    b.cursor = c.take<uint32_t>(statements * keys * 4);
+    b.entries = c.take<uint32_t>(statements * windows * n * 4);
+    b.digits = c.take<int16_t>(statements * windows * n * 2);
+    b.buckets = c.take<uint32_t>(statements * keys * MSMF_XYZZ_WORDS * 4);
+    b.fold[0] = c.take<uint32_t>(statements * (keys >> MSMF_FOLD_LOG) * 2 * MSMF_XYZZ_WORDS * 4);
+    b.fold[1] = c.take<uint32_t>(statements * (keys >> 2 * MSMF_FOLD_LOG) * 2 * MSMF_XYZZ_WORDS * 4);
+    b.bytes = c.off;
+    return b;
+}
+
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)
 {

@@ -334,6 +334,60 @@ def qapf_domain(p, generator, num_constraints, num_instance) -> QapfDomain:
     return _qapf_domain_of(s)
 
 
+MSMF_POINTS_ARE_CHECKED = 1                         # frw.h FRW_MSMF_POINTS_ARE_CHECKED: skip the on-curve check of the bases at load
+
+
+@dataclass(frozen=True)
+class CurveInfo:
+    base_modulus: int
+    scalar_modulus: int
+    b: int
+    base_bits: int
+    scalar_bits: int
+    b_mont: int              # b 2^256 mod q
+    one_mont: int            # 2^256 mod q
+    scalar_one_mont: int     # 2^256 mod r
+
+
+def _curve(q, r, b, where):
+    from ._lib import CurveStruct
+    if b < 0 or b >> 256:
+        raise FrwError(-1, where, "b does not fit four limbs")
+    return CurveStruct(_modulus(q, where), _modulus(r, where), _limbs4(b))
+
+
+def curve_info(q, r, b) -> CurveInfo:
+    """frw_curve_info (no device): the descriptor of y^2 = x^3 + b over F_q with scalar modulus r, refused as frw.h lists (an
+    inadmissible q or r, b = 0, b >= q), and its Montgomery constants."""
+    from ._lib import CurveInfoStruct
+    s = CurveInfoStruct()
+    check(load_library().frw_curve_info(C.byref(_curve(q, r, b, "frw_curve_info")), C.byref(s)), "frw_curve_info")
+    return CurveInfo(int(q), int(r), int(b), int(s.base_bits), int(s.scalar_bits), _val4(s.b_mont), _val4(s.one_mont), _val4(s.scalar_one_mont))
+
+
+def curve_check_points(q, r, b, points):
+    """frw_curve_check_points (no device): points uint64[count, 8] (x then y, Montgomery limbs over q; all zero: infinity) -> the index
+    of the first one with a coordinate >= q or off the curve, or -1."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    bad = C.c_int64(0)
+    check(load_library().frw_curve_check_points(C.byref(_curve(q, r, b, "frw_curve_check_points")), pts.shape[0], _p(pts), C.byref(bad)),
+          "frw_curve_check_points")
+    return int(bad.value)
+
+
+def curve_scalar_mul(q, r, b, points, scalars):
+    """frw_curve_scalar_mul (no device): out[i] = scalars[i] points[i] by double-and-add, scalars uint64[count, 4] plain integers (any
+    value up to 2^256 - 1) -> uint64[count, 8]."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    ks = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    if pts.shape[0] != ks.shape[0]:
+        raise ValueError("one scalar per point")
+    out = np.zeros_like(pts)
+    check(load_library().frw_curve_scalar_mul(C.byref(_curve(q, r, b, "frw_curve_scalar_mul")), pts.shape[0], _p(pts), _p(ks), _p(out)),
+          "frw_curve_scalar_mul")
+    return out
+
+
 def expand_field_host(p, logn, compact):
     """frw_expand_field_host (no device): compact u8[batch, bytes_per_signature] -> (witness u64[batch, W, 4], instance
     u64[batch, I, 4]) with every element in Montgomery form over the modulus p."""
@@ -1056,6 +1110,37 @@ class WitnessEngine:
         Allocates nothing; the batch goes through d_workspace in chunks of as many statements as it holds."""
         check(self._lib.frw_qapf_witness_map_dev(handle, batch, _p(d_wit), _p(d_inst), _p(d_h), _p(d_num_unsatisfied), _p(d_workspace),
                                                  workspace_bytes, C.c_void_p(stream)), "frw_qapf_witness_map_dev")
+
+    # ---- the sum over a run-time curve y^2 = x^3 + b (frw_msmf_*) ----
+    def msmf_load(self, q, r, b, bases, flags=0):
+        """The bases of a multi-scalar multiplication on this engine's device: uint64[n, 8] affine points, Montgomery limbs over q, all
+        zero the point at infinity; every base is checked to be on the curve unless flags has MSMF_POINTS_ARE_CHECKED.  Free with
+        msmf_free."""
+        pts = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+        h = C.c_void_p()
+        check(self._lib.frw_msmf_load(self.device, C.byref(_curve(q, r, b, "frw_msmf_load")), pts.shape[0], _p(pts), int(flags), C.byref(h)),
+              "frw_msmf_load")
+        return h
+
+    def msmf_free(self, handle):
+        self._lib.frw_msmf_free(handle)
+
+    def msmf_info(self, handle):
+        """-> the MsmfInfoStruct: num_points, window_bits, num_windows, bases_bytes, workspace_bytes_per_statement"""
+        from ._lib import MsmfInfoStruct
+        m = MsmfInfoStruct()
+        check(self._lib.frw_msmf_info(handle, C.byref(m)), "frw_msmf_info")
+        return m
+
+    def msmf_workspace_bytes(self, handle, batch_in_flight):
+        return int(self._lib.frw_msmf_workspace_bytes(handle, int(batch_in_flight)))
+
+    def msmf_dev(self, handle, batch, d_scalars, scalar_stride, num_scalars, montgomery, d_out, d_workspace, workspace_bytes, stream=0):
+        """d_out[s] = sum_{i < num_scalars} k[s, i] P_i for every statement: d_scalars int64[batch, scalar_stride, 4] (plain integers, or with
+        `montgomery` ark-ff's form over r, as qapf_witness_map_dev writes h), d_out int64[batch, 8].  Allocates nothing; the batch goes
+        through d_workspace in chunks of as many statements as it holds."""
+        check(self._lib.frw_msmf_dev(handle, batch, _p(d_scalars), scalar_stride, num_scalars, 1 if montgomery else 0, _p(d_out), _p(d_workspace),
+                                     workspace_bytes, C.c_void_p(stream)), "frw_msmf_dev")
 
     def r1cs_load_aggregate(self, logns):
         """The constraint system of an aggregate statement: FalconNTTVerificationCircuit once per entry of `logns` (9 / 10, in

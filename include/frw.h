@@ -407,7 +407,7 @@ int frw_r1csf_check_dev(const frw_r1csf *r, size_t batch, const uint64_t *d_witn
 /* ---- the QAP witness map over ANY four-limb field with a radix-2 domain ------------------------------------------------------
  * The step after A z, B z, C z in Groth16::prove over a field other than BLS12-381's: R1CStoQAP::witness_map,
  * h(X) = (A(X) B(X) - C(X)) / (X^n - 1) over ark-poly's Radix2EvaluationDomain::new(C + I) of that field (the QAP map section below
- * restates it).  A foreign-field MSM, key or prover is a curve port and is not here.
+ * restates it).  The G1 sum over such a field's curve is frw_msmf_* (below); a foreign key or prover is not here.
  *
  * frw_fft_field_info (no device): with p - 1 = 2^s t, t odd, two_adicity = s and two_adic_root = generator^t -- what ark-ff's
  * FftParameters lists.  The multiplicative generator is the caller's (ark-bn254: 5, ark-bls12-381: 7, ark-bls12-377: 22, Pallas and
@@ -466,6 +466,61 @@ int frw_qapf_info(const frw_qapf *q, frw_qapf_info_t *out);
 int frw_qapf_witness_map_dev(const frw_qapf *q, size_t batch, const uint64_t *d_witness, const uint64_t *d_instance,
                              uint64_t *d_h, uint32_t *d_num_unsatisfied /* may be NULL */, void *d_workspace,
                              size_t workspace_bytes, void *stream);
+
+/* ---- multi-scalar multiplication over ANY four-limb curve y^2 = x^3 + b -----------------------------------------------------------
+ * The step after h in Groth16::prove over BN254 or a Pasta curve (and a KZG / IPA commitment on its own): VariableBaseMSM::
+ * multi_scalar_mul over G1.  A curve is {base modulus q, scalar modulus r, b}: a = 0, q and r each admissible by frw_field_info's rule
+ * (odd, 2^160 < . < 2^255), b canonical with 0 < b < q.  The library hard-wires no curve.  Primality of q and r and the group's order are
+ * the caller's business; r serves ONE purpose, bringing a Montgomery-form scalar back to its integer.  There is NO subgroup check: BN254
+ * G1, Pallas, Vesta and Grumpkin have cofactor 1; for any other curve it is the caller's.  G2 over a foreign Fq2, keys, pairings and a
+ * foreign prover are not here.
+ *
+ * A point is affine, uint64_t[8]: x then y, each four little-endian limbs of v 2^256 mod q (ark-ff's Fp256); all zero is the point at
+ * infinity (b != 0: (0, 0) is never on the curve).
+ *
+ * Host only, no device: frw_curve_info (the refusals of a descriptor, and its constants); frw_curve_check_points (*first_bad = the first
+ * point with a coordinate >= q or off the curve, -1: none); frw_curve_scalar_mul (out[i] = scalars[i] points[i] for plain 256-bit
+ * integers, ANY value up to 2^256 - 1, by double-and-add: the reference; a point off the curve is refused).
+ *
+ * frw_msmf_load copies the n <= 2^22 bases to `device` as they are -- 64 bytes a point, no window tables -- after one thread per base
+ * has checked it: a bad base refuses the load with FRW_E_INVALID_ARG and frw_last_error() names the first bad index;
+ * FRW_MSMF_POINTS_ARE_CHECKED skips the check.  frw_msmf_dev writes, per statement s < batch,
+ *     d_out[s] = sum_{i < num_scalars} k_(s,i) P_i        k_(s,i) = d_scalars[(s scalar_stride + i) 4 ..], four limbs
+ * as the unique affine point (infinity: all zero).  num_scalars <= num_points uses the first num_scalars bases: a key loaded once for a
+ * domain of n points serves h directly with scalar_stride = n, num_scalars = n - 1, which is what ark-groth16 sums.
+ *     montgomery = 0     k is a plain 256-bit integer: the integer multiple, for any value up to 2^256 - 1, no reduction by r
+ *     montgomery != 0    k is ark-ff's h 2^256 mod r (what frw_qapf_witness_map_dev writes), brought to the integer h < r first
+ *     d_workspace        16-byte aligned, at least workspace_bytes_per_statement bytes; the batch goes through it in chunks of as many
+ *                        statements as it holds (frw_msmf_workspace_bytes(m, k): what k statements in flight take)
+ * Stream-ordered, nothing allocated, no synchronisation, capturable.  batch = 0 and num_scalars = 0 are valid (the latter writes infinity).
+ * FRW_E_INVALID_ARG with a message: an inadmissible q or r, b = 0 or b >= q, num_points = 0 or > 2^22, num_scalars > num_points,
+ * scalar_stride < num_scalars, a workspace smaller than one statement's or a misaligned buffer, null pointers. */
+typedef struct { uint64_t base_modulus[4], scalar_modulus[4], b[4]; } frw_curve_t;
+typedef struct {
+    uint32_t base_bits, scalar_bits;   /* bit lengths of q and r */
+    uint64_t b_mont[4];                /* b 2^256 mod q */
+    uint64_t one_mont[4];              /* 2^256 mod q: a coordinate equal to one */
+    uint64_t scalar_one_mont[4];       /* 2^256 mod r: a Montgomery-form scalar equal to one */
+} frw_curve_info_t;
+typedef struct {
+    uint64_t num_points;
+    uint32_t window_bits, num_windows; /* 13 x 20 below 2^16 points, 15 x 18 from there on: signed digits, 2^(window_bits - 1) buckets a window */
+    uint64_t reserved;
+    uint64_t bases_bytes;              /* device memory the handle holds */
+    uint64_t workspace_bytes_per_statement;
+} frw_msmf_info_t;
+#define FRW_MSMF_POINTS_ARE_CHECKED 1
+typedef struct frw_msmf frw_msmf;
+int frw_curve_info(const frw_curve_t *c, frw_curve_info_t *out);
+int frw_curve_check_points(const frw_curve_t *c, size_t count, const uint64_t *points, int64_t *first_bad);
+int frw_curve_scalar_mul(const frw_curve_t *c, size_t count, const uint64_t *points, const uint64_t *scalars /* [count][4] */,
+                         uint64_t *out /* [count][8] */);
+int frw_msmf_load(int device, const frw_curve_t *c, size_t num_points, const uint64_t *bases, int flags, frw_msmf **out);
+void frw_msmf_free(frw_msmf *m);
+int frw_msmf_info(const frw_msmf *m, frw_msmf_info_t *out);
+size_t frw_msmf_workspace_bytes(const frw_msmf *m, size_t batch_in_flight);
+int frw_msmf_dev(const frw_msmf *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, size_t num_scalars, int montgomery,
+                 uint64_t *d_out /* [batch][8] */, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- QAP witness map (the step after the hot path in a Groth16 prover) ------------------------------------------
  * examples/pok_sig.rs:30-47 hands the circuit to Groth16::<Bls12_381>::prove; after generate_constraints the prover's

@@ -85,6 +85,8 @@ pub struct frw_compact_layout_t {
 /// encodings 16 .. 16 + FRW_MAX_FIELDS - 1: a field registered on the context (`frw_ctx_field_encoding`)
 pub const FRW_ENC_FIELD_BASE: c_int = 16;
 pub const FRW_MAX_FIELDS: c_int = 8;
+/// `frw_msmf_load`: the bases are known to be on the curve
+pub const FRW_MSMF_POINTS_ARE_CHECKED: c_int = 1;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -167,6 +169,35 @@ pub struct frw_qapf_info_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct frw_curve_t {
+    pub base_modulus: [u64; 4],
+    pub scalar_modulus: [u64; 4],
+    pub b: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_curve_info_t {
+    pub base_bits: u32,
+    pub scalar_bits: u32,
+    pub b_mont: [u64; 4],
+    pub one_mont: [u64; 4],
+    pub scalar_one_mont: [u64; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_msmf_info_t {
+    pub num_points: u64,
+    pub window_bits: u32,
+    pub num_windows: u32,
+    pub reserved: u64,
+    pub bases_bytes: u64,
+    pub workspace_bytes_per_statement: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct frw_qap_info_t {
     pub log_domain_size: i32,
     pub domain_size: u64,
@@ -189,6 +220,10 @@ pub struct frw_r1csf {
 }
 #[repr(C)]
 pub struct frw_qapf {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct frw_msmf {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -342,6 +377,16 @@ extern "C" {
     pub fn frw_qapf_witness_map_dev(q: *const frw_qapf, batch: usize, d_witness: *const u64, d_instance: *const u64, d_h: *mut u64,
                                     d_num_unsatisfied: *mut u32, d_workspace: *mut c_void, workspace_bytes: usize,
                                     stream: *mut c_void) -> c_int;
+    pub fn frw_curve_info(c: *const frw_curve_t, out: *mut frw_curve_info_t) -> c_int;
+    pub fn frw_curve_check_points(c: *const frw_curve_t, count: usize, points: *const u64, first_bad: *mut i64) -> c_int;
+    pub fn frw_curve_scalar_mul(c: *const frw_curve_t, count: usize, points: *const u64, scalars: *const u64, out: *mut u64) -> c_int;
+    pub fn frw_msmf_load(device: c_int, c: *const frw_curve_t, num_points: usize, bases: *const u64, flags: c_int,
+                         out: *mut *mut frw_msmf) -> c_int;
+    pub fn frw_msmf_free(m: *mut frw_msmf);
+    pub fn frw_msmf_info(m: *const frw_msmf, out: *mut frw_msmf_info_t) -> c_int;
+    pub fn frw_msmf_workspace_bytes(m: *const frw_msmf, batch_in_flight: usize) -> usize;
+    pub fn frw_msmf_dev(m: *const frw_msmf, batch: usize, d_scalars: *const u64, scalar_stride: usize, num_scalars: usize,
+                        montgomery: c_int, d_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_r1cs_load_aggregate(device: c_int, count: usize, logn: *const i32, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_info(r: *const frw_r1cs, out: *mut frw_r1cs_info_t) -> c_int;
     pub fn frw_aggregate_assign_dev(aggregate: *const frw_r1cs, d_witness_512: *const u64, d_instance_512: *const u64,

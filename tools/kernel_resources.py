@@ -45,7 +45,12 @@ HOT_WHOLE = {"frw_kernels.hip": {"frw::witness_ntt_verify_kernel<10, 1>": (0, 1)
                                     "frw::r1csf_long_rows_kernel": (0, 3), "frw::r1csf_zsmall_kernel": (0, 8), "frw::r1csf_init_kernel": (0, 8)},
              # the witness map over a run-time modulus: one pass kernel, eight wavefronts a workgroup; LDS sets the occupancy -- two 64 KiB
              # tiles a CU (four waves per SIMD, 98 VGPRs), one 128 KiB array at 2^12 (two)
-             "frw_qap_field.hip": {"frw::qapf_pass_kernel<11>": (0, 4), "frw::qapf_pass_kernel<12>": (0, 2)}}
+             "frw_qap_field.hip": {"frw::qapf_pass_kernel<11>": (0, 4), "frw::qapf_pass_kernel<12>": (0, 2)},
+             # the sum over a run-time curve: the bucket kernel's mixed addition (accumulator, point, temporaries: 126 VGPRs) at four waves
+             # per SIMD; the fold is a few thousand lanes of full additions and doublings, written for latency (one wave); each kernel at the waves it reaches
+             "frw_msm_field.hip": {"frw::msmf_check_kernel": (0, 7), "frw::msmf_clear_kernel": (0, 8), "frw::msmf_digits_kernel<13, 20>": (0, 8), "frw::msmf_digits_kernel<15, 18>": (0, 8),
+                                   "frw::msmf_scan_kernel": (0, 8), "frw::msmf_scatter_kernel": (0, 8), "frw::msmf_bucket_kernel": (0, 4),
+                                   "frw::msmf_fold_kernel": (0, 1), "frw::msmf_finish_kernel": (0, 3)}}
 
 FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
           ("LDS Size [bytes/block]", "lds"))

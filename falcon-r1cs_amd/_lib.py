@@ -119,6 +119,21 @@ class MsmfInfoStruct(C.Structure):
                 ("bases_bytes", C.c_uint64), ("workspace_bytes_per_statement", C.c_uint64)]
 
 
+class Curve2Struct(C.Structure):
+    _fields_ = [("base_modulus", C.c_uint64 * 4), ("scalar_modulus", C.c_uint64 * 4), ("nonresidue", C.c_uint64 * 4), ("b", C.c_uint64 * 8)]
+
+
+class Curve2InfoStruct(C.Structure):
+    _fields_ = [("base_bits", C.c_uint32), ("scalar_bits", C.c_uint32), ("b_mont", C.c_uint64 * 8), ("one_mont", C.c_uint64 * 4),
+                ("nonresidue_mont", C.c_uint64 * 4), ("scalar_one_mont", C.c_uint64 * 4), ("nonresidue_is_minus_one", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class Msmf2InfoStruct(C.Structure):
+    _fields_ = [("num_points", C.c_uint64), ("window_bits", C.c_uint32), ("num_windows", C.c_uint32), ("reserved", C.c_uint64),
+                ("bases_bytes", C.c_uint64), ("workspace_bytes_per_statement", C.c_uint64)]
+
+
 class QapInfoStruct(C.Structure):
     _fields_ = [("log_domain_size", C.c_int32), ("domain_size", C.c_uint64), ("num_constraints", C.c_uint64),
                 ("num_instance", C.c_uint64), ("workspace_bytes_per_signature", C.c_uint64)]
@@ -275,6 +290,15 @@ PROTOTYPES = {
     "frw_msmf_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "frw_msmf_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]),
+    "frw_curve2_info": (C.c_int, [C.POINTER(Curve2Struct), C.POINTER(Curve2InfoStruct)]),
+    "frw_curve2_check_points": (C.c_int, [C.POINTER(Curve2Struct), C.c_size_t, C.c_void_p, C.POINTER(C.c_int64)]),
+    "frw_curve2_scalar_mul": (C.c_int, [C.POINTER(Curve2Struct), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frw_msmf2_load": (C.c_int, [C.c_int, C.POINTER(Curve2Struct), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "frw_msmf2_free": (None, [C.c_void_p]),
+    "frw_msmf2_info": (C.c_int, [C.c_void_p, C.POINTER(Msmf2InfoStruct)]),
+    "frw_msmf2_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "frw_msmf2_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.c_void_p]),
     "frw_r1cs_load_aggregate": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "frw_r1cs_info": (C.c_int, [C.c_void_p, C.POINTER(R1csInfoStruct)]),
     "frw_aggregate_assign_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

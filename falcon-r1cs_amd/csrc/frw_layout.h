@@ -530,6 +530,35 @@ inline MsmfBufs msmf_layout(void *ws, size_t statements, size_t n, int window_bi
     b.bytes = c.off;
     return b;
 }
+// ---- the same sum over a curve on a run-time Fq2 (frw_msm_field2.hip): the schedule and the scalar side are msmf_layout's, an XYZZ
+// item is four Fe2 = 64 words -------------------------------------------------------------------------------------------------------
+constexpr int MSMF2_XYZZ_WORDS = 64;
+struct Msmf2Bufs {
+    uint32_t *counts;       // [statements][keys]
+    uint32_t *offsets;      // [statements][keys]
+    uint32_t *cursor;       // [statements][keys]
+    uint32_t *entries;      // [statements][W n]         point index | sign << 31
+    int16_t *digits;        // [statements][W][n]
+    uint32_t *buckets;      // [statements][keys][64]    XYZZ over Fe2
+    uint32_t *fold[2];      // [statements][keys / 8][2][64], [statements][keys / 64][2][64]: the levels alternate
+    size_t bytes;
+};
+inline Msmf2Bufs msmf2_layout(void *ws, size_t statements, size_t n, int window_bits, int windows)
+{
+    Msmf2Bufs b{};
+    Carve c(ws);
+    const size_t keys = (size_t)windows << (window_bits - 1);
+    b.counts = c.take<uint32_t>(statements * keys * 4);
+    b.offsets = c.take<uint32_t>(statements * keys * 4);
+    b.cursor = c.take<uint32_t>(statements * keys * 4);
+    b.entries = c.take<uint32_t>(statements * windows * n * 4);
+    b.digits = c.take<int16_t>(statements * windows * n * 2);
+    b.buckets = c.take<uint32_t>(statements * keys * MSMF2_XYZZ_WORDS * 4);
+    b.fold[0] = c.take<uint32_t>(statements * (keys >> MSMF_FOLD_LOG) * 2 * MSMF2_XYZZ_WORDS * 4);
+    b.fold[1] = c.take<uint32_t>(statements * (keys >> 2 * MSMF_FOLD_LOG) * 2 * MSMF2_XYZZ_WORDS * 4);
+    b.bytes = c.off;
+    return b;
+}
 
 // the most proofs in flight, up to `batch`, whose workspace size(k) fits `bytes` (0: not even one)
 template <class SizeFn> size_t proofs_in_flight(size_t batch, size_t bytes, SizeFn size)

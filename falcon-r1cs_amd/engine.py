@@ -388,6 +388,63 @@ def curve_scalar_mul(q, r, b, points, scalars):
     return out
 
 
+@dataclass(frozen=True)
+class Curve2Info:
+    base_modulus: int
+    scalar_modulus: int
+    nonresidue: int
+    b: tuple                 # (c0, c1)
+    base_bits: int
+    scalar_bits: int
+    b_mont: tuple            # (c0 2^256 mod q, c1 2^256 mod q)
+    one_mont: int            # 2^256 mod q
+    nonresidue_mont: int     # nonresidue 2^256 mod q
+    scalar_one_mont: int     # 2^256 mod r
+    nonresidue_is_minus_one: bool
+
+
+def _curve2(q, r, nonresidue, b, where):
+    from ._lib import Curve2Struct
+    b0, b1 = b
+    if min(nonresidue, b0, b1) < 0 or max(nonresidue, b0, b1) >> 256:
+        raise FrwError(-1, where, "the non-residue or a component of b does not fit four limbs")
+    return Curve2Struct(_modulus(q, where), _modulus(r, where), _limbs4(nonresidue), (C.c_uint64 * 8)(*_limbs4(b0), *_limbs4(b1)))
+
+
+def curve2_info(q, r, nonresidue, b) -> Curve2Info:
+    """frw_curve2_info (no device): the descriptor of y^2 = x^3 + b over Fq2 = Fq[u] / (u^2 - nonresidue), b = (c0, c1), with scalar
+    modulus r, refused as frw.h lists, and its Montgomery constants."""
+    from ._lib import Curve2InfoStruct
+    s = Curve2InfoStruct()
+    check(load_library().frw_curve2_info(C.byref(_curve2(q, r, nonresidue, b, "frw_curve2_info")), C.byref(s)), "frw_curve2_info")
+    return Curve2Info(int(q), int(r), int(nonresidue), (int(b[0]), int(b[1])), int(s.base_bits), int(s.scalar_bits),
+                      (_val4(s.b_mont[:4]), _val4(s.b_mont[4:])), _val4(s.one_mont), _val4(s.nonresidue_mont), _val4(s.scalar_one_mont),
+                      bool(s.nonresidue_is_minus_one))
+
+
+def curve2_check_points(q, r, nonresidue, b, points):
+    """frw_curve2_check_points (no device): points uint64[count, 16] (x.c0, x.c1, y.c0, y.c1, Montgomery limbs over q; all zero:
+    infinity) -> the index of the first one with a component >= q or off the curve, or -1."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 16)
+    bad = C.c_int64(0)
+    check(load_library().frw_curve2_check_points(C.byref(_curve2(q, r, nonresidue, b, "frw_curve2_check_points")), pts.shape[0], _p(pts),
+                                                 C.byref(bad)), "frw_curve2_check_points")
+    return int(bad.value)
+
+
+def curve2_scalar_mul(q, r, nonresidue, b, points, scalars):
+    """frw_curve2_scalar_mul (no device): out[i] = scalars[i] points[i] by double-and-add, scalars uint64[count, 4] plain integers (any
+    value up to 2^256 - 1) -> uint64[count, 16]."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 16)
+    ks = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    if pts.shape[0] != ks.shape[0]:
+        raise ValueError("one scalar per point")
+    out = np.zeros_like(pts)
+    check(load_library().frw_curve2_scalar_mul(C.byref(_curve2(q, r, nonresidue, b, "frw_curve2_scalar_mul")), pts.shape[0], _p(pts), _p(ks),
+                                               _p(out)), "frw_curve2_scalar_mul")
+    return out
+
+
 def expand_field_host(p, logn, compact):
     """frw_expand_field_host (no device): compact u8[batch, bytes_per_signature] -> (witness u64[batch, W, 4], instance
     u64[batch, I, 4]) with every element in Montgomery form over the modulus p."""
@@ -1141,6 +1198,35 @@ class WitnessEngine:
         through d_workspace in chunks of as many statements as it holds."""
         check(self._lib.frw_msmf_dev(handle, batch, _p(d_scalars), scalar_stride, num_scalars, 1 if montgomery else 0, _p(d_out), _p(d_workspace),
                                      workspace_bytes, C.c_void_p(stream)), "frw_msmf_dev")
+
+    # ---- the same sum over G2: a curve y^2 = x^3 + b' over a run-time Fq2 (frw_msmf2_*) ----
+    def msmf2_load(self, q, r, nonresidue, b, bases, flags=0):
+        """The bases of a multi-scalar multiplication over Fq2 = Fq[u] / (u^2 - nonresidue) on this engine's device: uint64[n, 16] affine
+        points (x.c0, x.c1, y.c0, y.c1; Montgomery limbs over q), all zero the point at infinity; every base is checked to be on the curve
+        unless flags has MSMF_POINTS_ARE_CHECKED.  There is no subgroup check.  Free with msmf2_free."""
+        pts = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 16)
+        h = C.c_void_p()
+        check(self._lib.frw_msmf2_load(self.device, C.byref(_curve2(q, r, nonresidue, b, "frw_msmf2_load")), pts.shape[0], _p(pts), int(flags),
+                                       C.byref(h)), "frw_msmf2_load")
+        return h
+
+    def msmf2_free(self, handle):
+        self._lib.frw_msmf2_free(handle)
+
+    def msmf2_info(self, handle):
+        """-> the Msmf2InfoStruct: num_points, window_bits, num_windows, bases_bytes, workspace_bytes_per_statement"""
+        from ._lib import Msmf2InfoStruct
+        m = Msmf2InfoStruct()
+        check(self._lib.frw_msmf2_info(handle, C.byref(m)), "frw_msmf2_info")
+        return m
+
+    def msmf2_workspace_bytes(self, handle, batch_in_flight):
+        return int(self._lib.frw_msmf2_workspace_bytes(handle, int(batch_in_flight)))
+
+    def msmf2_dev(self, handle, batch, d_scalars, scalar_stride, num_scalars, montgomery, d_out, d_workspace, workspace_bytes, stream=0):
+        """d_out[s] = sum_{i < num_scalars} k[s, i] Q_i for every statement: msmf_dev's contract, d_out int64[batch, 16]."""
+        check(self._lib.frw_msmf2_dev(handle, batch, _p(d_scalars), scalar_stride, num_scalars, 1 if montgomery else 0, _p(d_out), _p(d_workspace),
+                                      workspace_bytes, C.c_void_p(stream)), "frw_msmf2_dev")
 
     def r1cs_load_aggregate(self, logns):
         """The constraint system of an aggregate statement: FalconNTTVerificationCircuit once per entry of `logns` (9 / 10, in

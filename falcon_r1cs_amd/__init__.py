@@ -13,4 +13,5 @@ from .engine import (G_ADD_MOD, G_L2_ELEM, G_LESS_THAN_Q, G_MOD_Q, G_NORM_BOUND_
                      PK_POINTS_ARE_CHECKED, groth16_pk_wire_bytes, groth16_pk_wire_info,
                      ENC_FIELD_BASE, MAX_FIELDS, FieldInfo, field_info, expand_field_host, r1cs_export_field, FftFieldInfo, QapfDomain, fft_field_info, qapf_domain,
                      MSMF_POINTS_ARE_CHECKED, CurveInfo, curve_info, curve_check_points, curve_scalar_mul,
+                     Curve2Info, curve2_info, curve2_check_points, curve2_scalar_mul,
                      DRAW_BLINDING, DRAW_RERANDOMIZE, fr_draw, fr_draw_dev)

@@ -472,8 +472,8 @@ int frw_qapf_witness_map_dev(const frw_qapf *q, size_t batch, const uint64_t *d_
  * multi_scalar_mul over G1.  A curve is {base modulus q, scalar modulus r, b}: a = 0, q and r each admissible by frw_field_info's rule
  * (odd, 2^160 < . < 2^255), b canonical with 0 < b < q.  The library hard-wires no curve.  Primality of q and r and the group's order are
  * the caller's business; r serves ONE purpose, bringing a Montgomery-form scalar back to its integer.  There is NO subgroup check: BN254
- * G1, Pallas, Vesta and Grumpkin have cofactor 1; for any other curve it is the caller's.  G2 over a foreign Fq2, keys, pairings and a
- * foreign prover are not here.
+ * G1, Pallas, Vesta and Grumpkin have cofactor 1; for any other curve it is the caller's.  The same sum over G2 is frw_msmf2_* (below); foreign
+ * keys, pairings and a foreign prover are not here.
  *
  * A point is affine, uint64_t[8]: x then y, each four little-endian limbs of v 2^256 mod q (ark-ff's Fp256); all zero is the point at
  * infinity (b != 0: (0, 0) is never on the curve).
@@ -521,6 +521,57 @@ int frw_msmf_info(const frw_msmf *m, frw_msmf_info_t *out);
 size_t frw_msmf_workspace_bytes(const frw_msmf *m, size_t batch_in_flight);
 int frw_msmf_dev(const frw_msmf *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, size_t num_scalars, int montgomery,
                  uint64_t *d_out /* [batch][8] */, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- multi-scalar multiplication over G2: a curve y^2 = x^3 + b' over a run-time Fq2 --------------------------------------------------
+ * What a Groth16 prover over BN254 sums for B in G2 (b_g2_query), and what a loader of such a key checks: VariableBaseMSM::
+ * multi_scalar_mul over a curve on the quadratic extension Fq2 = Fq[u] / (u^2 - nonresidue).  A curve is {base modulus q, scalar modulus
+ * r, nonresidue, b' = c0 + c1 u}: q and r as frw_curve_t's, 0 < nonresidue < q, both components of b' canonical below q and b' != 0.
+ * nonresidue = q - 1 (u^2 = -1: BN254, BLS12-381) is recognised and costs no product; any other value costs one more field product per
+ * Fq2 product.  The library hard-wires no curve.  THE CALLER'S BUSINESS, none of it checked: that nonresidue is a quadratic non-residue
+ * mod q (otherwise Fq2 is no field and the inversions are wrong), that q and r are prime, the group's order, and the SUBGROUP -- the
+ * twist of a pairing-friendly curve has a cofactor (BN254's G2: 2 q - r), and there is NO subgroup check here.  r serves ONE purpose,
+ * bringing a Montgomery-form scalar back to its integer.  Foreign keys, pairings and a foreign prover are not here.
+ *
+ * A point is affine, uint64_t[16]: x.c0, x.c1, y.c0, y.c1 (ark-ff's Fp2 order), each four little-endian limbs of v 2^256 mod q; all zero
+ * is the point at infinity.
+ *
+ * Host only, no device: frw_curve2_info, frw_curve2_check_points (*first_bad = the first point with a component >= q or off the curve,
+ * -1: none), frw_curve2_scalar_mul (plain 256-bit integers, ANY value, double-and-add: the reference; a point off the curve is refused).
+ *
+ * frw_msmf2_load / _free / _info / _workspace_bytes / _dev are frw_msmf_*'s contract word for word -- the scalars, scalar_stride,
+ * num_scalars, montgomery, the chunking through d_workspace, the 16-byte alignment, batch = 0 and num_scalars = 0, stream order and
+ * capture -- with 128 bytes a base and d_out uint64_t[batch][16].  FRW_MSMF_POINTS_ARE_CHECKED skips the on-curve check of the load.
+ * FRW_E_INVALID_ARG with a message: an inadmissible q or r, nonresidue = 0 or >= q, a component of b' >= q or b' = 0, num_points = 0 or
+ * > 2^22, num_scalars > num_points, scalar_stride < num_scalars, a workspace smaller than one statement's or a misaligned buffer, null
+ * pointers, a base that is not on the curve (named by its index). */
+typedef struct { uint64_t base_modulus[4], scalar_modulus[4], nonresidue[4], b[8]; } frw_curve2_t;   /* b = c0 then c1, canonical */
+typedef struct {
+    uint32_t base_bits, scalar_bits;   /* bit lengths of q and r */
+    uint64_t b_mont[8];                /* b' 2^256 mod q, c0 then c1 */
+    uint64_t one_mont[4];              /* 2^256 mod q: the c0 of a coordinate equal to one */
+    uint64_t nonresidue_mont[4];       /* nonresidue 2^256 mod q */
+    uint64_t scalar_one_mont[4];       /* 2^256 mod r */
+    uint32_t nonresidue_is_minus_one;  /* 1: u^2 = -1, the cheaper products */
+    uint32_t reserved;
+} frw_curve2_info_t;
+typedef struct {
+    uint64_t num_points;
+    uint32_t window_bits, num_windows; /* 13 x 20 below 2^16 points, 15 x 18 from there on */
+    uint64_t reserved;
+    uint64_t bases_bytes;              /* device memory the handle holds */
+    uint64_t workspace_bytes_per_statement;
+} frw_msmf2_info_t;
+typedef struct frw_msmf2 frw_msmf2;
+int frw_curve2_info(const frw_curve2_t *c, frw_curve2_info_t *out);
+int frw_curve2_check_points(const frw_curve2_t *c, size_t count, const uint64_t *points /* [count][16] */, int64_t *first_bad);
+int frw_curve2_scalar_mul(const frw_curve2_t *c, size_t count, const uint64_t *points, const uint64_t *scalars /* [count][4] */,
+                          uint64_t *out /* [count][16] */);
+int frw_msmf2_load(int device, const frw_curve2_t *c, size_t num_points, const uint64_t *bases, int flags, frw_msmf2 **out);
+void frw_msmf2_free(frw_msmf2 *m);
+int frw_msmf2_info(const frw_msmf2 *m, frw_msmf2_info_t *out);
+size_t frw_msmf2_workspace_bytes(const frw_msmf2 *m, size_t batch_in_flight);
+int frw_msmf2_dev(const frw_msmf2 *m, size_t batch, const uint64_t *d_scalars, size_t scalar_stride, size_t num_scalars, int montgomery,
+                  uint64_t *d_out /* [batch][16] */, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- QAP witness map (the step after the hot path in a Groth16 prover) ------------------------------------------
  * examples/pok_sig.rs:30-47 hands the circuit to Groth16::<Bls12_381>::prove; after generate_constraints the prover's

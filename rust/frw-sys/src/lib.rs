@@ -198,6 +198,40 @@ pub struct frw_msmf_info_t {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct frw_curve2_t {
+    pub base_modulus: [u64; 4],
+    pub scalar_modulus: [u64; 4],
+    pub nonresidue: [u64; 4],
+    /// c0 then c1, canonical
+    pub b: [u64; 8],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_curve2_info_t {
+    pub base_bits: u32,
+    pub scalar_bits: u32,
+    pub b_mont: [u64; 8],
+    pub one_mont: [u64; 4],
+    pub nonresidue_mont: [u64; 4],
+    pub scalar_one_mont: [u64; 4],
+    pub nonresidue_is_minus_one: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct frw_msmf2_info_t {
+    pub num_points: u64,
+    pub window_bits: u32,
+    pub num_windows: u32,
+    pub reserved: u64,
+    pub bases_bytes: u64,
+    pub workspace_bytes_per_statement: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct frw_qap_info_t {
     pub log_domain_size: i32,
     pub domain_size: u64,
@@ -224,6 +258,10 @@ pub struct frw_qapf {
 }
 #[repr(C)]
 pub struct frw_msmf {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct frw_msmf2 {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -387,6 +425,16 @@ extern "C" {
     pub fn frw_msmf_workspace_bytes(m: *const frw_msmf, batch_in_flight: usize) -> usize;
     pub fn frw_msmf_dev(m: *const frw_msmf, batch: usize, d_scalars: *const u64, scalar_stride: usize, num_scalars: usize,
                         montgomery: c_int, d_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn frw_curve2_info(c: *const frw_curve2_t, out: *mut frw_curve2_info_t) -> c_int;
+    pub fn frw_curve2_check_points(c: *const frw_curve2_t, count: usize, points: *const u64, first_bad: *mut i64) -> c_int;
+    pub fn frw_curve2_scalar_mul(c: *const frw_curve2_t, count: usize, points: *const u64, scalars: *const u64, out: *mut u64) -> c_int;
+    pub fn frw_msmf2_load(device: c_int, c: *const frw_curve2_t, num_points: usize, bases: *const u64, flags: c_int,
+                          out: *mut *mut frw_msmf2) -> c_int;
+    pub fn frw_msmf2_free(m: *mut frw_msmf2);
+    pub fn frw_msmf2_info(m: *const frw_msmf2, out: *mut frw_msmf2_info_t) -> c_int;
+    pub fn frw_msmf2_workspace_bytes(m: *const frw_msmf2, batch_in_flight: usize) -> usize;
+    pub fn frw_msmf2_dev(m: *const frw_msmf2, batch: usize, d_scalars: *const u64, scalar_stride: usize, num_scalars: usize,
+                         montgomery: c_int, d_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn frw_r1cs_load_aggregate(device: c_int, count: usize, logn: *const i32, out: *mut *mut frw_r1cs) -> c_int;
     pub fn frw_r1cs_info(r: *const frw_r1cs, out: *mut frw_r1cs_info_t) -> c_int;
     pub fn frw_aggregate_assign_dev(aggregate: *const frw_r1cs, d_witness_512: *const u64, d_instance_512: *const u64,

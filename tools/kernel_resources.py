@@ -50,7 +50,13 @@ HOT_WHOLE = {"frw_kernels.hip": {"frw::witness_ntt_verify_kernel<10, 1>": (0, 1)
              # per SIMD; the fold is a few thousand lanes of full additions and doublings, written for latency (one wave); each kernel at the waves it reaches
              "frw_msm_field.hip": {"frw::msmf_check_kernel": (0, 7), "frw::msmf_clear_kernel": (0, 8), "frw::msmf_digits_kernel<13, 20>": (0, 8), "frw::msmf_digits_kernel<15, 18>": (0, 8),
                                    "frw::msmf_scan_kernel": (0, 8), "frw::msmf_scatter_kernel": (0, 8), "frw::msmf_bucket_kernel": (0, 4),
-                                   "frw::msmf_fold_kernel": (0, 1), "frw::msmf_finish_kernel": (0, 3)}}
+                                   "frw::msmf_fold_kernel": (0, 1), "frw::msmf_finish_kernel": (0, 3)},
+             # the same sum over a run-time Fq2: every accumulator is a column of LDS, the registers hold an addition's temporaries -- the
+             # bucket kernel at two waves per SIMD (252 VGPRs; its 64 KiB of LDS a workgroup allow no more), fold and finish written for
+             # latency (one wave); the check is load-time only; no scratch anywhere
+             "frw_msm_field2.hip": {"frw::msmf2_check_kernel": (0, 2), "frw::msmf2_clear_kernel": (0, 8), "frw::msmf2_digits_kernel<13, 20>": (0, 8),
+                                    "frw::msmf2_digits_kernel<15, 18>": (0, 8), "frw::msmf2_scan_kernel": (0, 8), "frw::msmf2_scatter_kernel": (0, 8),
+                                    "frw::msmf2_bucket_kernel": (0, 2), "frw::msmf2_fold_kernel": (0, 1), "frw::msmf2_finish_kernel": (0, 1)}}
 
 FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
           ("LDS Size [bytes/block]", "lds"))
